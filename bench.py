@@ -2,16 +2,26 @@
 """bench.py -- BASELINE.json's metric on MI355X: rows/s + achieved HBM GB/s of the hot path.
 
   python bench.py --gpus N --steps K --warmup W [--workload all|sort|sorted_order|join|groupby|reduce|scan|gather]
-                  [--rows R] [--cpu-baseline/--no-cpu-baseline]
+                  [--rows R] [--full] [--dump-outputs DIR] [--cpu-baseline/--no-cpu-baseline]
 
 A "step" is one pass of the hot path over one batch of synthetic input already resident in HBM (generated on
 the device by a counter-based RNG: no PCIe traffic inside or outside the timed region).
 
 Default (N = 1, --workload all): the headline `value` is BASELINE.json configs[1], the 1e9-row int64 radix sort
-(cudf::sort), timed as K steps between barriers; the SAME JSON line then carries a `join` block (configs[2]:
-1e9-row probe x 1e8-row build inner hash join, probe phase timed, build time reported) and a `groupby` block
-(configs[3]: 1e9 rows, int32 key, 1e6 groups, f64 sum + count), each timed over its own K steps with its own
-`roofline`, `cpu_baseline` and a device-side correctness guard on the timed output.
+(cudf::sort), timed as K steps between barriers.  A plain run does nothing else: set-up, W warm-up steps, the K
+timed steps, the result line (and the outputs under --dump-outputs).
+
+--full: the same headline, then everything else the benchmark measures and checks.  With --workload all the SAME JSON
+line carries a `sorted_order` block, a `join` block (configs[2]: 1e9-row probe x 1e8-row build inner hash join, probe
+phase timed, build time reported) and a `groupby` block (configs[3]: 1e9 rows, int32 key, 1e6 groups, f64 sum +
+count), each timed over its own K steps with its own `roofline`, `cpu_baseline` and a device-side correctness guard
+on the timed output; the headline gets its `roofline`, `cpu_baseline` and guard as well, and `sort_robustness`,
+`sorted_order_robustness` and `through_cpp` follow.
+
+--dump-outputs DIR (sort workloads on one GPU): after the timed steps, what the last step returned to its caller as
+DIR/<name>.npy in float64 -- every row up to 2^21 rows, else the rows at 2^21 seeded positions, one in each of 2^21
+equal ranges.  int64 keys are split into exact halves (`sorted_keys_hi32` = key >> 32, `sorted_keys_lo32` = the low 32
+bits).  The inputs are seeded, so two builds run with the same arguments can be compared file by file.
 
 N > 1: one process per GPU (torch.distributed / RCCL over xGMI).  `python bench.py --gpus N` spawns the N ranks
 itself (and fails when fewer devices are visible); under torchrun (RANK / WORLD_SIZE set) it joins the group it
@@ -99,23 +109,37 @@ def parse():
                          "1-rank group on one GPU: what `--gpus N` executes, testable where only one device is visible")
     ap.add_argument("--preflight-only", action="store_true", help="multi-GPU: run the oracle-checked pre-flight of the sharded operators, print its verdict as one JSON line, exit")
     ap.add_argument("--preflight-timeout", type=float, default=90.0, help="multi-GPU: seconds the watchdog gives one pre-flight operator call")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline, everything else the benchmark measures and checks: the sorted_order / join / groupby "
+                         "blocks of --workload all, CPU baselines, per-kernel roofline figures, guards on the timed output, the "
+                         "robustness distributions and the C++-surface ratios.  Off: set-up, warm-up, the timed steps, the result line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step returned (sort workloads, one GPU) as DIR/<name>.npy in float64; "
+                         "more than 2^21 rows: a fixed seeded sample of 2^21 of them")
     ap.add_argument("--through-cpp", dest="through_cpp", action="store_true", default=None,
                     help="also time cudf::sort / sorted_order / hash_join::inner_join / groupby::aggregate through the C++ surface "
                          "(tests/cpp/cudf_api_bench, default pooled mr) and report the ratio to the C-ABI numbers; default: on for "
-                         "--workload all on one GPU (the driver's line), off otherwise")
+                         "--full --workload all on one GPU, off otherwise")
     ap.add_argument("--no-through-cpp", dest="through_cpp", action="store_false")
     ap.add_argument("--robustness", dest="robustness", action="store_true", default=None,
                     help="sort the same 1e9 rows on other VALUE DISTRIBUTIONS (bell-shaped, lognormal, Zipf-like, two clusters, keys around zero, "
                          "the reference benchmark's [100, 10001), a hot value) and report each time and its ratio to the uniform line; "
-                         "default: on for --workload all on one GPU (the driver's line)")
+                         "default: on for --full --workload all on one GPU")
     ap.add_argument("--no-robustness", dest="robustness", action="store_false")
-    ap.add_argument("--cpu-baseline", dest="cpu", action="store_true", default=True)
+    ap.add_argument("--cpu-baseline", dest="cpu", action="store_true", default=None, help="default: on with --full, off otherwise")
     ap.add_argument("--no-cpu-baseline", dest="cpu", action="store_false")
     ap.add_argument("--cpu-rows", type=float, default=0, help="rows of the CPU-baseline sample (0 = per-workload default)")
     ap.add_argument("--cpu-rows-pandas", type=float, default=0,
                     help="rows of the pandas / pyarrow legs; 0 = per-leg default: sort 1e8 and groupby 1e8 (BASELINE.md section 3's "
                          "larger size, ~15 s per library), join 1e7 (pandas.merge at 1e8 probe rows takes minutes)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if args.dump_outputs and (args.workload not in ("all", "sort", "sorted_order") or args.gpus > 1 or args.force_sharded):
+        ap.error("--dump-outputs writes the output of the sort workloads (all, sort, sorted_order) on one GPU")
+    if args.cpu is None:
+        args.cpu = args.full
+    return args
 
 
 # ------------------------------------------------------------------------------------------------
@@ -600,11 +624,38 @@ def pmc_traffic(roofline, n):
         roofline["traffic_note"] = f"no committed PMC file for this build ({type(ex).__name__})"
 
 
+DUMP_ROWS = 1 << 21   # rows per --dump-outputs file: int64 keys make two files of 16 MB, inside the 64-MB budget
+
+
+def dump_rows(n, m=DUMP_ROWS, seed=2026):
+    """the rows --dump-outputs writes: all n up to m, else one seeded position in each of m equal ranges (ascending, the same every run)"""
+    import numpy as np
+    if n <= m:
+        return np.arange(n, dtype=np.int64)
+    edges = np.arange(m + 1, dtype=np.int64) * n // m
+    return edges[:-1] + np.random.default_rng(seed).integers(0, edges[1:] - edges[:-1])
+
+
+def dump_outputs(c, col, dt):
+    """--dump-outputs: the column the timed path returned (dtype dt), at the rows of dump_rows(), as float64 .npy files; int64
+    values are split into two exact halves, since float64 holds 53 bits"""
+    np = c.np
+    t = c.as_tensor(col, dt)
+    v = t[c.torch.from_numpy(dump_rows(col.size)).to(t.device)].cpu().numpy()
+    if dt == c.torch.int64:
+        files = {"sorted_keys_hi32": v >> 32, "sorted_keys_lo32": v & 0xFFFFFFFF}
+    else:
+        files = {"sorted_order" if dt == c.torch.int32 else "sorted_keys": v}
+    os.makedirs(c.args.dump_outputs, exist_ok=True)
+    for name, a in files.items():
+        np.save(os.path.join(c.args.dump_outputs, name + ".npy"), a.astype(np.float64))
+
+
 # ------------------------------------------------------------------------------------------------
 # config 2: radix sort
 # ------------------------------------------------------------------------------------------------
 
-def bench_sort(c, pairs=False, cpu_leg=True):
+def bench_sort(c, pairs=False, cpu_leg=True, dump=False):
     a, lib, L, ops, np = c.args, c.lib, c.L, c.ops, c.np
     n = c.n
     lib.gx_sort_set_algorithm(a.algo)
@@ -747,10 +798,21 @@ def bench_sort(c, pairs=False, cpu_leg=True):
         read_profile()
         nsteps_prof = 1
     else:
-        # the timed steps carry the two events around the FIRST partition level only (gx_sort_profile(2)): an event between two kernels
-        # costs the stream ~15 us and the full set is 23 per sort -- 0.35 ms of an 11-ms step that no caller of cudf::sort pays.  The
-        # other kernels' durations come from ONE more call with every event, outside the timed region (`kernels_ms_note`).
-        sec = c.timed(single_step, after_warmup=lambda: lib.gx_sort_profile(2), slot=lib.gx_sort_profile_slot, read_slot=read_profile)
+        if a.full:
+            # the timed steps carry the two events around the FIRST partition level only (gx_sort_profile(2)): an event between two kernels
+            # costs the stream ~15 us and the full set is 23 per sort -- 0.35 ms of an 11-ms step that no caller of cudf::sort pays.  The
+            # other kernels' durations come from ONE more call with every event, outside the timed region (`kernels_ms_note`).
+            sec = c.timed(single_step, after_warmup=lambda: lib.gx_sort_profile(2), slot=lib.gx_sort_profile_slot, read_slot=read_profile)
+        else:
+            sec = c.timed(single_step)   # a plain run: no event inside the timed steps, they serve the roofline of --full only
+        if dump:
+            dump_outputs(c, out, c.torch.int32 if pairs else (c.torch.float64 if is_f64 else c.torch.int64))
+        if not a.full:
+            st = ctypes.c_int(0)
+            lib.gx_sort_status(c.ptr(tmp), ctypes.byref(st), c.stream)
+            assert st.value == 0, "look-back timed out"
+            return {"workload": workload, "rows": n, "ms_per_step": sec * 1e3, "rows_per_s": n * c.world / sec, "dtype": "f64" if is_f64 else "int64",
+                    "roofline": None, "cpu_baseline": None, "checked": None}
         nsteps_prof = a.steps
         live_l0 = prof["hyb"][0] / prof["hyb_n"] if prof["hyb_n"] else None
         prof.update({"pass_ms": 0.0, "hist_ms": 0.0, "launches": 0, "hyb": [0.0] * 4, "hyb_n": 0})
@@ -1506,6 +1568,7 @@ def sort_robustness(c, uniform_ms):
     for name, kw in cases:
         a = copy.copy(a0)
         a.steps, a.warmup, a.key_dist, a.key_range, a.hot_copies, a.key_type = 3, 1, "uniform", None, 0, "int64"
+        a.full = True   # the guard of every case, and its path from the profiled call
         for k, v in kw.items():
             setattr(a, k, v)
         c.args = a
@@ -1544,6 +1607,7 @@ def sorted_order_robustness(c, uniform_ms):
     for name, kw in cases:
         a = copy.copy(a0)
         a.steps, a.warmup, a.key_dist, a.key_range, a.hot_copies, a.key_type = 3, 1, "uniform", None, 0, "int64"
+        a.full = True   # the guard of every case, and its path from the profiled call
         for k, v in kw.items():
             setattr(a, k, v)
         c.args = a
@@ -1591,8 +1655,8 @@ def main():
             bad = [k for k in ("sort_fused", "sort_sample", "join", "groupby") if not str(c.preflight.get(k, "")).startswith("ok")]
             sys.exit(1 if bad else 0)
     if wl in ("all", "sort", "sorted_order"):
-        head = bench_sort(c, pairs=(wl == "sorted_order"))
-        if wl == "all":
+        head = bench_sort(c, pairs=(wl == "sorted_order"), dump=bool(args.dump_outputs))
+        if wl == "all" and args.full:
             if not c.sharded:  # cudf::sorted_order, what the reference's sort benchmark times (cpp/benchmarks/sort/sort.cpp:16-58): its own block
                 c.torch.cuda.empty_cache()
                 blocks["sorted_order"] = bench_sort(c, pairs=True, cpu_leg=False)
@@ -1615,7 +1679,7 @@ def main():
     if c.rank == 0:
         line = {
             "metric": METRIC, "value": head["rows_per_s"], "unit": "rows/s", "n_gpus": c.world, "steps": args.steps,
-            "warmup": args.warmup, "ms_per_step": head["ms_per_step"], "higher_is_better": True, "scaling": "weak",
+            "warmup": args.warmup, "ms_per_step": head["ms_per_step"], "higher_is_better": True, "scaling": "weak", "full": args.full,
             "vs_baseline": None, "dtype": head["dtype"], "data": "synthetic",
             "config": {"workload": head["workload"], "rows_per_gpu": c.n, "algo": args.algo, "gb_algo": args.gb_algo, "gb_spec": args.gb_spec, "gb_pbits": args.gb_pbits, "gb_keys": args.gb_keys,
                        "parallelism": (f"{c.world} ranks, row shards, one all-to-all exchange per step (RCCL over xGMI)"
@@ -1634,14 +1698,14 @@ def main():
                           **({"build_ms": b["build_ms"], "build_call_ms": b.get("build_call_ms"), "build_plus_probe_ms": b.get("build_plus_probe_ms"),
                               "build_rows_per_s": b.get("build_rows_per_s"), "partition_bits": b["partition_bits"], "join_keys": b.get("join_keys"),
                               "partition_mode": b.get("partition_mode")} if "build_ms" in b else {})}
-        want_rb = args.robustness if args.robustness is not None else (wl == "all" and c.n >= 100_000_000)
+        want_rb = args.robustness if args.robustness is not None else (args.full and wl == "all" and c.n >= 100_000_000)
         if want_rb and not c.sharded and wl in ("all", "sort"):
             line["sort_robustness"] = sort_robustness(c, head["ms_per_step"])
             if "sorted_order" in line:
                 line["sorted_order_robustness"] = sorted_order_robustness(c, line["sorted_order"]["ms_per_step"])
         if args.robustness and not c.sharded and wl == "sorted_order":
             line["sorted_order_robustness"] = sorted_order_robustness(c, head["ms_per_step"])
-        want_cpp = args.through_cpp if args.through_cpp is not None else (wl == "all" and c.n >= 100_000_000)
+        want_cpp = args.through_cpp if args.through_cpp is not None else (args.full and wl == "all" and c.n >= 100_000_000)
         if want_cpp and not c.sharded:
             blk = lambda name: (blocks.get(name) or (head if wl == name else {})).get("ms_per_step")
             line["through_cpp"] = through_cpp(args, c, head["ms_per_step"] if wl in ("all", "sort") else None, blk("sorted_order"),

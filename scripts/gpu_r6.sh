@@ -6,9 +6,9 @@
 #   suite                           the whole -m gpu suite
 #   cpp                             tests/cpp/cudf_api_tests through tests/test_cpp_api.py
 #   joinab:<xp,xp,...>              bench.py --workload join for each --join-xp value (A/B on one box)
-#   sortab:<dist,dist,...>          bench.py --workload sort --key-dist <d> on the tree's library, then on scripts/xp/bin/libcudf_amd_oldsort.so, then the tree's again
-#   bench:<workload>[:extra args]   bench.py --workload <w> --no-cpu-baseline <extra>
-#   default                         the driver-style default line (all legs)
+#   sortab:<dist,dist,...>          bench.py --full --workload sort --key-dist <d> on the tree's library, then on scripts/xp/bin/libcudf_amd_oldsort.so, then the tree's again
+#   bench:<workload>[:extra args]   bench.py --full --workload <w> --no-cpu-baseline <extra>
+#   default                         bench.py --full: the headline line with all its legs
 #   steps:<rows>                    scripts/xp/xp_gxd_steps.py <rows>  (forced-exchange single-rank steps of the sharded operators)
 #   profsteps:<rows>                rocprofv3 --kernel-trace --stats summary of scripts/xp/xp_gxd_steps.py <rows>
 #   xp:<file.hip>[:args]            hipcc + run a micro-benchmark under scripts/xp/
@@ -63,12 +63,12 @@ PY
     sortab)
       # same-box A/B of two builds of the kernel library: the tree's, then scripts/xp/bin/libcudf_amd_oldsort.so (a build with another gx_sort.hip)
       out=$O/r6_${TAG}_sort_ab.txt
-      echo "# round 6 $TAG: python bench.py --workload sort --no-cpu-baseline --no-robustness --no-through-cpp --key-dist <d>; ms per step, 1e9 int64 keys" >> $out
+      echo "# round 6 $TAG: python bench.py --full --workload sort --no-cpu-baseline --no-robustness --no-through-cpp --key-dist <d>; ms per step, 1e9 int64 keys" >> $out
       for variant in new old new2; do
         [ $variant = old ] && { cp cudf_amd/libcudf_amd.so /tmp/libcudf_amd_new.so; cp scripts/xp/bin/libcudf_amd_oldsort.so cudf_amd/libcudf_amd.so; }
         [ $variant = new2 ] && cp /tmp/libcudf_amd_new.so cudf_amd/libcudf_amd.so
         for d in ${rest//,/ }; do
-          timeout 300 python bench.py --workload sort --no-cpu-baseline --no-robustness --no-through-cpp --key-dist $d > $O/r6_${TAG}_sortab_${variant}_$d.jsonl 2>> $O/r6_${TAG}.log
+          timeout 300 python bench.py --full --workload sort --no-cpu-baseline --no-robustness --no-through-cpp --key-dist $d > $O/r6_${TAG}_sortab_${variant}_$d.jsonl 2>> $O/r6_${TAG}.log
           python - "$O/r6_${TAG}_sortab_${variant}_$d.jsonl" $variant $d <<'PY' | tee -a $out
 import json, sys
 try:
@@ -83,10 +83,10 @@ PY
     bench)
       wl=${rest%%:*}; extra=${rest#*:}; [ "$extra" = "$rest" ] && extra=""
       f=$O/r6_${TAG}_bench_${wl}$(echo "$extra" | tr -c 'A-Za-z0-9\n' '_').jsonl
-      timeout 600 python bench.py --workload $wl --no-cpu-baseline $extra > $f 2>> $O/r6_${TAG}.log
+      timeout 600 python bench.py --full --workload $wl --no-cpu-baseline $extra > $f 2>> $O/r6_${TAG}.log
       last_json $f | cut -c1-600 ;;
     default)
-      ( time timeout 900 python bench.py ) > $O/r6_${TAG}_bench_default.jsonl 2>> $O/r6_${TAG}.log
+      ( time timeout 900 python bench.py --full ) > $O/r6_${TAG}_bench_default.jsonl 2>> $O/r6_${TAG}.log
       last_json $O/r6_${TAG}_bench_default.jsonl | cut -c1-1500 ;;
     steps)
       timeout 900 python scripts/xp/xp_gxd_steps.py ${rest:-1e9} 2>&1 | grep -v "^\[W\|amdgpu.ids" > $O/r6_${TAG}_single_rank_steps_${rest:-1e9}.txt
@@ -124,11 +124,11 @@ PY
       ( echo "# round 6 $TAG: rocprofv3 --kernel-trace --pmc <SQ counters, two passes> -- python bench.py --workload $wl --rows 1e9 --steps 1 --warmup 0 --no-cpu-baseline $extra"; cat $O/pmc_sq_${wl}_summary.txt ) > $O/r6_${TAG}_pmc_sq_${wl}.txt
       grep -A17 "scatter\|probe_pipe\|k_hf_scatter\|k_local_place" $O/r6_${TAG}_pmc_sq_${wl}.txt | head -80 ;;
     evidence)
-      ( time timeout 900 python bench.py ) > $O/r6_${TAG}_bench_default.jsonl 2>> $O/r6_${TAG}.log
-      timeout 300 python bench.py --workload sorted_order --no-cpu-baseline > $O/r6_${TAG}_bench_sorted_order.jsonl 2>> $O/r6_${TAG}.log
-      (cd /tmp && timeout 600 rocprofv3 --kernel-trace --stats -d "$ROOT/$O/prof_default" -o default -- python "$ROOT/bench.py" --no-cpu-baseline --no-robustness --no-through-cpp) > $O/r6_${TAG}_bench_under_rocprof.jsonl 2>> $O/r6_${TAG}.log
+      ( time timeout 900 python bench.py --full ) > $O/r6_${TAG}_bench_default.jsonl 2>> $O/r6_${TAG}.log
+      timeout 300 python bench.py --full --workload sorted_order --no-cpu-baseline > $O/r6_${TAG}_bench_sorted_order.jsonl 2>> $O/r6_${TAG}.log
+      (cd "$TMPDIR" && timeout 600 rocprofv3 --kernel-trace --stats -d "$ROOT/$O/prof_default" -o default -- python "$ROOT/bench.py" --full --no-cpu-baseline --no-robustness --no-through-cpp) > $O/r6_${TAG}_bench_under_rocprof.jsonl 2>> $O/r6_${TAG}.log
       db=$(find $O/prof_default -name "*.db" | head -1)
-      [ -n "$db" ] && python scripts/rocprof_summary.py "$db" "round 6 $TAG: rocprofv3 --kernel-trace --stats -- python bench.py --no-cpu-baseline --no-robustness --no-through-cpp (sort + sorted_order + join + groupby, 5 steps + 2 warm-up each)" | head -60 | cut -c1-190 > $O/r6_${TAG}_default_kernel_stats.txt
+      [ -n "$db" ] && python scripts/rocprof_summary.py "$db" "round 6 $TAG: rocprofv3 --kernel-trace --stats -- python bench.py --full --no-cpu-baseline --no-robustness --no-through-cpp (sort + sorted_order + join + groupby, 5 steps + 2 warm-up each)" | head -60 | cut -c1-190 > $O/r6_${TAG}_default_kernel_stats.txt
       find $O/prof_default -name "*.db" -delete
       pmc() { local wl=$1 ctr=$2; local lc=$(echo $ctr | tr 'A-Z' 'a-z')
         (cd /tmp && timeout 300 rocprofv3 --kernel-trace --pmc $ctr -d "$ROOT/$O/pmc_${wl}_${lc}" -o $wl --output-format csv -- python "$ROOT/bench.py" --workload $wl --rows 1e9 --steps 1 --warmup 0 --no-cpu-baseline) >> $O/r6_${TAG}.log 2>&1; }

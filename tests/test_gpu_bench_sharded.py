@@ -49,7 +49,7 @@ def test_sharded_lines_single_rank_forced_exchange():
     """the `--gpus N` line itself (sort head + join + groupby blocks) in a 1-rank group: the full-size guards -- shard order over
     the ranks, pair count, the hit rows, EVERY pair's keys fetched from the owners of its global rows, group totals -- execute and
     pass, and the line carries the pre-flight verdict"""
-    r, line = _run(["--force-sharded", "--rows", "40000000", "--steps", "1", "--warmup", "1", "--no-cpu-baseline"], 900)
+    r, line = _run(["--force-sharded", "--rows", "40000000", "--steps", "1", "--warmup", "1", "--full", "--no-cpu-baseline"], 900)
     assert r.returncode == 0, r.stderr[-3000:]
     _assert_preflight_ok(line["preflight"], 1)
     assert "C++ operators over RCCL" in line["config"]["workload"]
@@ -75,7 +75,7 @@ def test_sharded_lines_two_ranks_over_rccl():
     import torch
     if torch.cuda.device_count() < 2:
         pytest.skip("needs two GPUs (the driver's multi-GPU box)")
-    r, line = _run(["--gpus", "2", "--rows", "40000000", "--steps", "1", "--warmup", "1", "--no-cpu-baseline"], 1200)
+    r, line = _run(["--gpus", "2", "--rows", "40000000", "--steps", "1", "--warmup", "1", "--full", "--no-cpu-baseline"], 1200)
     assert r.returncode == 0, r.stderr[-3000:]
     _assert_preflight_ok(line["preflight"], 2)
     assert line["n_gpus"] == 2
