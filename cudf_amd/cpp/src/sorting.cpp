@@ -75,6 +75,19 @@ void table_sorted_order(table_view const& keys, std::vector<order> const& column
   detail::post_sort_status(tmp, stream);
 }
 
+// one pass of the loop over the columns below: the stable argsort of ONE key column under the row comparator.  A DESCENDING float
+// column without nulls must not take the radix argsort -- its NaN block comes out in REVERSE row order there (the single-column rule of
+// sorted_order_radix.cu:37-48), which would undo the order the less significant columns set among tied NaN rows; the k = 1 table order
+// keeps equal NaNs in row order.  Every other column: the radix argsort already is the comparator order (validity split with nulls).
+void lsd_pass_order(column_view const& col, order ord, null_order nulls, int32_t* out, rmm::cuda_stream_view stream)
+{
+  if (ord == order::DESCENDING && is_floating_point(col.type()) && !col.has_nulls()) {
+    table_sorted_order(table_view{std::vector<column_view>{col}}, {ord}, out, stream);
+    return;
+  }
+  column_sorted_order(col, ord, nulls, out, stream);
+}
+
 std::unique_ptr<column> gather_column(column_view const& src, int32_t const* map, size_type n, bool nullify,
                                       rmm::cuda_stream_view stream, rmm::device_async_resource_ref mr)
 {
@@ -120,17 +133,17 @@ std::unique_ptr<column> sorted_order_impl(table_view const& input, std::vector<o
     return result;
   }
   // Lexicographic order of several columns = LSD over the columns: stable sorts from the least to
-  // the most significant column, each on the column gathered through the order so far.
+  // the most significant column, each on the column gathered through the order so far, each under the comparator (lsd_pass_order).
   rmm::device_uvector<int32_t> perm(n, stream), order_so_far(n, stream);
   bool first = true;
   for (size_type c = input.num_columns() - 1; c >= 0; --c) {
     if (first) {
-      column_sorted_order(input.column(c), ord(c), nulls(c), order_so_far.data(), stream);
+      lsd_pass_order(input.column(c), ord(c), nulls(c), order_so_far.data(), stream);
       first = false;
       continue;
     }
     auto gathered = gather_column(input.column(c), order_so_far.data(), n, false, stream, cudf::get_current_device_resource_ref());
-    column_sorted_order(gathered->view(), ord(c), nulls(c), perm.data(), stream);
+    lsd_pass_order(gathered->view(), ord(c), nulls(c), perm.data(), stream);
     // order_so_far = order_so_far[perm]
     rmm::device_uvector<int32_t> next(n, stream);
     detail::gx_check(gx_gather(4, order_so_far.data(), nullptr, n, perm.data(), n, 0, next.data(), nullptr, detail::gxs(stream)),
@@ -174,7 +187,9 @@ std::unique_ptr<column> stable_sorted_order(table_view const& input, std::vector
 // cudf::is_sorted (src/sort/is_sorted.cu:27-86).  One integer column without nulls: one streaming pass that counts the adjacent pairs
 // out of order (gx_checksum's violation count: NaN the greatest value, as the sort's comparator has it).  Everything else -- several
 // columns, nulls -- through the STABLE argsort: the rows are in order exactly when that argsort is the identity (equal rows keep
-// their places in a stable sort, and any adjacent pair out of order moves), compared with an iota on the device.
+// their places in a stable sort, and any adjacent pair out of order moves), compared with an iota on the device.  One float column
+// without nulls: the k = 1 table order, not the radix argsort, whose DESCENDING NaN block is in reverse row order (so that
+// {NaN, NaN, 1.0} would not be the identity).
 bool is_sorted(table_view const& in, std::vector<order> const& column_order, std::vector<null_order> const& null_precedence,
                rmm::cuda_stream_view stream)
 {
@@ -197,7 +212,14 @@ bool is_sorted(table_view const& in, std::vector<order> const& column_order, std
     stream.synchronize();
     return h[2] == 0;
   }
-  auto const ord = stable_sorted_order(in, column_order, null_precedence, stream, cudf::get_current_device_resource_ref());
+  std::unique_ptr<column> ord;
+  if (in.num_columns() == 1 && table_path_column(in.column(0)) && is_floating_point(in.column(0).type())) {
+    ord = make_numeric_column(data_type{type_id::INT32}, n, mask_state::UNALLOCATED, stream, cudf::get_current_device_resource_ref());
+    detail::throw_pending_sort_faults();
+    table_sorted_order(in, column_order, ord->mutable_view().data<int32_t>(), stream);
+  } else {
+    ord = stable_sorted_order(in, column_order, null_precedence, stream, cudf::get_current_device_resource_ref());
+  }
   rmm::device_uvector<int32_t> iota(n, stream);
   detail::gx_check(gx_sequence_i32(iota.data(), n, 0, detail::gxs(stream)), "is_sorted");
   rmm::device_uvector<int64_t> bad(1, stream);

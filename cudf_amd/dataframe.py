@@ -93,7 +93,12 @@ class DataFrame:
             col = self._cols[name] if order is None else ops.gather(self._cols[name], order)
             # NullOrder mapping of core/_internals/sorting.py:83-90: null_before = asc ^ (na == "last")
             null_before = a ^ (na_position == "last")
-            perm = ops.sorted_order(col, ascending=a, null_before=null_before)
+            if len(keys) >= 2 and not a and col.dtype.kind == "f" and not col.has_nulls():
+                # a DESCENDING float key without nulls: the comparator order (NaN rows tied, in row order), not the single-column radix
+                # argsort, whose NaN block comes out in reverse row order and would undo the less significant keys' order among them
+                perm = ops.sorted_order_table([col], [a])
+            else:
+                perm = ops.sorted_order(col, ascending=a, null_before=null_before)
             order = perm if order is None else ops.gather(order, perm)
         return self._take(order)
 

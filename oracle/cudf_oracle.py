@@ -139,6 +139,51 @@ def sorted_order_table(cols: Sequence[np.ndarray], ascending=True) -> np.ndarray
     return np.lexsort(tuple(reversed(keys))).astype(np.int32)
 
 
+def _per_column(x, k, default):
+    if x is None:
+        return [default] * k
+    if isinstance(x, (bool, np.bool_)):
+        return [bool(x)] * k
+    x = list(x)
+    assert len(x) == k
+    return x
+
+
+def sorted_order_rows(cols: Sequence[np.ndarray], valids=None, ascending=True, null_before=True) -> np.ndarray:
+    """cudf::stable_sorted_order of a TABLE -> int32 row indices: the rows sorted stably under the lexicographic row comparator
+    (cpp/src/sort/sort_impl.cuh:61-93), nulls included.  Per column a row's key is (null placement, sortable_bits), inverted as a whole
+    for a DESCENDING column: NaN equivalent to each other and greater than every number, -0.0 == +0.0
+    (row_operator/common_utils.cuh:157-169); nulls equivalent to each other and first iff null_before != descending, the placement of
+    sorted_order above (sort_column_impl.cuh:42-45).  Rows equal on the whole tuple keep their row order.  This is the order of every
+    multi-column entry point (sort, sort_by_key, is_sorted, segmented sorts) -- NOT the single-column radix path's reverse-row-order
+    rule for a DESCENDING NaN block, which only cudf::sorted_order / rank / top_k of ONE column follow (sorted_order above)."""
+    cols = [np.asarray(c) for c in cols]
+    k = len(cols)
+    assert k >= 1
+    n = len(cols[0])
+    valids = _per_column(valids, k, None)
+    asc = _per_column(ascending, k, True)
+    nb = _per_column(null_before, k, True)
+    keys = [np.arange(n, dtype=np.int64)]  # np.lexsort: the LAST key is the primary one; the row breaks whole-tuple ties
+    for c, v, a, b in reversed(list(zip(cols, valids, asc, nb))):
+        assert len(c) == n
+        ok = np.ones(n, bool) if v is None else np.asarray(v, bool)
+        bits = sortable_bits(c)
+        bits = bits if a else ~bits
+        bits = np.where(ok, bits, bits.dtype.type(0))  # nulls are all equivalent
+        nulls_first = b != (not a)
+        place = np.where(ok, 1, 0) if nulls_first else np.where(ok, 0, 1)
+        keys += [bits, place.astype(np.uint8)]
+    return np.lexsort(tuple(keys)).astype(np.int32)
+
+
+def is_sorted_rows(cols: Sequence[np.ndarray], valids=None, ascending=True, null_before=True) -> bool:
+    """cudf::is_sorted (cpp/src/sort/is_sorted.cu:27-86): no adjacent pair of rows out of order under the comparator, i.e. the stable
+    comparator order is the identity"""
+    order = sorted_order_rows(cols, valids, ascending, null_before)
+    return bool(np.array_equal(order, np.arange(len(order))))
+
+
 def sort_by_key(values: Sequence[np.ndarray], keys: np.ndarray, key_valid=None, ascending=True,
                 null_before=True):
     """cudf::sort_by_key = gather(values, sorted_order(keys)) (cpp/src/sort/sort.cu:31-50)."""
@@ -919,14 +964,14 @@ def top_k(values, k: int, descending=True, valid=None):
 def segmented_sorted_order(key_cols, offsets, valids=None, ascending=None, null_before=None):
     """cudf::stable_segmented_sorted_order (cpp/src/sort/segmented_sort_impl.cuh:178-203,265-293): every row gets a
     segment id -- rows of [offsets[j], offsets[j+1]) share one, rows outside every segment each their own, ascending
-    with the row -- and the table (segment id, keys...) is sorted lexicographically and stably.  Defaults: all
-    ASCENDING, nulls BEFORE (sorting.hpp:33-38)."""
+    with the row -- and the table (segment id, keys...) is sorted lexicographically and stably under the row comparator
+    (sorted_order_rows).  Defaults: all ASCENDING, nulls BEFORE (sorting.hpp:33-38)."""
     cols = [np.asarray(c) for c in key_cols]
     n = len(cols[0])
     nc = len(cols)
-    valids = [None] * nc if valids is None else valids
-    ascending = [True] * nc if ascending is None else ascending
-    null_before = [True] * nc if null_before is None else null_before
+    valids = _per_column(valids, nc, None)
+    ascending = _per_column(ascending, nc, True)
+    null_before = _per_column(null_before, nc, True)
     offsets = np.asarray(offsets, np.int64)
     ids = np.arange(n, dtype=np.int64)  # rows outside every segment: unique, in place
     for j in range(len(offsets) - 1):
@@ -935,13 +980,7 @@ def segmented_sorted_order(key_cols, offsets, valids=None, ascending=None, null_
         ids[: offsets[0]] = np.arange(offsets[0])
         tail = np.arange(offsets[-1], n)
         ids[offsets[-1] :] = tail + 1 if len(tail) else tail
-    order = np.arange(n, dtype=np.int64)
-    for c in range(nc - 1, -1, -1):  # LSD over the columns, each pass stable
-        ok = np.ones(n, bool) if valids[c] is None else np.asarray(valids[c], bool)
-        sub = sorted_order(cols[c][order], ok[order], ascending[c], null_before[c]).astype(np.int64)
-        order = order[sub]
-    order = order[np.argsort(ids[order], kind="stable")]
-    return order.astype(np.int32)
+    return sorted_order_rows([ids] + cols, [None] + list(valids), [True] + list(ascending), [True] + list(null_before))
 
 
 def join_match_counts(left, right, kind: str = "inner", left_valid=None, right_valid=None, nulls_equal=True):

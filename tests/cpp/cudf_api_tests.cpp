@@ -1685,6 +1685,14 @@ int main()
     CHECK(is_sorted(table_view{{f->view()}}, {O::ASCENDING}, {}));
     auto g = make_col<double>({-1.0, nan, 3.5});
     CHECK(!is_sorted(table_view{{g->view()}}, {O::ASCENDING}, {}));
+    // DESCENDING: tied NaNs in front of the numbers are in order (not only in the reverse row order of the single-column radix rule)
+    auto h = make_col<double>({nan, -nan, nan, 3.5, 0.0, -0.0, -1.0});
+    CHECK(is_sorted(table_view{{h->view()}}, {O::DESCENDING}, {}));
+    CHECK(!is_sorted(table_view{{g->view()}}, {O::DESCENDING}, {}));
+    auto hn = make_col<double>({nan, nan, nan, 1.0});
+    auto hb = make_col<int32_t>({1, 2, 2, 0});
+    CHECK(is_sorted(table_view{{hn->view(), hb->view()}}, {O::DESCENDING, O::ASCENDING}, {}));
+    CHECK(!is_sorted(table_view{{hn->view(), hb->view()}}, {O::DESCENDING, O::DESCENDING}, {}));
     // two columns, mixed directions; then a tie in the first column broken the wrong way by the second
     auto c1 = make_col<int32_t>({1, 1, 2, 2, 3});
     auto c2 = make_col<int64_t>({9, 7, 5, 5, 0});

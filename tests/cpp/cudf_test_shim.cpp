@@ -76,6 +76,38 @@ void emit(cudf::column_view const& c, void* out, uint32_t* out_valid, int* out_n
 
 void shim_sync() { cudf::get_default_stream().synchronize(); }
 
+// a table of `ncols` columns from per-column host arrays (valids_host / nulls_host may be NULL: no column has nulls)
+cudf::table_view table_of(int ncols, const int* dtypes_host, const void* const* datas_host, const uint32_t* const* valids_host,
+                          const int* nulls_host, int n)
+{
+  std::vector<cudf::column_view> cols;
+  for (int i = 0; i < ncols; ++i)
+    cols.push_back(view(dtypes_host[i], datas_host[i], valids_host ? valids_host[i] : nullptr, n, nulls_host ? nulls_host[i] : 0));
+  return cudf::table_view{cols};
+}
+
+std::vector<cudf::order> orders_of(int ncols, const int* descending_host)
+{
+  std::vector<cudf::order> ord;
+  for (int i = 0; i < ncols; ++i) ord.push_back(descending_host[i] ? cudf::order::DESCENDING : cudf::order::ASCENDING);
+  return ord;
+}
+
+std::vector<cudf::null_order> precedences_of(int ncols, const int* nulls_before_host)
+{
+  std::vector<cudf::null_order> prec;
+  for (int i = 0; i < ncols; ++i)
+    prec.push_back(nulls_before_host && !nulls_before_host[i] ? cudf::null_order::AFTER : cudf::null_order::BEFORE);
+  return prec;
+}
+
+// every column of a result table out: outs_host[i] (data), out_valids_host[i] (validity, or all-valid words), out_nulls_host[i]
+void emit_table(cudf::table_view const& t, void* const* outs_host, uint32_t* const* out_valids_host, int* out_nulls_host)
+{
+  for (int i = 0; i < t.num_columns(); ++i)
+    emit(t.column(i), outs_host[i], out_valids_host ? out_valids_host[i] : nullptr, out_nulls_host ? &out_nulls_host[i] : nullptr);
+}
+
 std::unique_ptr<cudf::groupby_aggregation> make_agg(int kind, int param)
 {
   using A = cudf::aggregation;
@@ -173,6 +205,52 @@ int shim_table_sorted_order(int ncols, const int* dtypes_host, const void* const
     }
     auto r = stable ? cudf::stable_sorted_order(cudf::table_view{cols}, ord, prec) : cudf::sorted_order(cudf::table_view{cols}, ord, prec);
     emit(r->view(), out, nullptr, nullptr);
+    shim_sync();
+  });
+}
+
+// cudf::is_sorted of a key table (reference cpp/src/sort/is_sorted.cu:27-86); *out_host = 1 when the rows are in order
+int shim_is_sorted(int ncols, const int* dtypes_host, const void* const* datas_host, const uint32_t* const* valids_host,
+                   const int* nulls_host, int n, const int* descending_host, const int* nulls_before_host, int* out_host)
+{
+  return guarded([&] {
+    *out_host = cudf::is_sorted(table_of(ncols, dtypes_host, datas_host, valids_host, nulls_host, n), orders_of(ncols, descending_host),
+                                precedences_of(ncols, nulls_before_host))
+                  ? 1
+                  : 0;
+    shim_sync();
+  });
+}
+
+// cudf::sort / stable_sort of a table (reference cpp/src/sort/sort.cu:52-89, stable_sort.cu); outs_host[i] has room for n rows
+int shim_sort(int ncols, const int* dtypes_host, const void* const* datas_host, const uint32_t* const* valids_host, const int* nulls_host,
+              int n, const int* descending_host, const int* nulls_before_host, int stable, void* const* outs_host,
+              uint32_t* const* out_valids_host, int* out_nulls_host)
+{
+  return guarded([&] {
+    auto const in   = table_of(ncols, dtypes_host, datas_host, valids_host, nulls_host, n);
+    auto const ord  = orders_of(ncols, descending_host);
+    auto const prec = precedences_of(ncols, nulls_before_host);
+    auto r          = stable ? cudf::stable_sort(in, ord, prec) : cudf::sort(in, ord, prec);
+    emit_table(r->view(), outs_host, out_valids_host, out_nulls_host);
+    shim_sync();
+  });
+}
+
+// cudf::sort_by_key / stable_sort_by_key (reference cpp/src/sort/sort.cu:31-50): the value table gathered through the keys' order
+int shim_sort_by_key(int nvals, const int* val_dtypes_host, const void* const* val_datas_host, const uint32_t* const* val_valids_host,
+                     const int* val_nulls_host, int nkeys, const int* key_dtypes_host, const void* const* key_datas_host,
+                     const uint32_t* const* key_valids_host, const int* key_nulls_host, int n, const int* descending_host,
+                     const int* nulls_before_host, int stable, void* const* outs_host, uint32_t* const* out_valids_host,
+                     int* out_nulls_host)
+{
+  return guarded([&] {
+    auto const vals = table_of(nvals, val_dtypes_host, val_datas_host, val_valids_host, val_nulls_host, n);
+    auto const keys = table_of(nkeys, key_dtypes_host, key_datas_host, key_valids_host, key_nulls_host, n);
+    auto const ord  = orders_of(nkeys, descending_host);
+    auto const prec = precedences_of(nkeys, nulls_before_host);
+    auto r          = stable ? cudf::stable_sort_by_key(vals, keys, ord, prec) : cudf::sort_by_key(vals, keys, ord, prec);
+    emit_table(r->view(), outs_host, out_valids_host, out_nulls_host);
     shim_sync();
   });
 }
