@@ -31,6 +31,7 @@ _sz = ctypes.POINTER(ctypes.c_size_t)
 INT8, INT16, INT32, INT64, UINT8, UINT16, UINT32, UINT64, FLOAT32, FLOAT64, BOOL8 = range(1, 12)
 OP_SUM, OP_PRODUCT, OP_MIN, OP_MAX, OP_COUNT_VALID, OP_COUNT_ALL = 0, 1, 2, 3, 4, 5
 OP_MEAN = 10
+CMP_EQ, CMP_NE, CMP_LT, CMP_LE, CMP_GT, CMP_GE = range(6)
 
 _PROTOS = {
     "gx_version": (ctypes.c_char_p, []),
@@ -152,6 +153,16 @@ _PROTOS = {
     "gx_sequence_i32": (_i, [_p, _i64, ctypes.c_int32, _p]),
     "gx_copy_bytes": (_i, [_p, _p, ctypes.c_size_t, _p]),
     "gx_checksum": (_i, [_i, _p, _i64, _i, _p, _p]),
+    # row filtering (gx_compact.hip): selectors write the plan, the per-column calls read it
+    "gx_compact_plan_bytes": (ctypes.c_size_t, [_i64]),
+    "gx_select_mask": (_i, [_p, _p, _i64, _i64, _p, _p, _sz, _p]),
+    "gx_select_valid_count": (_i, [_i, ctypes.POINTER(_p), ctypes.POINTER(_i64), _i64, _i, _p, _p, _sz, _p]),
+    "gx_select_not_nan": (_i, [_i, ctypes.POINTER(_i), ctypes.POINTER(_p), ctypes.POINTER(_p), ctypes.POINTER(_i64), _i64, _i, _i, _p, _p, _sz, _p]),
+    "gx_compact_column": (_i, [_i, _p, _p, _i64, _i64, _p, _p, _p, _p, _p]),
+    "gx_compact_indices": (_i, [_i64, _p, _p, _p]),
+    "gx_compare_scalar": (_i, [_i, _p, _p, _i64, _i, ctypes.c_uint64, _p, _p]),
+    "gx_select_set_stages": (None, [_i]),
+    "gx_compact_set_kernel": (None, [_i]),
 }
 
 for _name, (_res, _args) in _PROTOS.items():

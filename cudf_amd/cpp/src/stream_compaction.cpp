@@ -1,0 +1,158 @@
+// cudf::apply_boolean_mask / drop_nulls / drop_nans over the C ABI (gx_select_* -> gx_compact_column, cudf_amd/csrc/gx_compact.hip).
+// reference: cpp/src/stream_compaction/apply_boolean_mask.cu (apply_boolean_mask), drop_nulls.cu (drop_nulls), drop_nans.cu
+// (drop_nans), all three a predicate handed to cudf::detail::copy_if (include/cudf/detail/copy_if.cuh); contract pinned by
+// cpp/tests/stream_compaction/apply_boolean_mask_tests.cpp, drop_nulls_tests.cpp, drop_nans_tests.cpp.
+// A selector writes the plan (selection bits + chunk starts) and the number of kept rows; that count is the one value read back
+// before the outputs are allocated, the null counts of all output columns come back in one more read behind the scatters.
+#include "common.hpp"
+
+#include <cudf/column/column_factories.hpp>
+#include <cudf/null_mask.hpp>
+#include <cudf/stream_compaction.hpp>
+
+#include <stdexcept>
+
+namespace cudf {
+namespace {
+
+constexpr size_type MAX_KEYS = 32;  // key columns of one selector call (gx.h)
+
+std::unique_ptr<table> empty_like_table(table_view const& t)
+{
+  std::vector<std::unique_ptr<column>> cols;
+  cols.reserve(t.num_columns());
+  for (auto const& c : t) cols.emplace_back(make_empty_column(c.type()));
+  return std::make_unique<table>(std::move(cols));
+}
+
+// every column of `input` compacted from one plan
+std::unique_ptr<table> compact_table(table_view const& input, void const* plan, size_type count, rmm::cuda_stream_view stream,
+                                     rmm::device_async_resource_ref mr)
+{
+  if (count == 0) return empty_like_table(input);
+  auto const n  = input.num_rows();
+  auto const nc = input.num_columns();
+  rmm::device_uvector<int64_t> nulls_dev(static_cast<std::size_t>(nc), stream);
+  std::vector<rmm::device_buffer> data, masks;
+  data.reserve(nc);
+  masks.reserve(nc);
+  bool any_mask = false;
+  for (size_type k = 0; k < nc; ++k) {
+    auto const& c  = input.column(k);
+    auto const esz = gx_dtype_size(detail::gx_type(c.type()));
+    data.emplace_back(static_cast<std::size_t>(count) * esz, stream, mr);
+    bool const with_mask = c.has_nulls();
+    masks.emplace_back(create_null_mask(count, with_mask ? mask_state::ALL_NULL : mask_state::UNALLOCATED, stream, mr));
+    any_mask |= with_mask;
+    detail::gx_check(gx_compact_column(esz, detail::row0(c), with_mask ? c.null_mask() : nullptr, c.offset(), n, plan, data.back().data(),
+                                       with_mask ? static_cast<uint32_t*>(masks.back().data()) : nullptr, nulls_dev.data() + k,
+                                       detail::gxs(stream)),
+                     "gx_compact_column");
+  }
+  std::vector<int64_t> nulls(static_cast<std::size_t>(nc), 0);
+  if (any_mask) {
+    CUDF_CUDA_TRY(hipMemcpyAsync(nulls.data(), nulls_dev.data(), nulls.size() * sizeof(int64_t), hipMemcpyDeviceToHost, stream.value()));
+    stream.synchronize();
+  }
+  std::vector<std::unique_ptr<column>> cols;
+  cols.reserve(nc);
+  for (size_type k = 0; k < nc; ++k) {
+    auto const nk = static_cast<size_type>(nulls[k]);
+    cols.emplace_back(std::make_unique<column>(input.column(k).type(), count, std::move(data[k]),
+                                               nk > 0 ? std::move(masks[k]) : rmm::device_buffer{0, stream, mr}, nk));
+  }
+  return std::make_unique<table>(std::move(cols));
+}
+
+// runs a selector (scratch-query convention, the count as a device word in front of it) and compacts the table from its plan
+template <typename Selector>
+std::unique_ptr<table> select_and_compact(table_view const& input, Selector&& sel, char const* what, rmm::cuda_stream_view stream,
+                                          rmm::device_async_resource_ref mr)
+{
+  rmm::device_uvector<int64_t> count_dev(1, stream);
+  auto plan        = detail::run_with_scratch([&](void* t, std::size_t* b) { return sel(count_dev.data(), t, b); }, what, stream);
+  auto const count = static_cast<size_type>(detail::read_i64(count_dev.data(), stream));
+  return compact_table(input, plan.data(), count, stream, mr);
+}
+
+}  // namespace
+
+std::unique_ptr<table> apply_boolean_mask(table_view const& input, column_view const& boolean_mask, rmm::cuda_stream_view stream,
+                                          rmm::device_async_resource_ref mr)
+{
+  if (boolean_mask.is_empty()) return empty_like_table(input);  // (apply_boolean_mask: an empty mask gives empty_like(input))
+  CUDF_EXPECTS(input.num_rows() == boolean_mask.size(), "Column size mismatch");
+  CUDF_EXPECTS(boolean_mask.type().id() == type_id::BOOL8, "Mask must be Boolean type");
+  if (input.num_columns() == 0) return std::make_unique<table>(input, stream, mr);
+  auto const n = input.num_rows();
+  return select_and_compact(
+    input,
+    [&](int64_t* cnt, void* t, std::size_t* b) {
+      return gx_select_mask(static_cast<uint8_t const*>(detail::row0(boolean_mask)), boolean_mask.has_nulls() ? boolean_mask.null_mask() : nullptr,
+                            boolean_mask.offset(), n, cnt, t, b, detail::gxs(stream));
+    },
+    "apply_boolean_mask", stream, mr);
+}
+
+std::unique_ptr<table> drop_nulls(table_view const& input, std::vector<size_type> const& keys, size_type keep_threshold,
+                                  rmm::cuda_stream_view stream, rmm::device_async_resource_ref mr)
+{
+  auto const key_view = input.select(keys);  // std::out_of_range for an invalid index
+  CUDF_EXPECTS(keep_threshold >= 0, "keep_threshold must not be negative", std::invalid_argument);
+  if (keys.empty() || input.num_rows() == 0 || !cudf::has_nulls(key_view)) return std::make_unique<table>(input, stream, mr);
+  CUDF_EXPECTS(key_view.num_columns() <= MAX_KEYS, "drop_nulls: at most 32 key columns", std::invalid_argument);
+  std::vector<uint32_t const*> valid;
+  std::vector<int64_t> begin;
+  for (auto const& c : key_view) {
+    valid.push_back(c.has_nulls() ? c.null_mask() : nullptr);
+    begin.push_back(c.offset());
+  }
+  return select_and_compact(
+    input,
+    [&](int64_t* cnt, void* t, std::size_t* b) {
+      return gx_select_valid_count(static_cast<int>(valid.size()), valid.data(), begin.data(), input.num_rows(), keep_threshold, cnt, t, b,
+                                   detail::gxs(stream));
+    },
+    "drop_nulls", stream, mr);
+}
+
+std::unique_ptr<table> drop_nulls(table_view const& input, std::vector<size_type> const& keys, rmm::cuda_stream_view stream,
+                                  rmm::device_async_resource_ref mr)
+{
+  return drop_nulls(input, keys, static_cast<size_type>(keys.size()), stream, mr);
+}
+
+std::unique_ptr<table> drop_nans(table_view const& input, std::vector<size_type> const& keys, size_type keep_threshold,
+                                 rmm::cuda_stream_view stream, rmm::device_async_resource_ref mr)
+{
+  auto const key_view = input.select(keys);  // std::out_of_range for an invalid index
+  CUDF_EXPECTS(keep_threshold >= 0, "keep_threshold must not be negative", std::invalid_argument);
+  if (input.num_columns() == 0 || input.num_rows() == 0 || keys.empty()) return std::make_unique<table>(input, stream, mr);
+  for (auto const& c : key_view) CUDF_EXPECTS(is_floating_point(c.type()), "Key column is not of floating-point type");
+  CUDF_EXPECTS(key_view.num_columns() <= MAX_KEYS, "drop_nans: at most 32 key columns", std::invalid_argument);
+  std::vector<int> dtypes;
+  std::vector<void const*> data;
+  std::vector<uint32_t const*> valid;
+  std::vector<int64_t> begin;
+  for (auto const& c : key_view) {
+    dtypes.push_back(detail::gx_type(c.type()));
+    data.push_back(detail::row0(c));
+    valid.push_back(c.has_nulls() ? c.null_mask() : nullptr);
+    begin.push_back(c.offset());
+  }
+  return select_and_compact(
+    input,
+    [&](int64_t* cnt, void* t, std::size_t* b) {
+      return gx_select_not_nan(static_cast<int>(dtypes.size()), dtypes.data(), data.data(), valid.data(), begin.data(), input.num_rows(),
+                               keep_threshold, /*null_is_missing=*/0, cnt, t, b, detail::gxs(stream));
+    },
+    "drop_nans", stream, mr);
+}
+
+std::unique_ptr<table> drop_nans(table_view const& input, std::vector<size_type> const& keys, rmm::cuda_stream_view stream,
+                                 rmm::device_async_resource_ref mr)
+{
+  return drop_nans(input, keys, static_cast<size_type>(keys.size()), stream, mr);
+}
+
+}  // namespace cudf

@@ -1,5 +1,5 @@
 """Thin pandas-like wrapper over the hot path (the cudf.DataFrame surface of the reference, reduced
-to the methods that land on it): sort_values, merge, groupby(...).agg.
+to the methods that land on it): sort_values, merge, groupby(...).agg, df[mask], dropna.
 
 reference: python/cudf/cudf/core/dataframe.py (sort_values -> core/_internals/sorting.py ->
 pylibcudf.sorting.sorted_order + gather; merge -> core/join/join.py -> pylibcudf.join.inner_join /
@@ -59,8 +59,46 @@ class DataFrame:
             raise ValueError("Length of values does not match length of index")
         self._cols[name] = col
 
-    def __getitem__(self, name: str) -> Column:
-        return self._cols[name]
+    def __getitem__(self, key):
+        """df["name"] -> the column; df[mask] -> the rows where a bool Column / NumPy bool array of len(df) is true, in row order
+        (a null mask element drops its row)"""
+        if isinstance(key, str):
+            return self._cols[key]
+        if isinstance(key, np.ndarray):
+            if key.dtype != np.bool_:
+                raise TypeError("a row mask must be a bool array")
+            key = Column.from_numpy(key)
+        if not isinstance(key, Column):
+            raise TypeError(f"unsupported key type {type(key).__name__}")
+        if key.dtype != np.bool_:
+            raise TypeError("a row mask must be a bool Column")
+        if key.size != len(self):
+            raise ValueError(f"Item wrong length {key.size} instead of {len(self)}.")
+        return self._from_columns(ops.apply_boolean_mask(list(self._cols.values()), key))
+
+    def _from_columns(self, cols: Sequence[Column]) -> "DataFrame":
+        out = DataFrame()
+        for name, c in zip(self._cols, cols):
+            out._cols[name] = c
+        return out
+
+    def dropna(self, subset: Optional[Union[str, Sequence[str]]] = None, how: Optional[str] = None,
+               thresh: Optional[int] = None) -> "DataFrame":
+        """pandas' DataFrame.dropna(axis=0): a null or a NaN counts as missing.  how="any" (default) drops a row with any missing
+        value among `subset` (default: every column), how="all" one whose values are all missing; thresh keeps the rows with at
+        least that many values present.  Row order is kept."""
+        if how is not None and thresh is not None:
+            raise TypeError("You cannot set both the how and thresh arguments at the same time.")
+        if how not in (None, "any", "all"):
+            raise ValueError(f"invalid how option: {how}")
+        names = list(self._cols) if subset is None else ([subset] if isinstance(subset, str) else list(subset))
+        for k in names:
+            if k not in self._cols:
+                raise KeyError(k)
+        order = list(self._cols)
+        keys = [order.index(k) for k in names]
+        need = int(thresh) if thresh is not None else (1 if how == "all" else len(keys))
+        return self._from_columns(ops.dropna_rows(list(self._cols.values()), keys, need))
 
     def __len__(self) -> int:
         return next(iter(self._cols.values())).size if self._cols else 0

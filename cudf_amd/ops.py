@@ -978,6 +978,174 @@ def scan(col: Column, op: str = "sum", inclusive: bool = True, null_include: boo
 
 
 # ------------------------------------------------------------------------------------------------
+# stream compaction  (cudf::apply_boolean_mask / drop_nulls / drop_nans: stream_compaction.hpp; pylibcudf/stream_compaction.pyx)
+# A selector writes the plan (one bit per row + chunk starts, gx_compact.hip) and the number of selected rows; every column of
+# the table is then compacted from that one plan.  Host reads per call: the count, and once the null counts of all outputs.
+# ------------------------------------------------------------------------------------------------
+
+_CMP = {"eq": L.CMP_EQ, "==": L.CMP_EQ, "ne": L.CMP_NE, "!=": L.CMP_NE, "lt": L.CMP_LT, "<": L.CMP_LT,
+        "le": L.CMP_LE, "<=": L.CMP_LE, "gt": L.CMP_GT, ">": L.CMP_GT, "ge": L.CMP_GE, ">=": L.CMP_GE}
+
+
+def _copy_column(col: Column) -> Column:
+    out = Column(col.data.clone(), col.dtype, col.size)
+    if col.mask is not None:
+        out.mask, out.null_count = col.mask.clone(), col.null_count
+    return out
+
+
+def _ptr_array(ptrs):
+    return (ctypes.c_void_p * max(len(ptrs), 1))(*[p.value if isinstance(p, ctypes.c_void_p) else p for p in ptrs])
+
+
+def _select_mask(mask: Column):
+    """(plan, selected rows) of a BOOL8 mask column: a row is kept where the mask is valid and non-zero"""
+    if mask.dtype != np.bool_:
+        raise TypeError("Mask must be Boolean type")            # apply_boolean_mask.cu: "Mask must be Boolean type"
+    cnt = _dev_i64()
+    plan = _run(_lib.gx_select_mask, mask.data_ptr, mask.mask_ptr, 0, mask.size, ptr(cnt))
+    return plan, int(cnt.item())
+
+
+def _compact(cols: Sequence[Column], plan: torch.Tensor, n: int, count: int) -> List[Column]:
+    """every column compacted from one plan; a column whose output holds no null comes back without a mask"""
+    if count == 0:
+        return [Column.empty(c.dtype, 0) for c in cols]
+    outs = []
+    nulls = torch.zeros(max(len(cols), 1), dtype=torch.int64, device="cuda")
+    for k, c in enumerate(cols):
+        out = Column.empty(c.dtype, count, nullable=c.mask is not None)
+        L.check(_lib.gx_compact_column(c.dtype.itemsize, c.data_ptr, c.mask_ptr, 0, n, ptr(plan), out.data_ptr, out.mask_ptr,
+                                       ctypes.c_void_p(nulls.data_ptr() + 8 * k), stream_ptr()), "gx_compact_column")
+        outs.append(out)
+    if any(c.mask is not None for c in cols):
+        host = nulls.cpu().numpy()
+        for k, out in enumerate(outs):
+            if out.mask is not None:
+                out.null_count = int(host[k])
+                if out.null_count == 0:
+                    out.mask = None
+    return outs
+
+
+def apply_boolean_mask(cols: Sequence[Column], mask: Column) -> List[Column]:
+    """cudf::apply_boolean_mask: the rows of the table `cols` where `mask` is true, in row order; a null mask element drops its row."""
+    cols = list(cols)
+    if mask.dtype != np.bool_:
+        raise TypeError("Mask must be Boolean type")
+    for c in cols:
+        if c.size != mask.size:
+            raise ValueError("Column size mismatch")            # apply_boolean_mask.cu: "Column size mismatch"
+    if mask.size == 0 or not cols:
+        return [_copy_column(c) for c in cols]
+    plan, count = _select_mask(mask)
+    return _compact(cols, plan, mask.size, count)
+
+
+def selected_rows(mask: Column) -> Column:
+    """the ascending row numbers at which `mask` is true (INT32): the gather map of the selection, np.flatnonzero on the device"""
+    if mask.size == 0:
+        if mask.dtype != np.bool_:
+            raise TypeError("Mask must be Boolean type")
+        return Column.empty(np.int32, 0)
+    plan, count = _select_mask(mask)
+    out = Column.empty(np.int32, count)
+    L.check(_lib.gx_compact_indices(mask.size, ptr(plan), out.data_ptr, stream_ptr()), "gx_compact_indices")
+    return out
+
+
+def _keys_of(cols: Sequence[Column], keys: Sequence[int]) -> List[Column]:
+    for k in keys:
+        if not 0 <= int(k) < len(cols):
+            raise IndexError("key column index out of range")   # table_view::select -> std::out_of_range
+    if len(keys) > 32:
+        raise ValueError("at most 32 key columns")
+    return [cols[int(k)] for k in keys]
+
+
+def drop_nulls(cols: Sequence[Column], keys: Sequence[int], keep_threshold: Optional[int] = None) -> List[Column]:
+    """cudf::drop_nulls: the rows with at least keep_threshold (default: all) valid elements among the key columns cols[k], k in
+    keys.  Keys without any null return a copy of the input whatever the threshold (drop_nulls.cu)."""
+    cols = list(cols)
+    kc = _keys_of(cols, keys)
+    thr = len(kc) if keep_threshold is None else int(keep_threshold)
+    if thr < 0:
+        raise ValueError("keep_threshold must not be negative")
+    n = cols[0].size if cols else 0
+    if n == 0 or not kc or not any(c.has_nulls() for c in kc):
+        return [_copy_column(c) for c in cols]
+    valids = _ptr_array([c.mask_ptr if c.has_nulls() else None for c in kc])
+    cnt = _dev_i64()
+    plan = _run(_lib.gx_select_valid_count, len(kc), valids, None, n, thr, ptr(cnt))
+    return _compact(cols, plan, n, int(cnt.item()))
+
+
+def _select_not_nan(kc: Sequence[Column], n: int, thr: int, null_is_missing: bool):
+    dts = (ctypes.c_int * len(kc))(*[c.gx for c in kc])
+    datas = _ptr_array([c.data_ptr for c in kc])
+    valids = _ptr_array([c.mask_ptr if c.has_nulls() else None for c in kc])
+    cnt = _dev_i64()
+    plan = _run(_lib.gx_select_not_nan, len(kc), dts, datas, valids, None, n, thr, int(null_is_missing), ptr(cnt))
+    return plan, int(cnt.item())
+
+
+def drop_nans(cols: Sequence[Column], keys: Sequence[int], keep_threshold: Optional[int] = None) -> List[Column]:
+    """cudf::drop_nans: the rows with at least keep_threshold (default: all) non-NaN elements among the FLOAT32 / FLOAT64 key
+    columns; a null element is not a NaN."""
+    cols = list(cols)
+    kc = _keys_of(cols, keys)
+    for c in kc:
+        if c.dtype.kind != "f" or c.dtype.itemsize not in (4, 8):
+            raise TypeError("Key column is not of floating-point type")    # drop_nans.cu
+    thr = len(kc) if keep_threshold is None else int(keep_threshold)
+    if thr < 0:
+        raise ValueError("keep_threshold must not be negative")
+    n = cols[0].size if cols else 0
+    if n == 0 or not kc:
+        return [_copy_column(c) for c in cols]
+    plan, count = _select_not_nan(kc, n, thr, False)
+    return _compact(cols, plan, n, count)
+
+
+def dropna_rows(cols: Sequence[Column], keys: Sequence[int], keep_threshold: int) -> List[Column]:
+    """pandas' dropna on a table: the rows with at least keep_threshold elements among the key columns that are neither null nor NaN"""
+    cols = list(cols)
+    kc = _keys_of(cols, keys)
+    n = cols[0].size if cols else 0
+    if n == 0 or not kc or not any(c.has_nulls() or c.dtype.kind == "f" for c in kc):
+        if kc and n and keep_threshold > len(kc):
+            plan, count = _select_not_nan(kc, n, keep_threshold, True)   # nothing can reach the threshold: every row goes
+            return _compact(cols, plan, n, count)
+        return [_copy_column(c) for c in cols]
+    plan, count = _select_not_nan(kc, n, keep_threshold, True)
+    return _compact(cols, plan, n, count)
+
+
+def compare_scalar(col: Column, op: str, value) -> Column:
+    """BOOL8 column of col[i] <op> value, op in eq / ne / lt / le / gt / ge (or ==, !=, <, <=, >, >=); it shares the input's validity
+    (a null row stays null).  NaN compares false except under ne.  The scalar must be representable in the column's dtype."""
+    if op not in _CMP:
+        raise ValueError(f"unknown comparison {op!r}")
+    dt = col.dtype
+    if dt.kind in "iu":
+        info = np.iinfo(dt)
+        if int(value) != value or not info.min <= int(value) <= info.max:
+            raise OverflowError(f"{value!r} is not representable as {dt}")
+        raw = np.array([int(value)], dtype=dt)
+    else:
+        raw = np.array([value]).astype(dt)
+    sc = np.zeros(8, dtype=np.uint8)
+    sc[: dt.itemsize] = raw.view(np.uint8)
+    bits = int(sc.view(np.uint64)[0])
+    out = Column.empty(np.bool_, col.size)
+    L.check(_lib.gx_compare_scalar(col.gx, col.data_ptr, col.mask_ptr, col.size, _CMP[op], ctypes.c_uint64(bits), out.data_ptr,
+                                   stream_ptr()), "gx_compare_scalar")
+    if col.mask is not None:
+        out.mask, out.null_count = col.mask, col.null_count
+    return out
+
+
+# ------------------------------------------------------------------------------------------------
 # synthetic data / checks (bench + tests)
 # ------------------------------------------------------------------------------------------------
 

@@ -209,6 +209,47 @@ int gx_bitmask_and(const uint32_t* const* masks_host, int nmasks, int64_t nbits,
                    int64_t* count_dev, gx_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Ordered stream compaction (row filtering).  Replaces thrust::copy_if / cudf::detail::copy_if behind
+ * cudf::apply_boolean_mask, drop_nulls and drop_nans (src/stream_compaction/apply_boolean_mask.cu, drop_nulls.cu,
+ * drop_nans.cu; include/cudf/detail/copy_if.cuh).  Two steps:
+ *   a SELECTOR writes the plan into `sel_tmp` -- one bit per row as uint64 ballot words, the number of selected rows before
+ *   every 4096-row chunk -- and the number of selected rows to *count_dev (device int64, optional).  cub-style query:
+ *   sel_tmp == NULL -> *tmp_bytes = gx_compact_plan_bytes(n) = align256(8 * (ceil(n / 64) + 1)) + align256(8 * (ceil(n / 4096) + 1));
+ *   gx_compact_column / gx_compact_indices read the plan, once per column: the selected elements in row order.  One plan
+ *   serves every column of a table of n rows (`n` must be the n the plan was made for).
+ * Bitmaps are Arrow validity bitmaps read from a begin bit on (sliced views), as in gx_bitmask_copy.  n < 2^31.
+ *
+ * gx_select_mask: selected = mask[i] != 0 and (mask_valid == NULL or its bit is set): a null mask element drops the row.
+ * gx_select_valid_count: selected = (number of the nkeys <= 32 bitmaps whose bit is set) >= keep_threshold; a NULL entry of
+ *   valid_ptrs_host is a column without nulls.  valid_ptrs_host / begin_bits_host (NULL = zeros) are HOST arrays.
+ * gx_select_not_nan: null_is_missing == 0 (cudf::drop_nans): selected = (number of keys that are not a VALID NaN) >=
+ *   keep_threshold -- a null element is not a NaN; every dtype must be FLOAT32 / FLOAT64, else GX_EDTYPE.
+ *   null_is_missing != 0 (pandas dropna): a key counts when it is valid AND not NaN; keys of other dtypes are allowed, their
+ *   validity alone decides (cols_host[k] is not read for them).
+ * gx_compact_column: elem_size in {1,2,4,8} (else GX_EDTYPE).  in_valid != NULL: out_valid (REQUIRED then, zeroed by the
+ *   caller, (selected + 31) / 32 words) receives bit j = validity of the j-th selected row, *out_null_count_dev (device
+ *   int64, optional) the number of selected null rows.
+ * gx_compact_indices: out_idx[j] = row number of the j-th selected row (the gather map of the selection).
+ * gx_compare_scalar: out_bool8[i] = in[i] <cmp> scalar (gx_cmp; the scalar's bits in the column's type sit in the low bytes of
+ *   scalar_bits); NaN compares false except under GX_CMP_NE; a null row (in_valid bit 0) gets 0 -- the result column shares
+ *   the input's bitmap.  One grid-stride kernel; what makes a mask on the device.
+ * ------------------------------------------------------------------------------------------ */
+enum gx_cmp { GX_CMP_EQ = 0, GX_CMP_NE = 1, GX_CMP_LT = 2, GX_CMP_LE = 3, GX_CMP_GT = 4, GX_CMP_GE = 5 };
+size_t gx_compact_plan_bytes(int64_t n); /* 0 for n outside [0, 2^31) */
+int gx_select_mask(const uint8_t* mask_bool8, const uint32_t* mask_valid, int64_t mask_valid_begin_bit, int64_t n,
+                   int64_t* count_dev, void* sel_tmp, size_t* tmp_bytes, gx_stream_t stream);
+int gx_select_valid_count(int nkeys, const uint32_t* const* valid_ptrs_host, const int64_t* begin_bits_host, int64_t n,
+                          int keep_threshold, int64_t* count_dev, void* sel_tmp, size_t* tmp_bytes, gx_stream_t stream);
+int gx_select_not_nan(int nkeys, const int* dtypes_host, const void* const* cols_host, const uint32_t* const* valid_ptrs_host,
+                      const int64_t* begin_bits_host, int64_t n, int keep_threshold, int null_is_missing, int64_t* count_dev,
+                      void* sel_tmp, size_t* tmp_bytes, gx_stream_t stream);
+int gx_compact_column(int elem_size, const void* in, const uint32_t* in_valid, int64_t in_valid_begin_bit, int64_t n,
+                      const void* sel_tmp, void* out, uint32_t* out_valid, int64_t* out_null_count_dev, gx_stream_t stream);
+int gx_compact_indices(int64_t n, const void* sel_tmp, int32_t* out_idx, gx_stream_t stream);
+int gx_compare_scalar(int dtype, const void* in, const uint32_t* in_valid, int64_t n, int cmp, uint64_t scalar_bits,
+                      uint8_t* out_bool8, gx_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * Hashing / partitioning.
  * gx_murmur3_32: cudf::hashing::detail::MurmurHash3_x86_32<T>
  * (include/cudf/hashing/detail/murmurhash3_x86_32.cuh:22-67), null -> UINT32_MAX, and the

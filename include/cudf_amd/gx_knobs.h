@@ -209,6 +209,14 @@ void gx_groupby_set_partition_mode(int speculative);
  * partitions give the scatter 32-row instead of 16-row runs (9.5 vs 10.1 ms per 1e9 rows; sparse keys 12.7 vs 19.5 ms the other way). */
 int gx_groupby_set_partition_bits(int bits);
 
+/* Measurement hook (process-wide) of the row-filter selectors (gx_select_*): bit 0 = the select kernel runs, bit 1 = the scan of
+ * the chunk counts (and the store of the total) runs.  3 (default) = both.  scripts/xp/xp_compaction.py times the stages apart. */
+void gx_select_set_stages(int mask);
+/* A/B knob (process-wide) of gx_compact_column for columns without a bitmap: 1 = the direct scatter (every selected lane stores its
+ * element), 2 = the LDS-staged scatter (a chunk's selected elements are collected in LDS and leave as 16-byte lanes; needs a 16-byte
+ * aligned output, else the direct one runs), 0 = the default choice (DESIGN.md, row filtering: the measured table). */
+void gx_compact_set_kernel(int kernel);
+
 #ifdef __cplusplus
 }
 #endif
