@@ -8,13 +8,15 @@
 #include <stdint.h>
 
 #include "../../include/cudf_amd/gx.h"
+#include "gx_lds_book.hpp"
 
 #define GX_WAVE 64
 
+// expr: a hipError_t, or the int of a helper that returns one (gx::device, gx::launch_lds)
 #define GX_HIP_TRY(expr)                           \
   do {                                             \
-    hipError_t _e = (expr);                        \
-    if (_e != hipSuccess) return (int)_e;          \
+    const int _e = (int)(expr);                    \
+    if (_e != (int)hipSuccess) return _e;          \
   } while (0)
 
 #define GX_LAUNCH_CHECK()                          \
@@ -43,6 +45,56 @@ struct Carver {
   }
   size_t total() const { return align_up(off, 256); }
 };
+
+// ---------------------------------------------------------------- launch layer (host)
+// The current device: id and CU count, cached per device id (the 256-CU fallback lives here and nowhere else).  An entry point
+// takes it once and hands it to the launches below, so a launch makes no HIP call of its own beyond the launch.
+struct Device {
+  int id;
+  int cus;
+};
+#define GX_LOCAL __attribute__((visibility("hidden")))  // one copy per library, not part of its exported surface
+GX_LOCAL inline int device(Device* d)
+{
+  static std::atomic<int> cus_of[LDS_BOOK_DEVICES];  // 0 = not asked yet
+  GX_HIP_TRY(hipGetDevice(&d->id));
+  const bool cached = d->id >= 0 && d->id < LDS_BOOK_DEVICES;
+  d->cus            = cached ? cus_of[d->id].load(std::memory_order_relaxed) : 0;
+  if (d->cus == 0) {
+    GX_HIP_TRY(hipDeviceGetAttribute(&d->cus, hipDeviceAttributeMultiprocessorCount, d->id));
+    if (d->cus <= 0) d->cus = 256;
+    if (cached) cus_of[d->id].store(d->cus, std::memory_order_relaxed);
+  }
+  return 0;
+}
+
+inline int set_max_dynamic_lds(const void* kernel, int bytes)
+{
+  return (int)hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+}
+GX_LOCAL inline LdsBook& lds_book()
+{
+  static LdsBook book;
+  return book;
+}
+// Launch of a kernel that needs dynamic LDS: raises the kernel's limit on this device to lds_bytes when no earlier launch asked for
+// as much (gx_lds_book.hpp), then launches with exactly lds_bytes -- the byte count is written once.  Launches with 0 bytes stay
+// plain hipLaunchKernelGGL.  Like those, a failed launch is picked up by the caller's GX_LAUNCH_CHECK.
+template <typename Kernel, typename... Args>
+inline int launch_lds(const Device& dev, Kernel kernel, dim3 grid, dim3 block, size_t lds_bytes, hipStream_t s, Args&&... args)
+{
+  GX_HIP_TRY(lds_book().ensure(reinterpret_cast<const void*>(kernel), dev.id, (int)lds_bytes, set_max_dynamic_lds));
+  hipLaunchKernelGGL(kernel, grid, block, lds_bytes, s, static_cast<Args&&>(args)...);
+  return 0;
+}
+// resident workgroups per CU of `kernel` with this block size and dynamic LDS (>= 1), limit raised first
+inline int max_resident_wgs(const Device& dev, const void* kernel, int block, size_t lds_bytes, int* wgs)
+{
+  GX_HIP_TRY(lds_book().ensure(kernel, dev.id, (int)lds_bytes, set_max_dynamic_lds));
+  GX_HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(wgs, kernel, block, lds_bytes));
+  if (*wgs < 1) *wgs = 1;
+  return 0;
+}
 
 // ---------------------------------------------------------------- device primitives
 __device__ __forceinline__ unsigned lane_id()

@@ -1034,12 +1034,8 @@ int launch_partitioned(const K* keys, const uint32_t* kvalid, const V* vals, con
   constexpr int S        = lds_slots<K, HAS_VV>();
   constexpr size_t lds_a = (size_t)(S + 1) * 16 + (size_t)(S + 2) * sizeof(K) + (size_t)(S + 1) * 4 * (HAS_VV ? 2 : 1);
   auto ka                = k_part_aggregate<K, V, IS_FLOAT, HAS_VV>;
-  static std::atomic<bool> attr_set{false};
-  if (!attr_set) {
-    GX_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(ks), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_s));
-    GX_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(ka), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_a));
-    attr_set = true;
-  }
+  Device dev;
+  GX_HIP_TRY(device(&dev));
   const int nsplit    = g_gb_nsplit;
   const int nsub      = lds_nsub(max_groups, S);
   // the plan of a call may choose 8 bits (dense ids): workgroups per partition for that case; the grid covers both
@@ -1077,31 +1073,25 @@ int launch_partitioned(const K* keys, const uint32_t* kvalid, const V* vals, con
         constexpr size_t lds_d = (size_t)DD_GMAX * 20;
         auto ksd               = k_part_scatter<K, V, false, true>;
         auto kad               = k_dense_aggregate<K, V, IS_FLOAT>;
-        static std::atomic<bool> dattr{false};
-        if (!dattr) {
-          GX_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(ksd), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_s));
-          GX_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kad), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_d));
-          dattr = true;
-        }
         hipLaunchKernelGGL((k_dense_sample<K>), dim3((unsigned)sblocks), dim3(256), 0, s, keys, kvalid, n, plan, stride, range_rows);
         hipLaunchKernelGGL((k_slot_plan<PartPlan>), dim3(1), dim3(NPART), 0, s, plan, n, stride, range_rows, (unsigned long long)slot_elems(n, stride),
                            (long long)max_groups, 1);
-        hipLaunchKernelGGL(ksd, dim3(sgrd), dim3(PBT), lds_s, s, keys, kvalid, vals, vvalid, n, plan, pkeys, pvals, pflags, NRANGE, cap, 0);
-        hipLaunchKernelGGL(kad, dim3(DD_PARTS), dim3(ABT), lds_d, s, reinterpret_cast<const unsigned short*>(pkeys), (const V*)pvals, (const PartPlan*)plan, table, lg,
-                           sum, comp, cv, ca, st);
+        GX_HIP_TRY(launch_lds(dev, ksd, dim3(sgrd), dim3(PBT), lds_s, s, keys, kvalid, vals, vvalid, n, plan, pkeys, pvals, pflags, NRANGE, cap, 0));
+        GX_HIP_TRY(launch_lds(dev, kad, dim3(DD_PARTS), dim3(ABT), lds_d, s, reinterpret_cast<const unsigned short*>(pkeys), (const V*)pvals, (const PartPlan*)plan, table, lg,
+                                   sum, comp, cv, ca, st));
       }
     }
-    hipLaunchKernelGGL(ks, dim3(sgrd), dim3(PBT), lds_s, s, keys, kvalid, vals, vvalid, n, plan, pkeys, pvals, pflags, NRANGE, cap, 0);
-    hipLaunchKernelGGL(ka, dim3(agrd), dim3(ABT), lds_a, s, pkeys, pvals, pflags, plan, nsplit, nsub, table, lg, sum, comp, cv, ca, st, cap,
-                       0, nsub8);
+    GX_HIP_TRY(launch_lds(dev, ks, dim3(sgrd), dim3(PBT), lds_s, s, keys, kvalid, vals, vvalid, n, plan, pkeys, pvals, pflags, NRANGE, cap, 0));
+    GX_HIP_TRY(launch_lds(dev, ka, dim3(agrd), dim3(ABT), lds_a, s, pkeys, pvals, pflags, plan, nsplit, nsub, table, lg, sum, comp, cv, ca, st, cap,
+                               0, nsub8));
     hipLaunchKernelGGL(k_part_reset_cursors, dim3(1), dim3(NPART), 0, s, plan);
     gated = 1;  // the exact sequence below runs only if a slot overflowed
   }
   hipLaunchKernelGGL((k_part_hist<K>), dim3((unsigned)(hb * NRANGE)), dim3(256), 0, s, keys, kvalid, n, plan, g_gb_nrange, gated);
   hipLaunchKernelGGL(k_part_offsets, dim3(1), dim3(NPART), 0, s, plan, gated);
-  hipLaunchKernelGGL(ks, dim3(sgrd), dim3(PBT), lds_s, s, keys, kvalid, vals, vvalid, n, plan, pkeys, pvals, pflags, g_gb_nrange, 0u, gated);
-  hipLaunchKernelGGL(ka, dim3(agrd), dim3(ABT), lds_a, s, pkeys, pvals, pflags, plan, nsplit, nsub, table, lg, sum, comp, cv, ca, st, 0u,
-                     gated, nsub8);
+  GX_HIP_TRY(launch_lds(dev, ks, dim3(sgrd), dim3(PBT), lds_s, s, keys, kvalid, vals, vvalid, n, plan, pkeys, pvals, pflags, g_gb_nrange, 0u, gated));
+  GX_HIP_TRY(launch_lds(dev, ka, dim3(agrd), dim3(ABT), lds_a, s, pkeys, pvals, pflags, plan, nsplit, nsub, table, lg, sum, comp, cv, ca, st, 0u,
+                             gated, nsub8));
   GX_LAUNCH_CHECK();
   return 0;
 }
@@ -1599,12 +1589,8 @@ int launch_partitioned_minmax(const K* keys, const uint32_t* kvalid, const V* va
   constexpr int S        = lds_slots_mm<K, HAS_VV>();
   constexpr size_t lds_a = (size_t)(S + 1) * 16 + (size_t)(S + 2) * sizeof(K) + (size_t)(S + 1) * 4;
   auto ka                = k_part_minmax<K, V, HAS_VV>;
-  static std::atomic<bool> attr_set{false};
-  if (!attr_set) {
-    GX_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(ks), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_s));
-    GX_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(ka), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_a));
-    attr_set = true;
-  }
+  Device dev;
+  GX_HIP_TRY(device(&dev));
   const int nsplit    = g_gb_nsplit;
   const int nsub      = lds_nsub(max_groups, S);
   const unsigned sgrd = (unsigned)div_up(n, PTILE);
@@ -1619,15 +1605,15 @@ int launch_partitioned_minmax(const K* keys, const uint32_t* kvalid, const V* va
     if (sblocks > 2048) sblocks = 2048;
     hipLaunchKernelGGL((k_slot_sample<K>), dim3((unsigned)sblocks), dim3(256), 0, s, keys, kvalid, n, plan, stride, range_rows);
     hipLaunchKernelGGL((k_slot_plan<PartPlan>), dim3(1), dim3(NPART), 0, s, plan, n, stride, range_rows, (unsigned long long)slot_elems(n, stride));
-    hipLaunchKernelGGL(ks, dim3(sgrd), dim3(PBT), lds_s, s, keys, kvalid, vals, vvalid, n, plan, pkeys, pvals, pflags, NRANGE, cap, 0);
-    hipLaunchKernelGGL(ka, dim3(agrd), dim3(ABT), lds_a, s, pkeys, pvals, pflags, plan, nsplit, nsub, table, lg, mn, mx, cv, st, cap, 0);
+    GX_HIP_TRY(launch_lds(dev, ks, dim3(sgrd), dim3(PBT), lds_s, s, keys, kvalid, vals, vvalid, n, plan, pkeys, pvals, pflags, NRANGE, cap, 0));
+    GX_HIP_TRY(launch_lds(dev, ka, dim3(agrd), dim3(ABT), lds_a, s, pkeys, pvals, pflags, plan, nsplit, nsub, table, lg, mn, mx, cv, st, cap, 0));
     hipLaunchKernelGGL(k_part_reset_cursors, dim3(1), dim3(NPART), 0, s, plan);
     gated = 1;
   }
   hipLaunchKernelGGL((k_part_hist<K>), dim3((unsigned)(hb * NRANGE)), dim3(256), 0, s, keys, kvalid, n, plan, g_gb_nrange, gated);
   hipLaunchKernelGGL(k_part_offsets, dim3(1), dim3(NPART), 0, s, plan, gated);
-  hipLaunchKernelGGL(ks, dim3(sgrd), dim3(PBT), lds_s, s, keys, kvalid, vals, vvalid, n, plan, pkeys, pvals, pflags, g_gb_nrange, 0u, gated);
-  hipLaunchKernelGGL(ka, dim3(agrd), dim3(ABT), lds_a, s, pkeys, pvals, pflags, plan, nsplit, nsub, table, lg, mn, mx, cv, st, 0u, gated);
+  GX_HIP_TRY(launch_lds(dev, ks, dim3(sgrd), dim3(PBT), lds_s, s, keys, kvalid, vals, vvalid, n, plan, pkeys, pvals, pflags, g_gb_nrange, 0u, gated));
+  GX_HIP_TRY(launch_lds(dev, ka, dim3(agrd), dim3(ABT), lds_a, s, pkeys, pvals, pflags, plan, nsplit, nsub, table, lg, mn, mx, cv, st, 0u, gated));
   GX_LAUNCH_CHECK();
   return 0;
 }
@@ -2298,12 +2284,8 @@ int wide_impl(const void* const* key_cols, const void* vals, int64_t n, int64_t 
     constexpr size_t lds_a = (size_t)S * (16 + 8 * W + 8);
     auto ks                = k_wide_scatter<W, V>;
     auto ka                = k_wide_aggregate<W, V, IS_FLOAT>;
-    static std::atomic<bool> attr_set{false};
-    if (!attr_set) {
-      GX_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(ks), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_s));
-      GX_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(ka), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_a));
-      attr_set = true;
-    }
+    Device dev;
+    GX_HIP_TRY(device(&dev));
     // workgroups per partition: the groups one LDS table has to hold stay under half of its slots
     const double per_part = (double)(max_groups < 1 ? 1 : max_groups) / (double)(1 << g_gb_pbits);
     int nsub              = 1;
@@ -2315,8 +2297,8 @@ int wide_impl(const void* const* key_cols, const void* vals, int64_t n, int64_t 
     if (sblocks < 1) sblocks = 1;
     hipLaunchKernelGGL((k_wide_sample<W>), dim3((unsigned)sblocks), dim3(256), 0, s, kc, n, plan, stride, range_rows);
     hipLaunchKernelGGL((k_slot_plan<WidePlan>), dim3(1), dim3(NPART), 0, s, plan, n, stride, range_rows, (unsigned long long)elems);
-    hipLaunchKernelGGL(ks, dim3((unsigned)wtiles), dim3(PBT), lds_s, s, kc, static_cast<const V*>(vals), n, plan, pk, pv);
-    hipLaunchKernelGGL(ka, dim3((unsigned)((1 << g_gb_pbits) * nsub)), dim3(ABT), lds_a, s, pk, pv, plan, nsub, max_groups, ok, out_sum, out_cv);
+    GX_HIP_TRY(launch_lds(dev, ks, dim3((unsigned)wtiles), dim3(PBT), lds_s, s, kc, static_cast<const V*>(vals), n, plan, pk, pv));
+    GX_HIP_TRY(launch_lds(dev, ka, dim3((unsigned)((1 << g_gb_pbits) * nsub)), dim3(ABT), lds_a, s, pk, pv, plan, nsub, max_groups, ok, out_sum, out_cv));
   }
   hipLaunchKernelGGL(k_wide_finish, dim3(1), dim3(1), 0, s, plan, max_groups, reinterpret_cast<long long*>(ngroups));
   GX_LAUNCH_CHECK();

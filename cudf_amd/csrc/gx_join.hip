@@ -4094,18 +4094,12 @@ int pj_partition_fn(const K* keys, int64_t n, int pbits, PjPlan* plan, K* pkeys,
   auto k4          = k_pj_scatter<K, 8, 512, F>;
   auto k8          = k_pj_scatter<K, 16, 512, F>;
   auto k16         = k_pj_scatter<K, 16, 1024, F>;
-  static std::atomic<bool> attr_set{false};  // per instantiation
-  if (!attr_set) {
-    const int lds_max = 160 * 1024 - 256;
-    GX_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k4), hipFuncAttributeMaxDynamicSharedMemorySize, lds_max));
-    GX_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k8), hipFuncAttributeMaxDynamicSharedMemorySize, lds_max));
-    GX_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k16), hipFuncAttributeMaxDynamicSharedMemorySize, lds_max));
-    attr_set = true;
-  }
+  Device dev;
+  GX_HIP_TRY(device(&dev));
   const unsigned grid = (unsigned)div_up(n, (int64_t)tile_rows);
-  if (tile_rows == 16384) hipLaunchKernelGGL(k16, dim3(grid), dim3(1024), lds, s, keys, n, plan, pbits, rrows, pkeys, pidx, part_of, row0, spec_cap, payload);
-  else if (tile_rows == 8192) hipLaunchKernelGGL(k8, dim3(grid), dim3(512), lds, s, keys, n, plan, pbits, rrows, pkeys, pidx, part_of, row0, spec_cap, payload);
-  else hipLaunchKernelGGL(k4, dim3(grid), dim3(512), lds, s, keys, n, plan, pbits, rrows, pkeys, pidx, part_of, row0, spec_cap, payload);
+  if (tile_rows == 16384) GX_HIP_TRY(launch_lds(dev, k16, dim3(grid), dim3(1024), lds, s, keys, n, plan, pbits, rrows, pkeys, pidx, part_of, row0, spec_cap, payload));
+  else if (tile_rows == 8192) GX_HIP_TRY(launch_lds(dev, k8, dim3(grid), dim3(512), lds, s, keys, n, plan, pbits, rrows, pkeys, pidx, part_of, row0, spec_cap, payload));
+  else GX_HIP_TRY(launch_lds(dev, k4, dim3(grid), dim3(512), lds, s, keys, n, plan, pbits, rrows, pkeys, pidx, part_of, row0, spec_cap, payload));
   if (profile) jprof_mark(2, s);
   GX_LAUNCH_CHECK();
   return 0;
@@ -4248,57 +4242,12 @@ int probe_partitioned_impl2(const K* keys, int64_t n, const Slot<K>* slots, uint
   }
   constexpr size_t lds_p = ((size_t)1 << (PJ_SUB_LOG2 - 1)) + PP_TAGPAD + (size_t)6 * PP_ROWS * sizeof(int32_t);
   const size_t lds_s     = (rec || win_soa) ? (size_t)8192 * 12 + ((size_t)8 << pbits) : (size_t)16384 * sizeof(K) + ((size_t)8 << pbits);
-  static std::atomic<bool> attr_set{false};  // per instantiation
-  static int num_cus     = 0;
-  if (!attr_set) {
-    const int lds_max = 160 * 1024 - 256;
-    GX_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kspec), hipFuncAttributeMaxDynamicSharedMemorySize, lds_max));
-    GX_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kexact), hipFuncAttributeMaxDynamicSharedMemorySize, lds_max));
-    if constexpr (sizeof(K) == 8) {
-      GX_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k_pj2_scatter_rec<16, false, false, true, false, F>), hipFuncAttributeMaxDynamicSharedMemorySize, lds_max));
-      GX_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k_pj2_scatter_rec<16, false, false, true, true, F>), hipFuncAttributeMaxDynamicSharedMemorySize, lds_max));
-      GX_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k_pj2_scatter_rec<16, false, true, true, false, F>), hipFuncAttributeMaxDynamicSharedMemorySize, lds_max));
-      GX_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k_pj2_scatter_rec<16, false, true, true, true, F>), hipFuncAttributeMaxDynamicSharedMemorySize, lds_max));
-      GX_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k_pj2_scatter_rec<16, true, false, true, false, F>), hipFuncAttributeMaxDynamicSharedMemorySize, lds_max));
-      GX_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k_pj2_scatter_rec<16, true, false, true, true, F>), hipFuncAttributeMaxDynamicSharedMemorySize, lds_max));
-      GX_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k_pj2_scatter_rec<16, true, true, true, false, F>), hipFuncAttributeMaxDynamicSharedMemorySize, lds_max));
-      GX_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k_pj2_scatter_rec<16, true, true, true, true, F>), hipFuncAttributeMaxDynamicSharedMemorySize, lds_max));
-      GX_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k_pj2_scatter_rec<16, false, false, false, false, F>), hipFuncAttributeMaxDynamicSharedMemorySize, lds_max));
-      GX_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k_pj2_scatter_rec<16, false, false, false, true, F>), hipFuncAttributeMaxDynamicSharedMemorySize, lds_max));
-      GX_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k_pj2_scatter_rec<16, false, true, false, false, F>), hipFuncAttributeMaxDynamicSharedMemorySize, lds_max));
-      GX_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k_pj2_scatter_rec<16, false, true, false, true, F>), hipFuncAttributeMaxDynamicSharedMemorySize, lds_max));
-      GX_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k_pj2_scatter_rec<16, true, false, false, false, F>), hipFuncAttributeMaxDynamicSharedMemorySize, lds_max));
-      GX_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k_pj2_scatter_rec<16, true, false, false, true, F>), hipFuncAttributeMaxDynamicSharedMemorySize, lds_max));
-      GX_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k_pj2_scatter_rec<16, true, true, false, false, F>), hipFuncAttributeMaxDynamicSharedMemorySize, lds_max));
-      GX_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k_pj2_scatter_rec<16, true, true, false, true, F>), hipFuncAttributeMaxDynamicSharedMemorySize, lds_max));
-      GX_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k_pj2_scatter_rec<24, false, false, true, false, F>), hipFuncAttributeMaxDynamicSharedMemorySize, lds_max));
-      GX_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k_pj2_scatter_rec<24, false, false, true, true, F>), hipFuncAttributeMaxDynamicSharedMemorySize, lds_max));
-      GX_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k_pj2_scatter_rec<24, false, true, true, false, F>), hipFuncAttributeMaxDynamicSharedMemorySize, lds_max));
-      GX_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k_pj2_scatter_rec<24, false, true, true, true, F>), hipFuncAttributeMaxDynamicSharedMemorySize, lds_max));
-      GX_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k_pj2_scatter_rec<24, true, false, true, false, F>), hipFuncAttributeMaxDynamicSharedMemorySize, lds_max));
-      GX_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k_pj2_scatter_rec<24, true, false, true, true, F>), hipFuncAttributeMaxDynamicSharedMemorySize, lds_max));
-      GX_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k_pj2_scatter_rec<24, true, true, true, false, F>), hipFuncAttributeMaxDynamicSharedMemorySize, lds_max));
-      GX_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k_pj2_scatter_rec<24, true, true, true, true, F>), hipFuncAttributeMaxDynamicSharedMemorySize, lds_max));
-      GX_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k_pj2_probe_pipe<K, false, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_p));
-      GX_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k_pj2_probe_pipe<K, false, false, true, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_p));
-      GX_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k_pj2_probe_pipe<K, false, false, true, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_p));
-      GX_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k_pj2_probe_pipe<K, false, false, true, 3>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_p));
-      GX_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k_pj2_probe_pipe<K, false, false, true, 0, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_p));
-      GX_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k_pj2_probe_pipe<K, false, false, true, 4, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_p));
-    }
-    GX_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k_pj2_probe_pipe<K, true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_p));
-    GX_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k_pj2_probe_pipe<K, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_p));
-    GX_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k_pj2_probe_pipe<K, true, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_p));
-    GX_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k_pj2_probe_pipe<K, false, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_p));
-    int dev = 0;
-    GX_HIP_TRY(hipGetDevice(&dev));
-    GX_HIP_TRY(hipDeviceGetAttribute(&num_cus, hipDeviceAttributeMultiprocessorCount, dev));
-    attr_set = true;
-  }
+  Device dev;
+  GX_HIP_TRY(device(&dev));
   const int64_t ntiles = div_up(n, (int64_t)TILE);
   const int64_t rrows  = pj_range_rows(n, TILE);
   const int xmajor     = (g_pj_xp & (1 << 24)) ? 0 : 1;  // bit 24 (measurement): the fill-counter atomics on fill[] itself, as until round 6
-  int64_t grid         = num_cus > 0 ? num_cus : 256;
+  int64_t grid         = dev.cus;
   if (((g_pj_xp >> 8) & 255) != 0) grid = ((g_pj_xp >> 8) & 255) * 4;  // measurement: bits 8-15 = workgroups of the partition pass / 4
   grid                 = grid / PJ_NR * PJ_NR;  // v % 8 must stay the XCD of a workgroup over its whole walk
   if (grid < PJ_NR) grid = PJ_NR;
@@ -4311,7 +4260,7 @@ int probe_partitioned_impl2(const K* keys, int64_t n, const Slot<K>* slots, uint
   // ---- speculative pass
   // (record form: full tiles, then the ragged tail as one more workgroup)
   const int64_t nfull = n / TILE;
-  auto launch_rec = [&](bool exact) {
+  auto launch_rec = [&](bool exact) -> int {
     if constexpr (sizeof(K) == 8) {
       const uint64_t* k64 = reinterpret_cast<const uint64_t*>(keys);
       PjRec* precs        = reinterpret_cast<PjRec*>(pkeys);
@@ -4319,10 +4268,10 @@ int probe_partitioned_impl2(const K* keys, int64_t n, const Slot<K>* slots, uint
       const int64_t tail0 = nfull * TILE;
 #define GX_PJ_REC2(RPT_, EX_, AOS_, PAY_)                                                                                                       \
   do {                                                                                                                                          \
-    if (gf) hipLaunchKernelGGL((k_pj2_scatter_rec<RPT_, EX_, false, AOS_, PAY_, F>), dim3(gf), dim3(1024), lds_s, s, k64, n, plan2, plan, pbits, \
-                               rrows, cap, nfull, (int64_t)0, precs, part_of, row0, payload, pidx, xmajor);                                             \
-    if (tail0 < n) hipLaunchKernelGGL((k_pj2_scatter_rec<RPT_, EX_, true, AOS_, PAY_, F>), dim3(1), dim3(1024), lds_s, s, k64, n, plan2, plan,   \
-                                      pbits, rrows, cap, (int64_t)1, tail0, precs, part_of, row0, payload, pidx, xmajor);                               \
+    if (gf) GX_HIP_TRY(launch_lds(dev, (k_pj2_scatter_rec<RPT_, EX_, false, AOS_, PAY_, F>), dim3(gf), dim3(1024), lds_s, s, k64, n, plan2, plan, \
+                                  pbits, rrows, cap, nfull, (int64_t)0, precs, part_of, row0, payload, pidx, xmajor));                          \
+    if (tail0 < n) GX_HIP_TRY(launch_lds(dev, (k_pj2_scatter_rec<RPT_, EX_, true, AOS_, PAY_, F>), dim3(1), dim3(1024), lds_s, s, k64, n, plan2,  \
+                                         plan, pbits, rrows, cap, (int64_t)1, tail0, precs, part_of, row0, payload, pidx, xmajor));             \
   } while (0)
 #define GX_PJ_REC(RPT_, EX_, AOS_)                              \
   do {                                                          \
@@ -4339,9 +4288,10 @@ int probe_partitioned_impl2(const K* keys, int64_t n, const Slot<K>* slots, uint
 #undef GX_PJ_REC2
 #undef GX_PJ_REC
     }
+    return 0;
   };
-  if (rec || win_soa) launch_rec(false);
-  else hipLaunchKernelGGL(kspec, dim3((unsigned)grid), dim3(1024), lds_s, s, keys, n, plan2, plan, pbits, rrows, cap, ntiles, pkeys, pidx, part_of, row0, payload, xmajor);
+  if (rec || win_soa) GX_HIP_TRY(launch_rec(false));
+  else GX_HIP_TRY(launch_lds(dev, kspec, dim3((unsigned)grid), dim3(1024), lds_s, s, keys, n, plan2, plan, pbits, rrows, cap, ntiles, pkeys, pidx, part_of, row0, payload, xmajor));
   jprof_mark(2, s);
   // (6 / 7: the same kernel with the tag windows read from the L2 -- the partition pass then cuts 2^20-slot sub-tables, see pj_bits)
   // the probe kernel: 0 the pipelined LDS-tag gang probe; 2 / 3 the L2-resident direct probe with 4 / 2 rows per thread (round 5,
@@ -4356,26 +4306,31 @@ int probe_partitioned_impl2(const K* keys, int64_t n, const Slot<K>* slots, uint
   const unsigned alt_rpt    = (pk == 2 || pk == 5 || pk == 7) ? 4u : 2u;
   const size_t alt_lds      = (pk == 4 || pk == 5) ? ((size_t)1 << (PJ_SUB_LOG2 - 1)) + PP_TAGPAD : 0;  // (6 / 7: no LDS tags)
   const unsigned piece_rows = !alt ? (unsigned)PP_ROWS : (pk >= 4 ? (unsigned)(PT_PW * GX_WAVE) * alt_rpt : alt_bt * alt_rpt);
-  static std::atomic<int> alt_wgs[6];  // resident workgroups per CU of the alternative kernels (occupancy query, once each; zero-initialised)
-  if (alt && alt_wgs[pk - 2] == 0) {
-    if (alt_lds) GX_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kalt), hipFuncAttributeMaxDynamicSharedMemorySize, (int)alt_lds));
-    int nb = 0;
-    GX_HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, reinterpret_cast<const void*>(kalt), (int)alt_bt, alt_lds));
-    alt_wgs[pk - 2] = nb > 0 ? nb : 1;
+  // resident workgroups per CU of the alternative kernels (occupancy query, once per kernel and device; zero-initialised)
+  static std::atomic<int> alt_wgs[6][LDS_BOOK_DEVICES];
+  int awgs = 0;
+  if (alt) {
+    std::atomic<int>* memo = dev.id < LDS_BOOK_DEVICES ? &alt_wgs[pk - 2][dev.id] : nullptr;
+    if (memo) awgs = *memo;
+    if (awgs == 0) {
+      GX_HIP_TRY(max_resident_wgs(dev, reinterpret_cast<const void*>(kalt), (int)alt_bt, alt_lds, &awgs));
+      if (memo) *memo = awgs;
+    }
   }
-  auto launch_probe = [&](const PieceTable& t) {
+  auto launch_probe = [&](const PieceTable& t) -> int {
     if (alt) {
-      const int64_t g = (int64_t)(num_cus > 0 ? num_cus : 256) * alt_wgs[pk - 2];
-      hipLaunchKernelGGL(kalt, dim3((unsigned)g), dim3(alt_bt), alt_lds, s, pkeys, pidx, t, pbits, slots, lg, left_outer, out_probe, out_build, capacity, cur);
+      const int64_t g = (int64_t)dev.cus * awgs;
+      GX_HIP_TRY(launch_lds(dev, kalt, dim3((unsigned)g), dim3(alt_bt), alt_lds, s, pkeys, pidx, t, pbits, slots, lg, left_outer, out_probe, out_build, capacity, cur));
     } else {
-      int64_t g = num_cus > 0 ? num_cus : 256;
+      int64_t g = dev.cus;
       if (((g_pj_xp >> 16) & 255) != 0) g = ((g_pj_xp >> 16) & 255) * 4;  // measurement: bits 16-23 = workgroups of the probe / 4
       if (g > 256 && longp) g = 256;  // (the overflow list has 256 slices)
-      hipLaunchKernelGGL(kprobe, dim3((unsigned)g), dim3(PP_BT), lds_p, s, pkeys, pidx, t, pbits, slots, lg, left_outer, out_probe, out_build, capacity, cur);
+      GX_HIP_TRY(launch_lds(dev, kprobe, dim3((unsigned)g), dim3(PP_BT), lds_p, s, pkeys, pidx, t, pbits, slots, lg, left_outer, out_probe, out_build, capacity, cur));
       if (t.ovf)
         hipLaunchKernelGGL((k_pj2_probe_rare<K>), dim3((unsigned)g * PR_SUB), dim3(256), 0, s, t.ovf, t.ovf_cap, t.ovf_count, slots, lg, left_outer, out_probe, out_build,
                            capacity, cur);
     }
+    return 0;
   };
   hipLaunchKernelGGL(k_pj2_offsets, dim3(1), dim3(1024), 0, s, plan2, pbits, cap, piece_rows, xmajor);
   PieceTable pt{plan2->chunk0, plan2->list_chunk0, plan2->ticket, nullptr, plan2->fill, cap, PJ_NR, 0u, nullptr, nullptr, 0u, nullptr};
@@ -4388,17 +4343,17 @@ int probe_partitioned_impl2(const K* keys, int64_t n, const Slot<K>* slots, uint
     pt.fixedk = (cap + piece_rows - 1) / piece_rows;
     pt.gate   = &plan2->fallback;
   }
-  launch_probe(pt);
+  GX_HIP_TRY(launch_probe(pt));
   // ---- exact sequence: every kernel returns at once unless plan2->fallback is set
   int64_t hb = div_up(n, 256 * 8 * 4 * PJ_NR);
   if (hb > 256) hb = 256;
   if (hb < 1) hb = 1;
   hipLaunchKernelGGL((k_pj_hist<K, F>), dim3((unsigned)(hb * PJ_NR)), dim3(256), 0, s, keys, n, plan, pbits, rrows, part_of, &plan2->fallback);
   hipLaunchKernelGGL(k_pj_offsets, dim3(1), dim3(1024), 0, s, plan, pbits, piece_rows, &plan2->fallback);
-  if (rec || win_soa) launch_rec(true);
-  else hipLaunchKernelGGL(kexact, dim3((unsigned)grid), dim3(1024), lds_s, s, keys, n, plan2, plan, pbits, rrows, cap, ntiles, pkeys, pidx, part_of, row0, payload, xmajor);
+  if (rec || win_soa) GX_HIP_TRY(launch_rec(true));
+  else GX_HIP_TRY(launch_lds(dev, kexact, dim3((unsigned)grid), dim3(1024), lds_s, s, keys, n, plan2, plan, pbits, rrows, cap, ntiles, pkeys, pidx, part_of, row0, payload, xmajor));
   PieceTable pe{plan->chunk0, plan->list_chunk0, plan2->ticket_exact, plan->offset, nullptr, 0u, 1, 0u, nullptr, pt.ovf, pt.ovf_cap, pt.ovf_count};
-  launch_probe(pe);
+  GX_HIP_TRY(launch_probe(pe));
   jprof_mark(3, s);
   g_jprof.marked = g_jprof.enabled;
   GX_LAUNCH_CHECK();
@@ -4453,29 +4408,19 @@ int probe_partitioned_impl(const void* keys, int64_t n, const void* table, size_
   const int64_t max_chunks = div_up(n, (int64_t)chunk_rows) + (1 << pbits);
   if (use_pipe) {
     constexpr size_t lds_p = ((size_t)1 << (PJ_SUB_LOG2 - 1)) + (size_t)6 * PP_ROWS * sizeof(int32_t);
-    static std::atomic<bool> pattr_set{false};
-    static int num_cus     = 0;
-    if (!pattr_set) {
-      GX_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k_pj_probe_pipe<K>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_p));
-      int dev = 0;
-      GX_HIP_TRY(hipGetDevice(&dev));
-      GX_HIP_TRY(hipDeviceGetAttribute(&num_cus, hipDeviceAttributeMultiprocessorCount, dev));
-      pattr_set = true;
-    }
+    Device dev;
+    GX_HIP_TRY(device(&dev));
     // persistent workgroups, one per CU (the LDS admits no second one); pieces come from per-XCD tickets
-    int64_t grid = num_cus > 0 ? num_cus : 256;
+    int64_t grid = dev.cus;
     if (grid > max_chunks) grid = max_chunks;
-    hipLaunchKernelGGL((k_pj_probe_pipe<K>), dim3((unsigned)grid), dim3(PP_BT), lds_p, s, pkeys, pidx, plan, pbits, slots, lg,
-                       left_outer, out_probe, out_build, capacity, reinterpret_cast<unsigned long long*>(cursor));
+    GX_HIP_TRY(launch_lds(dev, (k_pj_probe_pipe<K>), dim3((unsigned)grid), dim3(PP_BT), lds_p, s, pkeys, pidx, plan, pbits, slots, lg,
+                               left_outer, out_probe, out_build, capacity, reinterpret_cast<unsigned long long*>(cursor)));
   } else if (use_tags) {
     constexpr size_t lds_t = (size_t)1 << (PJ_SUB_LOG2 - 1);
-    static std::atomic<bool> tattr_set{false};
-    if (!tattr_set) {
-      GX_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k_pj_probe_tags<K>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_t));
-      tattr_set = true;
-    }
-    hipLaunchKernelGGL((k_pj_probe_tags<K>), dim3((unsigned)max_chunks), dim3(PJ_BT), lds_t, s, pkeys, pidx, plan, pbits, slots, lg,
-                       left_outer, out_probe, out_build, capacity, reinterpret_cast<unsigned long long*>(cursor), chunk_rows);
+    Device dev;
+    GX_HIP_TRY(device(&dev));
+    GX_HIP_TRY(launch_lds(dev, (k_pj_probe_tags<K>), dim3((unsigned)max_chunks), dim3(PJ_BT), lds_t, s, pkeys, pidx, plan, pbits, slots, lg,
+                               left_outer, out_probe, out_build, capacity, reinterpret_cast<unsigned long long*>(cursor), chunk_rows));
   } else {
     hipLaunchKernelGGL((k_pj_probe<K>), dim3((unsigned)max_chunks), dim3(PJ_BT), 0, s, pkeys, pidx, plan, pbits, slots, lg,
                        left_outer, out_probe, out_build, capacity, reinterpret_cast<unsigned long long*>(cursor));
@@ -4537,12 +4482,9 @@ int build_partitioned_impl(const void* keys, int64_t n, void* table, size_t tabl
     GX_HIP_TRY(hipMemsetAsync(fix, 0, 128, s));
     const size_t lds = (size_t)(1u << PJ_SUB_LOG2) / 2;
     auto kb          = k_bs_build<K>;
-    static std::atomic<bool> attr_set{false};  // per instantiation
-    if (!attr_set) {
-      GX_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kb), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-      attr_set = true;
-    }
-    hipLaunchKernelGGL(kb, dim3(1u << pbits), dim3(BS_BT), lds, s, pkeys, pidx, plan, slots, tags, lg, fix);
+    Device dev;
+    GX_HIP_TRY(device(&dev));
+    GX_HIP_TRY(launch_lds(dev, kb, dim3(1u << pbits), dim3(BS_BT), lds, s, pkeys, pidx, plan, slots, tags, lg, fix));
     hipLaunchKernelGGL((k_bs_fixup<K>), dim3(256), dim3(256), 0, s, pkeys, pidx, n, slots, tags, lg, fix, 0);
     hipLaunchKernelGGL((k_bs_fixup<K>), dim3(1024), dim3(256), 0, s, pkeys, pidx, n, slots, tags, lg, fix, 1);
     GX_LAUNCH_CHECK();

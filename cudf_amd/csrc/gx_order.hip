@@ -980,24 +980,14 @@ static int sorted_order_words(const void* keys, int64_t n, int descending, int32
   const uint64_t desc_mask = descending ? ~0ull : 0ull;
   int ib                   = 1;
   while (((int64_t)1 << ib) < n) ++ib;
-  static std::atomic<bool> attr_set{false};
-  static int num_cus = 0;
-  if (!attr_set) {
-    GX_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k_om_plan), hipFuncAttributeMaxDynamicSharedMemorySize, OM_S * 8));
-    GX_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k_om_map<KIND>), hipFuncAttributeMaxDynamicSharedMemorySize, OM_B * 28 + OM_LUT * 2 + 64));
-    GX_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k_om_count<KIND>), hipFuncAttributeMaxDynamicSharedMemorySize, OM_B * 16 + OM_LUT * 2 + 64));
-    GX_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k_om_long<OneCol<KIND>>), hipFuncAttributeMaxDynamicSharedMemorySize, OM_LDSRUN * 12));
-    int dev = 0;
-    GX_HIP_TRY(hipGetDevice(&dev));
-    GX_HIP_TRY(hipDeviceGetAttribute(&num_cus, hipDeviceAttributeMultiprocessorCount, dev));
-    attr_set = true;
-  }
-  const unsigned cus = (unsigned)(num_cus > 0 ? num_cus : 256);
+  Device dev;
+  GX_HIP_TRY(device(&dev));
+  const unsigned cus = (unsigned)dev.cus;
   hipLaunchKernelGGL((k_om_sample<KIND>), dim3(OM_S / 256), dim3(256), 0, s, k, n, desc_mask, L.samp);
-  hipLaunchKernelGGL(k_om_plan, dim3(1), dim3(1024), OM_S * 8, s, (const uint64_t*)L.samp, L.plan, ib, n);
-  hipLaunchKernelGGL((k_om_count<KIND>), dim3(cus), dim3(256), OM_B * 16 + OM_LUT * 2 + 64, s, k, n, desc_mask, L.plan);
+  GX_HIP_TRY(launch_lds(dev, k_om_plan, dim3(1), dim3(1024), OM_S * 8, s, (const uint64_t*)L.samp, L.plan, ib, n));
+  GX_HIP_TRY(launch_lds(dev, (k_om_count<KIND>), dim3(cus), dim3(256), OM_B * 16 + OM_LUT * 2 + 64, s, k, n, desc_mask, L.plan));
   hipLaunchKernelGGL(k_om_plan2, dim3(1), dim3(1024), 0, s, L.plan);
-  hipLaunchKernelGGL((k_om_map<KIND>), dim3(cus), dim3(1024), OM_B * 28 + OM_LUT * 2 + 64, s, k, n, desc_mask, L.plan, L.words);
+  GX_HIP_TRY(launch_lds(dev, (k_om_map<KIND>), dim3(cus), dim3(1024), OM_B * 28 + OM_LUT * 2 + 64, s, k, n, desc_mask, L.plan, L.words));
   size_t ib2 = L.inner_bytes;
   rc         = gx_sort_keys(GX_UINT64, L.words, L.sorted, n, 0, L.inner, &ib2, s);
   if (rc) return rc;
@@ -1009,8 +999,8 @@ static int sorted_order_words(const void* keys, int64_t n, int descending, int32
   hipLaunchKernelGGL((k_om_finish_b<OneCol<KIND>>), dim3(g.wgs), dim3(256), 0, s, (const uint64_t*)L.sorted, n, pol, L.plan, out, (const unsigned int*)R.heads,
                      (const RunSeg*)R.segs, g.seg_cap, R.longlist, (unsigned int)g.long_cap);
   hipLaunchKernelGGL((k_om_medium<OneCol<KIND>>), dim3(cus * 8), dim3(256), 0, s, (const uint64_t*)L.sorted, pol, L.plan, (const LongRun*)R.longlist, (unsigned int)g.long_cap, R.wglist, out);
-  hipLaunchKernelGGL((k_om_long<OneCol<KIND>>), dim3(cus), dim3(1024), OM_LDSRUN * 12, s, (const uint64_t*)L.sorted, pol, (const OmPlan*)L.plan, out,
-                     (const LongRun*)R.wglist, (unsigned int)g.long_cap, R.gk, R.gr);
+  GX_HIP_TRY(launch_lds(dev, (k_om_long<OneCol<KIND>>), dim3(cus), dim3(1024), OM_LDSRUN * 12, s, (const uint64_t*)L.sorted, pol, (const OmPlan*)L.plan, out,
+                             (const LongRun*)R.wglist, (unsigned int)g.long_cap, R.gk, R.gr));
   if (KIND == K_FLOAT && descending) hipLaunchKernelGGL(k_om_reverse_nans, dim3(cus), dim3(256), 0, s, out, (const OmPlan*)L.plan);
   GX_LAUNCH_CHECK();
   return 0;
@@ -1057,26 +1047,16 @@ static int sorted_order_table(int ncols, const int* dtypes, const void* const* c
   }
   int ib = 1;
   while (((int64_t)1 << ib) < n) ++ib;
-  static std::atomic<bool> attr_set{false};
-  static int num_cus = 0;
-  if (!attr_set) {
-    GX_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k_om_plan), hipFuncAttributeMaxDynamicSharedMemorySize, OM_S * 8));
-    GX_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k_omt_map), hipFuncAttributeMaxDynamicSharedMemorySize, OM_B * 28 + OM_LUT * 2 + 64));
-    GX_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k_omt_count), hipFuncAttributeMaxDynamicSharedMemorySize, OM_B * 16 + OM_LUT * 2 + 64));
-    GX_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k_om_long<Tuple>), hipFuncAttributeMaxDynamicSharedMemorySize, OM_LDSRUN * 12));
-    int dev = 0;
-    GX_HIP_TRY(hipGetDevice(&dev));
-    GX_HIP_TRY(hipDeviceGetAttribute(&num_cus, hipDeviceAttributeMultiprocessorCount, dev));
-    attr_set = true;
-  }
-  const unsigned cus = (unsigned)(num_cus > 0 ? num_cus : 256);
+  Device dev;
+  GX_HIP_TRY(device(&dev));
+  const unsigned cus = (unsigned)dev.cus;
   for (int c = ncols - 1; c >= 0; --c) {  // from the last column to the leading one: each level reads the fraction the level behind it left
     OmPlan* P = L.plan + c;
     hipLaunchKernelGGL(k_omt_sample, dim3(OM_S / 256), dim3(256), 0, s, t.c[c], n, L.samp);
-    hipLaunchKernelGGL(k_om_plan, dim3(1), dim3(1024), OM_S * 8, s, (const uint64_t*)L.samp, P, c == 0 ? ib : 0, n);
-    hipLaunchKernelGGL(k_omt_count, dim3(cus), dim3(256), OM_B * 16 + OM_LUT * 2 + 64, s, t.c[c], n, P);
+    GX_HIP_TRY(launch_lds(dev, k_om_plan, dim3(1), dim3(1024), OM_S * 8, s, (const uint64_t*)L.samp, P, c == 0 ? ib : 0, n));
+    GX_HIP_TRY(launch_lds(dev, k_omt_count, dim3(cus), dim3(256), OM_B * 16 + OM_LUT * 2 + 64, s, t.c[c], n, P));
     hipLaunchKernelGGL(k_om_plan2, dim3(1), dim3(1024), 0, s, P);
-    hipLaunchKernelGGL(k_omt_map, dim3(cus), dim3(1024), OM_B * 28 + OM_LUT * 2 + 64, s, t.c[c], n, (const OmPlan*)P, L.words, c == ncols - 1 ? 1 : 0, c == 0 ? 1 : 0);
+    GX_HIP_TRY(launch_lds(dev, k_omt_map, dim3(cus), dim3(1024), OM_B * 28 + OM_LUT * 2 + 64, s, t.c[c], n, (const OmPlan*)P, L.words, c == ncols - 1 ? 1 : 0, c == 0 ? 1 : 0));
   }
   size_t ib2 = L.inner_bytes;
   rc         = gx_sort_keys(GX_UINT64, L.words, L.sorted, n, 0, L.inner, &ib2, s);
@@ -1088,8 +1068,8 @@ static int sorted_order_table(int ncols, const int* dtypes, const void* const* c
   hipLaunchKernelGGL((k_om_finish_b<Tuple>), dim3(g.wgs), dim3(256), 0, s, (const uint64_t*)L.sorted, n, pol, L.plan, out, (const unsigned int*)R.heads,
                      (const RunSeg*)R.segs, g.seg_cap, R.longlist, (unsigned int)g.long_cap);
   hipLaunchKernelGGL((k_om_medium<Tuple>), dim3(cus * 8), dim3(256), 0, s, (const uint64_t*)L.sorted, pol, L.plan, (const LongRun*)R.longlist, (unsigned int)g.long_cap, R.wglist, out);
-  hipLaunchKernelGGL((k_om_long<Tuple>), dim3(cus), dim3(1024), OM_LDSRUN * 12, s, (const uint64_t*)L.sorted, pol, (const OmPlan*)L.plan, out, (const LongRun*)R.wglist,
-                     (unsigned int)g.long_cap, R.gk, R.gr);
+  GX_HIP_TRY(launch_lds(dev, (k_om_long<Tuple>), dim3(cus), dim3(1024), OM_LDSRUN * 12, s, (const uint64_t*)L.sorted, pol, (const OmPlan*)L.plan, out, (const LongRun*)R.wglist,
+                             (unsigned int)g.long_cap, R.gk, R.gr));
   GX_LAUNCH_CHECK();
   return 0;
 }

@@ -3794,6 +3794,8 @@ int sort_impl(const void* keys_in, void* keys_out, const int32_t* vals_in, int32
 
   GX_HIP_TRY(hipMemsetAsync(plan, 0, sizeof(SortPlan), stream));
   if (n == 0) return 0;
+  Device dev;
+  GX_HIP_TRY(device(&dev));
   if (algo != 1 && !fc.on) GX_HIP_TRY(hipMemsetAsync(status, 0, status_words * sizeof(unsigned long long), stream));
   if (cells) GX_HIP_TRY(hipMemsetAsync(hist2, 0, (size_t)4 * BINS * NB2MAX * sizeof(uint32_t), stream));
   const int64_t range_rows = try_hybrid ? div_up(msd_ntiles, NRANGE) * msd_tile : div_up(ntiles, NRANGE) * TILE;
@@ -3824,21 +3826,6 @@ int sort_impl(const void* keys_in, void* keys_out, const int32_t* vals_in, int32
       HfK kf1 = fc.bits2_max <= 8 ? (HfK)k_hf_scatter<KeyT, CK, 1, 8> : (fc.bits2_max == 9 ? (HfK)k_hf_scatter<KeyT, CK, 1, 9> : (HfK)k_hf_scatter<KeyT, CK, 1, 10>);
       HfK kf2 = fc.bits2_max <= 8 ? (HfK)k_hf_scatter<KeyT, CK, 2, 8> : (fc.bits2_max == 9 ? (HfK)k_hf_scatter<KeyT, CK, 2, 9> : (HfK)k_hf_scatter<KeyT, CK, 2, 10>);
       const int nbf = fc.bits2_max <= 8 ? 256 : (1 << fc.bits2_max);
-      static std::atomic<bool> fattr_set{false};
-      if (!fattr_set) {
-        GX_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k_hf_scatter<KeyT, CK, 2, 8>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_hf(256)));
-        GX_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k_hf_scatter<KeyT, CK, 2, 9>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_hf(512)));
-        GX_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k_hf_scatter<KeyT, CK, 2, 10>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_hf(1024)));
-        GX_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k_hf_scatter<KeyT, CK, 0, 8>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_hf(256)));
-        GX_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k_hf_scatter<KeyT, CK, 1, 8>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_hf(256)));
-        GX_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k_hf_scatter<KeyT, CK, 1, 9>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_hf(512)));
-        GX_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k_hf_scatter<KeyT, CK, 1, 10>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_hf(1024)));
-        GX_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k_local_sort<uint64_t, CK, HAS_VAL, 13, KeyT>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       (int)(((size_t)8 << 13) + (size_t)(((1 << 13) / 16 / GX_WAVE) * BINS + 32 + 2 * BINS) * 4)));
-        GX_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k_local_place<KeyT, CK, HAS_VAL, 13>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       (int)place_lds_bytes(13, WORD_BYTES)));
-        fattr_set = true;
-      }
       const int64_t step = (int64_t)fc.stride * HF_CHUNK;
       int64_t sblocks    = div_up(div_up(n, step), (int64_t)4 * 4);
       if (sblocks > 2048) sblocks = 2048;
@@ -3850,12 +3837,7 @@ int sort_impl(const void* keys_in, void* keys_out, const int32_t* vals_in, int32
       {
         // counting sort of a column whose varying bits are its low <= 15 (state 5; no-ops otherwise): histogram in LDS, scan, fill
         // (counters | group starts | group values live in the cell tables, unused on this branch and zeroed above)
-        static std::atomic<bool> cattr_set{false};
-        if (!cattr_set) {
-          GX_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k_cs_count<KeyT, CK>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(4u << CS_MAXBITS)));
-          cattr_set = true;
-        }
-        hipLaunchKernelGGL((k_cs_count<KeyT, CK>), dim3(256), dim3(CS_BT), (size_t)4 << CS_MAXBITS, stream, kin, n, desc_mask, plan, hist2);
+        GX_HIP_TRY(launch_lds(dev, (k_cs_count<KeyT, CK>), dim3(256), dim3(CS_BT), (size_t)4 << CS_MAXBITS, stream, kin, n, desc_mask, plan, hist2));
         hipLaunchKernelGGL(k_cs_scan, dim3(1), dim3(CS_BT), 0, stream, plan, (const uint32_t*)hist2, base2, xoff, n, NPASS);
         hipLaunchKernelGGL((k_cs_fill<KeyT, CK>), dim3(4096), dim3(256), 0, stream, bufA, n, desc_mask, (const SortPlan*)plan, (const uint32_t*)base2,
                            (const uint32_t*)xoff);
@@ -3869,16 +3851,9 @@ int sort_impl(const void* keys_in, void* keys_out, const int32_t* vals_in, int32
       int64_t ftiles_s = 0;
       if constexpr (sizeof(KeyT) == 8) {
         if (allow_split) {
-          static std::atomic<bool> sattr_set{false};
-          if (!sattr_set) {
-            GX_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k_sp_plan<CK>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(SP_NSAMP * 8)));
-            GX_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k_sp_level0<CK, 0>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sp_level0_lds()));
-            GX_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k_sp_level0<CK, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sp_level0_lds()));
-            sattr_set = true;
-          }
           ftiles_s               = div_up(n, (int64_t)SP_TILE);
           const int64_t frange_s = (ftiles_s / NRANGE) * SP_TILE;
-          hipLaunchKernelGGL((k_sp_plan<CK>), dim3(1), dim3(1024), (size_t)SP_NSAMP * 8, stream, kin, n, (uint64_t)desc_mask, plan, fc.bits2_max);
+          GX_HIP_TRY(launch_lds(dev, (k_sp_plan<CK>), dim3(1), dim3(1024), (size_t)SP_NSAMP * 8, stream, kin, n, (uint64_t)desc_mask, plan, fc.bits2_max));
           // (half the workgroups of k_hf_sample: each flushes 2048 + 4096 counters)
           hipLaunchKernelGGL((k_sp_sample<CK>), dim3((unsigned)(sblocks > 1024 ? 1024 : sblocks)), dim3(256), 0, stream, kin, n, (uint64_t)desc_mask, plan, fc.stride, frange_s);
           hipLaunchKernelGGL(k_hf_plan, dim3(1), dim3(BINS), 0, stream, plan, 1, (int)(8 * sizeof(KeyT)), n, fc.bits2, 1 << 13, fc.stride, frange_s, FT,
@@ -3887,18 +3862,18 @@ int sort_impl(const void* keys_in, void* keys_out, const int32_t* vals_in, int32
       }
       prof_mark(1, stream);
       prof_mark_h(0, stream);
-      hipLaunchKernelGGL(kf0, dim3((unsigned)ftiles), dim3(BT), lds_hf(256), stream, kin, slot0_buf, desc_mask, plan, hist2, 1u << 13, n, (KeyT*)nullptr);
+      GX_HIP_TRY(launch_lds(dev, kf0, dim3((unsigned)ftiles), dim3(BT), lds_hf(256), stream, kin, slot0_buf, desc_mask, plan, hist2, 1u << 13, n, (KeyT*)nullptr));
       if constexpr (sizeof(KeyT) == 8) {
         if (allow_split)
         {
-          hipLaunchKernelGGL((k_sp_level0<CK, 0>), dim3((unsigned)ftiles_s), dim3(BT), sp_level0_lds(), stream, kin, slot0_buf, (uint64_t)desc_mask, plan, n);
-          hipLaunchKernelGGL((k_sp_level0<CK, 1>), dim3((unsigned)ftiles_s), dim3(BT), sp_level0_lds(), stream, kin, slot0_buf, (uint64_t)desc_mask, plan, n);
+          GX_HIP_TRY(launch_lds(dev, (k_sp_level0<CK, 0>), dim3((unsigned)ftiles_s), dim3(BT), sp_level0_lds(), stream, kin, slot0_buf, (uint64_t)desc_mask, plan, n));
+          GX_HIP_TRY(launch_lds(dev, (k_sp_level0<CK, 1>), dim3((unsigned)ftiles_s), dim3(BT), sp_level0_lds(), stream, kin, slot0_buf, (uint64_t)desc_mask, plan, n));
         }
       }
       hipLaunchKernelGGL(k_hf_plan, dim3(1), dim3(BINS), 0, stream, plan, 2, (int)(8 * sizeof(KeyT)), n, fc.bits2, 1 << 13, fc.stride, frange, FT,
                          (unsigned long long)fc.slot_rows, g_cursor_margin, MIN_SHIFT2, fc.bits2_max, (unsigned long long)nb_buf);
       prof_mark_h(1, stream);
-      hipLaunchKernelGGL(kf1, dim3((unsigned)(ftiles + NRANGE * BINS)), dim3(BT), lds_hf(nbf), stream, slot0_buf, kb_scratch, desc_mask, plan, hist2, 1u << 13, n, bufA);
+      GX_HIP_TRY(launch_lds(dev, kf1, dim3((unsigned)(ftiles + NRANGE * BINS)), dim3(BT), lds_hf(nbf), stream, slot0_buf, kb_scratch, desc_mask, plan, hist2, 1u << 13, n, bufA));
       prof_mark_h(2, stream);
       hipLaunchKernelGGL(k_plan2, dim3(BINS), dim3(GX_WAVE), 0, stream, plan, hist2, base2, NPASS, 1);
       prof_mark_h(3, stream);
@@ -3907,13 +3882,13 @@ int sort_impl(const void* keys_in, void* keys_out, const int32_t* vals_in, int32
           hipLaunchKernelGGL((k_sp_fill<CK>), dim3(BINS, SP_FILL_Y), dim3(256), 0, stream, bufA, (uint64_t)desc_mask, (const SortPlan*)plan, (const uint32_t*)base2);
       }
       // (one workgroup per cell of the plan n suggests; when the device took the extra level-1 bit each of them walks two cells)
-      hipLaunchKernelGGL((k_local_place<KeyT, CK, HAS_VAL, 13>), dim3(local_place_grid(BINS << fc.bits2)), dim3((1 << 13) / 16),
-                         place_lds_bytes(13, WORD_BYTES), stream, kb_scratch, bufA, (const uint32_t*)nullptr, (uint32_t*)nullptr, desc_mask, plan, hist2,
-                         base2, todo, g_exp, 1);
+      GX_HIP_TRY(launch_lds(dev, (k_local_place<KeyT, CK, HAS_VAL, 13>), dim3(local_place_grid(BINS << fc.bits2)), dim3((1 << 13) / 16),
+                                 place_lds_bytes(13, WORD_BYTES), stream, kb_scratch, bufA, (const uint32_t*)nullptr, (uint32_t*)nullptr, desc_mask, plan, hist2,
+                                 base2, todo, g_exp, 1));
       // the cells k_local_place left: 64-bit words (32-bit keys are widened to their sortable form on the way in)
-      hipLaunchKernelGGL((k_local_sort<uint64_t, CK, HAS_VAL, 13, KeyT>), dim3(local_sort_grid(BINS << fc.bits2_max)), dim3((1 << 13) / 16),
-                         ((size_t)8 << 13) + (size_t)(((1 << 13) / 16 / GX_WAVE) * BINS + 32 + 2 * BINS) * 4, stream, (const KeyT*)kb_scratch, bufA,
-                         (const uint32_t*)nullptr, (uint32_t*)nullptr, (uint64_t)desc_mask, plan, hist2, base2, g_exp, 1, (const uint32_t*)todo);
+      GX_HIP_TRY(launch_lds(dev, (k_local_sort<uint64_t, CK, HAS_VAL, 13, KeyT>), dim3(local_sort_grid(BINS << fc.bits2_max)), dim3((1 << 13) / 16),
+                                 ((size_t)8 << 13) + (size_t)(((1 << 13) / 16 / GX_WAVE) * BINS + 32 + 2 * BINS) * 4, stream, (const KeyT*)kb_scratch, bufA,
+                                 (const uint32_t*)nullptr, (uint32_t*)nullptr, (uint64_t)desc_mask, plan, hist2, base2, g_exp, 1, (const uint32_t*)todo));
       prof_mark_h(4, stream);
       g_prof.hybrid_marked = g_prof.enabled;
       cursor_marked        = true;
@@ -3921,7 +3896,7 @@ int sort_impl(const void* keys_in, void* keys_out, const int32_t* vals_in, int32
       // cell has left it by now); the LSD passes below then sort X between the two halves of the level-0 buffer
       hipLaunchKernelGGL(k_big_plan, dim3(1), dim3(BINS), 0, stream, plan, (unsigned long long)(fc.slot_rows / 2));
       hipLaunchKernelGGL(k_big_cells, dim3(BINS), dim3(GX_WAVE), 0, stream, (const SortPlan*)plan, (const uint32_t*)hist2, xoff, biglist);
-      hipLaunchKernelGGL(kf2, dim3((unsigned)(ftiles + NRANGE * BINS)), dim3(BT), lds_hf(nbf), stream, slot0_buf, kb_scratch, desc_mask, plan, hist2, 1u << 13, n, bufA);
+      GX_HIP_TRY(launch_lds(dev, kf2, dim3((unsigned)(ftiles + NRANGE * BINS)), dim3(BT), lds_hf(nbf), stream, slot0_buf, kb_scratch, desc_mask, plan, hist2, 1u << 13, n, bufA));
       hipLaunchKernelGGL(k_hf_clear_status, dim3(2048), dim3(256), 0, stream, plan, reinterpret_cast<uint4*>(status), status_words / 2);
     }
   }
@@ -3944,22 +3919,6 @@ int sort_impl(const void* keys_in, void* keys_out, const int32_t* vals_in, int32
       MsdK kmsd1 = kmsd0;
       auto kloc  = k_local_sort<KeyT, KIND, HAS_VAL, 14>;
       int ls_bt  = (1 << 14) / 16;
-      static std::atomic<bool> hattr_set{false};
-      if (!hattr_set) {
-        const int lds_mmax = (int)lds_msd(16, BINS);
-        GX_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k_msd_pass<KeyT, KIND, HAS_VAL, 8, 4, 8>), hipFuncAttributeMaxDynamicSharedMemorySize, lds_mmax));
-        GX_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k_msd_pass<KeyT, KIND, HAS_VAL, 10, 4, 8>), hipFuncAttributeMaxDynamicSharedMemorySize, lds_mmax));
-        GX_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k_msd_pass<KeyT, KIND, HAS_VAL, 12, 4, 8>), hipFuncAttributeMaxDynamicSharedMemorySize, lds_mmax));
-        GX_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k_msd_pass<KeyT, KIND, HAS_VAL, 16, 4, 8>), hipFuncAttributeMaxDynamicSharedMemorySize, lds_mmax));
-        GX_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kloc), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_loc(14)));
-        if constexpr (SMALLOK) {
-          GX_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k_msd_pass<KeyT, KIND, HAS_VAL, SKPT, 4, 9>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_msd(SKPT, NB9)));
-          GX_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k_local_sort<KeyT, KIND, HAS_VAL, 13>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_loc(13)));
-          GX_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k_local_place<KeyT, KIND, HAS_VAL, 13>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)place_lds_bytes(13)));
-        }
-        GX_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k_local_place<KeyT, KIND, HAS_VAL, 14>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)place_lds_bytes(14)));
-        hattr_set = true;
-      }
       int kpt1 = hyb_kpt;
       if constexpr (SMALLOK) {
         if (hc.bits2 > 8) {
@@ -3967,14 +3926,6 @@ int sort_impl(const void* keys_in, void* keys_out, const int32_t* vals_in, int32
           kpt1  = SKPT;
         }
         if constexpr (!HAS_VAL) if (g_lbw != 4 && hyb_kpt == 16) {  // A/B knob: predecessors examined per look-back round
-          static std::atomic<bool> lattr_set{false};
-          if (!lattr_set) {
-            GX_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k_msd_pass<KeyT, KIND, HAS_VAL, 16, 8, 8>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_msd(16, BINS)));
-            GX_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k_msd_pass<KeyT, KIND, HAS_VAL, 16, 16, 8>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_msd(16, BINS)));
-            GX_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k_msd_pass<KeyT, KIND, HAS_VAL, 16, 8, 9>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_msd(16, NB9)));
-            GX_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k_msd_pass<KeyT, KIND, HAS_VAL, 16, 16, 9>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_msd(16, NB9)));
-            lattr_set = true;
-          }
           kmsd0 = g_lbw == 8 ? (MsdK)k_msd_pass<KeyT, KIND, HAS_VAL, 16, 8, 8> : (MsdK)k_msd_pass<KeyT, KIND, HAS_VAL, 16, 16, 8>;
           if (hc.bits2 > 8) kmsd1 = g_lbw == 8 ? (MsdK)k_msd_pass<KeyT, KIND, HAS_VAL, 16, 8, 9> : (MsdK)k_msd_pass<KeyT, KIND, HAS_VAL, 16, 16, 9>;
           else kmsd1 = kmsd0;
@@ -4017,14 +3968,14 @@ int sort_impl(const void* keys_in, void* keys_out, const int32_t* vals_in, int32
       m.spin_ticks  = (unsigned long long)g_spin_ms * 100000ull | (g_soft_fault ? SPIN_SOFT_BIT : 0ull);
       m.inject_tile = g_inject_tile;
       if (!cursor_marked) prof_mark_h(0, stream);
-      hipLaunchKernelGGL(kmsd0, dim3((unsigned)(msd_ntiles + NRANGE)), dim3(BT), lds_msd(hyb_kpt, BINS), stream, m);
+      GX_HIP_TRY(launch_lds(dev, kmsd0, dim3((unsigned)(msd_ntiles + NRANGE)), dim3(BT), lds_msd(hyb_kpt, BINS), stream, m));
       if (!cursor_marked) prof_mark_h(1, stream);
       m.in    = bufA;
       m.out   = bufB;
       m.vin   = valA;
       m.vout  = valB;
       m.level = 1;
-      hipLaunchKernelGGL(kmsd1, dim3((unsigned)(msd_ntiles + BINS + NRANGE)), dim3(BT), lds_msd(hyb_kpt, nb1), stream, m);
+      GX_HIP_TRY(launch_lds(dev, kmsd1, dim3((unsigned)(msd_ntiles + BINS + NRANGE)), dim3(BT), lds_msd(hyb_kpt, nb1), stream, m));
       if (!cursor_marked) prof_mark_h(2, stream);
       hipLaunchKernelGGL(k_plan2, dim3(BINS), dim3(GX_WAVE), 0, stream, plan, hist2, base2, NPASS, 0);
       if (!cursor_marked) prof_mark_h(3, stream);
@@ -4033,15 +3984,15 @@ int sort_impl(const void* keys_in, void* keys_out, const int32_t* vals_in, int32
       if constexpr (SMALLOK) {
         if (hc.cl2 == 13) kplace = k_local_place<KeyT, KIND, HAS_VAL, 13>;
       }
-      hipLaunchKernelGGL(kplace, dim3(local_place_grid(BINS << hc.bits2)), dim3(ls_bt), place_lds_bytes(hc.cl2), stream, (const KeyT*)bufB, bufA,
-                         (const uint32_t*)valB, valA, desc_mask, plan, hist2, base2, todo, m.exp, 0);
-      hipLaunchKernelGGL(kloc, dim3(local_sort_grid(BINS << hc.bits2)), dim3(ls_bt), lds_loc(hc.cl2), stream, bufB, bufA, valB, valA, desc_mask,
-                         plan, hist2, base2, m.exp, 0, (const uint32_t*)todo);
+      GX_HIP_TRY(launch_lds(dev, kplace, dim3(local_place_grid(BINS << hc.bits2)), dim3(ls_bt), place_lds_bytes(hc.cl2), stream, (const KeyT*)bufB, bufA,
+                                 (const uint32_t*)valB, valA, desc_mask, plan, hist2, base2, todo, m.exp, 0));
+      GX_HIP_TRY(launch_lds(dev, kloc, dim3(local_sort_grid(BINS << hc.bits2)), dim3(ls_bt), lds_loc(hc.cl2), stream, bufB, bufA, valB, valA, desc_mask,
+                                 plan, hist2, base2, m.exp, 0, (const uint32_t*)todo));
       if (hc.cl2_alt == 14) {  // the cell sort on 16384-key cells, should k_hy_plan have switched to them (no-ops otherwise)
-        hipLaunchKernelGGL((k_local_place<KeyT, KIND, HAS_VAL, 14>), dim3(local_place_grid(BINS << hc.bits2)), dim3((1 << 14) / 16), place_lds_bytes(14), stream,
-                           (const KeyT*)bufB, bufA, (const uint32_t*)valB, valA, desc_mask, plan, hist2, base2, todo, m.exp, 0);
-        hipLaunchKernelGGL((k_local_sort<KeyT, KIND, HAS_VAL, 14>), dim3(local_sort_grid(BINS << hc.bits2)), dim3((1 << 14) / 16), lds_loc(14), stream, bufB, bufA,
-                           valB, valA, desc_mask, plan, hist2, base2, m.exp, 0, (const uint32_t*)todo);
+        GX_HIP_TRY(launch_lds(dev, (k_local_place<KeyT, KIND, HAS_VAL, 14>), dim3(local_place_grid(BINS << hc.bits2)), dim3((1 << 14) / 16), place_lds_bytes(14), stream,
+                                   (const KeyT*)bufB, bufA, (const uint32_t*)valB, valA, desc_mask, plan, hist2, base2, todo, m.exp, 0));
+        GX_HIP_TRY(launch_lds(dev, (k_local_sort<KeyT, KIND, HAS_VAL, 14>), dim3(local_sort_grid(BINS << hc.bits2)), dim3((1 << 14) / 16), lds_loc(14), stream, bufB, bufA,
+                                   valB, valA, desc_mask, plan, hist2, base2, m.exp, 0, (const uint32_t*)todo));
       }
       if (!cursor_marked) prof_mark_h(4, stream);
       if (!cursor_marked) g_prof.hybrid_marked = g_prof.enabled;
@@ -4077,31 +4028,19 @@ int sort_impl(const void* keys_in, void* keys_out, const int32_t* vals_in, int32
   auto kern_lb         = (algo == 2) ? k_radix_pass<KeyT, KIND, HAS_VAL, KPT, 1>
                                        : (cells ? k_radix_pass<KeyT, KIND, HAS_VAL, KPT, 4, true> : k_radix_pass<KeyT, KIND, HAS_VAL, KPT, 4>);
   auto kern_pre        = k_radix_pass<KeyT, KIND, HAS_VAL, KPT, 0>;
-  static std::atomic<bool> attr_set{false};  // per template instantiation
-  if (!attr_set) {
-    GX_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k_radix_pass<KeyT, KIND, HAS_VAL, KPT, 4>),
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    GX_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k_radix_pass<KeyT, KIND, HAS_VAL, KPT, 1>),
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    GX_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k_radix_pass<KeyT, KIND, HAS_VAL, KPT, 4, true>),
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    GX_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern_pre),
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    attr_set = true;
-  }
   for (int pass = 0; pass < NPASS; ++pass) {
     a.pass = pass;
     prof_mark(2 + 2 * pass, stream);
     if (algo != 1) {
       const int64_t lb_grid = (cells && algo != 2) ? div_up(ntiles, PASS_TPB) : ntiles;
-      hipLaunchKernelGGL(kern_lb, dim3((unsigned)lb_grid), dim3(BT), lds, stream, a);
+      GX_HIP_TRY(launch_lds(dev, kern_lb, dim3((unsigned)lb_grid), dim3(BT), lds, stream, a));
     } else {
       hipLaunchKernelGGL((k_tile_hist<KeyT, KIND, KPT>), dim3((unsigned)ntiles), dim3(BT), 0, stream, a, tile_hist);
       scan::PlainLoader<uint32_t, uint32_t> ld{tile_hist, nullptr, 0u};
       int rc = scan::device_scan<uint32_t, uint32_t>(ld, ntiles * BINS, 0u, SumOp(), false, tile_hist, partials,
                                                      stream, &plan->pass_skip[pass]);
       if (rc) return rc;
-      hipLaunchKernelGGL(kern_pre, dim3((unsigned)ntiles), dim3(BT), lds, stream, a);
+      GX_HIP_TRY(launch_lds(dev, kern_pre, dim3((unsigned)ntiles), dim3(BT), lds, stream, a));
     }
     prof_mark(3 + 2 * pass, stream);
   }
@@ -4287,11 +4226,8 @@ int sortx_level0(const void* keys, int64_t n, int64_t recv_rows_max, const unsig
   int64_t sblocks       = div_up(div_up(n, step), (int64_t)4 * 4);
   if (sblocks > 2048) sblocks = 2048;
   const size_t lds0 = (size_t)FT * sizeof(KeyT) + (size_t)(3 * 256 + 16 + 4) * 4 + (size_t)2 * NW * 8;
-  static std::atomic<bool> attr_set{false};  // per instantiation
-  if (!attr_set) {
-    GX_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k_hf_scatter<KeyT, KIND, 0, 8>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds0));
-    attr_set = true;
-  }
+  Device dev;
+  GX_HIP_TRY(device(&dev));
   // the masks of all ranks replace the sample's; forced_masks tells the verdict after level 0 not to compare the local top bit
   GX_HIP_TRY(hipMemcpyAsync(&L.plan->hy.or_mask, masks2_host, 2 * sizeof(unsigned long long), hipMemcpyHostToDevice, stream));
   const uint32_t one = 1;
@@ -4305,7 +4241,7 @@ int sortx_level0(const void* keys, int64_t n, int64_t recv_rows_max, const unsig
   hipLaunchKernelGGL((k_hf_sample<KeyT, KIND, true>), dim3((unsigned)sblocks), dim3(256), 0, stream, kin, n, KeyT(0), L.plan, cs.stride, frange);
   hipLaunchKernelGGL(k_hf_plan, dim3(1), dim3(BINS), 0, stream, L.plan, 1, (int)(8 * sizeof(KeyT)), n, bits2_hint, 1 << 13, cs.stride, frange, FT,
                      (unsigned long long)cs.slot_rows, 8.0f, MIN_SHIFT2, bits2_hint);
-  hipLaunchKernelGGL((k_hf_scatter<KeyT, KIND, 0, 8>), dim3((unsigned)ftiles), dim3(BT), lds0, stream, kin, L.level0, KeyT(0), L.plan, L.hist2, 1u << 13, n, (KeyT*)nullptr);
+  GX_HIP_TRY(launch_lds(dev, (k_hf_scatter<KeyT, KIND, 0, 8>), dim3((unsigned)ftiles), dim3(BT), lds0, stream, kin, L.level0, KeyT(0), L.plan, L.hist2, 1u << 13, n, (KeyT*)nullptr));
   hipLaunchKernelGGL(k_hf_plan, dim3(1), dim3(BINS), 0, stream, L.plan, 2, (int)(8 * sizeof(KeyT)), n, bits2_hint, 1 << 13, cs.stride, frange, FT,
                      (unsigned long long)cs.slot_rows, 8.0f, MIN_SHIFT2, bits2_hint);
   GX_LAUNCH_CHECK();
@@ -4347,37 +4283,25 @@ int sortx_finish(int64_t n_send, int64_t recv_rows_max, int64_t n, const unsigne
   const size_t lds_ls = ((size_t)8 << 13) + (size_t)(((1 << 13) / 16 / GX_WAVE) * BINS + 32 + 2 * BINS) * 4;
   constexpr int KPT_L = kpt_for<KeyT>(false);
   constexpr size_t lds_pass = pass_lds_bytes<KeyT, false, KPT_L>();
-  static std::atomic<bool> attr_set{false};  // per instantiation
-  if (!attr_set) {
-    GX_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k_hf_scatter<KeyT, KIND, 1, 8>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_hf(256)));
-    GX_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k_hf_scatter<KeyT, KIND, 1, 9>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_hf(512)));
-    GX_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k_hf_scatter<KeyT, KIND, 1, 10>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_hf(1024)));
-    GX_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k_hf_scatter<KeyT, KIND, 2, 8>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_hf(256)));
-    GX_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k_hf_scatter<KeyT, KIND, 2, 9>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_hf(512)));
-    GX_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k_hf_scatter<KeyT, KIND, 2, 10>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_hf(1024)));
-    GX_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k_local_sort<uint64_t, KIND, false, 13, KeyT>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_ls));
-    GX_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k_local_place<KeyT, KIND, false, 13>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                   (int)place_lds_bytes(13, WORD_BYTES)));
-    GX_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k_radix_pass<KeyT, KIND, false, KPT_L, 4, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_pass));
-    attr_set = true;
-  }
+  Device dev;
+  GX_HIP_TRY(device(&dev));
   // tiles of the regions: one per FT keys + one tail per region
   const int64_t l1_grid = div_up(n, (int64_t)FT) + nreg;
   KeyT* bufA = static_cast<KeyT*>(out);
   hipLaunchKernelGGL(k_hfx_plan, dim3(1), dim3(BINS), 0, stream, L.plan, (long long)n, cr.bits2, cr.bits2_max, 1 << 13, MIN_SHIFT2, FT, masks2_host[0], masks2_host[1],
                      (uint32_t)nreg, (const uint32_t*)L.breg0, L.x_tile0, (const uint32_t*)L.x_start, (const uint32_t*)L.x_count, (const uint32_t*)L.x_bucket,
                      (unsigned long long)L.cells_rows);
-  hipLaunchKernelGGL(kf1, dim3((unsigned)l1_grid), dim3(BT), lds_hf(nbf), stream, (const KeyT*)L.level0, L.cells, KeyT(0), L.plan, L.hist2, 1u << 13, n, (KeyT*)nullptr);
+  GX_HIP_TRY(launch_lds(dev, kf1, dim3((unsigned)l1_grid), dim3(BT), lds_hf(nbf), stream, (const KeyT*)L.level0, L.cells, KeyT(0), L.plan, L.hist2, 1u << 13, n, (KeyT*)nullptr));
   hipLaunchKernelGGL(k_plan2, dim3(BINS), dim3(GX_WAVE), 0, stream, L.plan, L.hist2, L.base2, (int)sizeof(KeyT), 1);
-  hipLaunchKernelGGL((k_local_place<KeyT, KIND, false, 13>), dim3(local_place_grid(BINS << cr.bits2)), dim3((1 << 13) / 16), place_lds_bytes(13, WORD_BYTES), stream,
-                     (const KeyT*)L.cells, bufA, (const uint32_t*)nullptr, (uint32_t*)nullptr, KeyT(0), L.plan, L.hist2, L.base2, L.todo, 0, 1);
-  hipLaunchKernelGGL((k_local_sort<uint64_t, KIND, false, 13, KeyT>), dim3(local_sort_grid(BINS << cr.bits2_max)), dim3((1 << 13) / 16), lds_ls, stream,
-                     (const KeyT*)L.cells, bufA, (const uint32_t*)nullptr, (uint32_t*)nullptr, (uint64_t)0, L.plan, L.hist2, L.base2, 0, 1, (const uint32_t*)L.todo);
+  GX_HIP_TRY(launch_lds(dev, (k_local_place<KeyT, KIND, false, 13>), dim3(local_place_grid(BINS << cr.bits2)), dim3((1 << 13) / 16), place_lds_bytes(13, WORD_BYTES), stream,
+                             (const KeyT*)L.cells, bufA, (const uint32_t*)nullptr, (uint32_t*)nullptr, KeyT(0), L.plan, L.hist2, L.base2, L.todo, 0, 1));
+  GX_HIP_TRY(launch_lds(dev, (k_local_sort<uint64_t, KIND, false, 13, KeyT>), dim3(local_sort_grid(BINS << cr.bits2_max)), dim3((1 << 13) / 16), lds_ls, stream,
+                             (const KeyT*)L.cells, bufA, (const uint32_t*)nullptr, (uint32_t*)nullptr, (uint64_t)0, L.plan, L.hist2, L.base2, 0, 1, (const uint32_t*)L.todo));
   // big cells: X in the cell buffer, the LSD passes between the two halves of the level-0 area (every region has been read by then)
   const size_t xcap = L.level0_rows / 2;
   hipLaunchKernelGGL(k_big_plan, dim3(1), dim3(BINS), 0, stream, L.plan, (unsigned long long)xcap);
   hipLaunchKernelGGL(k_big_cells, dim3(BINS), dim3(GX_WAVE), 0, stream, (const SortPlan*)L.plan, (const uint32_t*)L.hist2, L.xoff, L.biglist);
-  hipLaunchKernelGGL(kf2, dim3((unsigned)l1_grid), dim3(BT), lds_hf(nbf), stream, (const KeyT*)L.level0, L.cells, KeyT(0), L.plan, L.hist2, 1u << 13, n, (KeyT*)nullptr);
+  GX_HIP_TRY(launch_lds(dev, kf2, dim3((unsigned)l1_grid), dim3(BT), lds_hf(nbf), stream, (const KeyT*)L.level0, L.cells, KeyT(0), L.plan, L.hist2, 1u << 13, n, (KeyT*)nullptr));
   hipLaunchKernelGGL(k_hf_clear_status, dim3(2048), dim3(256), 0, stream, L.plan, reinterpret_cast<uint4*>(L.status), L.status_words / 2);
   int64_t hblocks = div_up(n, (int64_t)BT * 8);
   if (hblocks > 2048) hblocks = 2048;
@@ -4399,7 +4323,7 @@ int sortx_finish(int64_t n_send, int64_t recv_rows_max, int64_t n, const unsigne
   const int64_t xtiles = div_up((int64_t)(n < (int64_t)xcap ? n : (int64_t)xcap), (int64_t)(BT * KPT_L));
   for (int pass = 0; pass < (int)sizeof(KeyT); ++pass) {
     a.pass = pass;
-    hipLaunchKernelGGL((k_radix_pass<KeyT, KIND, false, KPT_L, 4, true>), dim3((unsigned)div_up(xtiles, (int64_t)PASS_TPB)), dim3(BT), lds_pass, stream, a);
+    GX_HIP_TRY(launch_lds(dev, (k_radix_pass<KeyT, KIND, false, KPT_L, 4, true>), dim3((unsigned)div_up(xtiles, (int64_t)PASS_TPB)), dim3(BT), lds_pass, stream, a));
   }
   hipLaunchKernelGGL((k_finalize_copy<KeyT, false>), dim3(1024), dim3(256), 0, stream, a);
   hipLaunchKernelGGL((k_big_distribute<KeyT>), dim3(2048), dim3(256), 0, stream, (const SortPlan*)L.plan, (const KeyT*)L.level0, bufA, (const uint32_t*)L.biglist,

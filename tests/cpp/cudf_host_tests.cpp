@@ -14,10 +14,14 @@
 #include <cudf/table/table_view.hpp>
 #include <cudf/types.hpp>
 
+#include "../../cudf_amd/csrc/gx_lds_book.hpp"  // plain C++: the bookkeeping behind gx::launch_lds (no HIP include)
+
+#include <atomic>
 #include <cstdio>
 #include <functional>
 #include <stdexcept>
 #include <string>
+#include <thread>
 #include <vector>
 
 using namespace cudf;
@@ -65,6 +69,63 @@ int main()
     CHECK(is_floating_point(data_type{type_id::FLOAT64}) && !is_floating_point(data_type{type_id::INT32}));
     CHECK(type_to_id<int32_t>() == type_id::INT32 && type_to_id<double>() == type_id::FLOAT64);
     CHECK(JoinNoMatch == std::numeric_limits<size_type>::min());
+  });
+  run("launch layer: the dynamic-LDS limit is recorded per (kernel, device) (csrc/gx_lds_book.hpp)", [] {
+    static gx::LdsBook book;  // (static: the table is too large for the stack)
+    int ka = 0, kb = 0;       // two "kernels": only their addresses matter
+    struct Call { const void* k; int bytes; };
+    std::vector<Call> calls;
+    int fail_with = 0;
+    auto set = [&](const void* k, int bytes) {
+      if (fail_with) return fail_with;
+      calls.push_back({k, bytes});
+      return 0;
+    };
+    CHECK(book.ensure(&ka, 0, 100, set) == 0 && calls.size() == 1 && calls[0].k == &ka && calls[0].bytes == 100);  // first request: one set
+    CHECK(book.ensure(&ka, 0, 100, set) == 0 && book.ensure(&ka, 0, 40, set) == 0 && calls.size() == 1);           // same / smaller: none
+    CHECK(book.ensure(&ka, 0, 0, set) == 0 && calls.size() == 1);
+    CHECK(book.ensure(&ka, 0, 131072, set) == 0 && calls.size() == 2 && calls[1].k == &ka && calls[1].bytes == 131072);  // larger: one set, larger value
+    CHECK(book.ensure(&ka, 0, 100, set) == 0 && calls.size() == 2);
+    CHECK(book.ensure(&ka, 1, 100, set) == 0 && calls.size() == 3 && calls[2].k == &ka && calls[2].bytes == 100);  // another device: its own record
+    CHECK(book.ensure(&ka, 1, 100, set) == 0 && calls.size() == 3);
+    CHECK(book.ensure(&kb, 0, 64, set) == 0 && calls.size() == 4 && calls[3].k == &kb && calls[3].bytes == 64);    // the kernels are independent
+    CHECK(book.ensure(&kb, 1, 64, set) == 0 && calls.size() == 5);
+    CHECK(book.ensure(&ka, 0, 131072, set) == 0 && book.ensure(&ka, 1, 100, set) == 0 && calls.size() == 5);
+    // a failing setter: its error comes back and the record stays, so the retry sets again
+    fail_with = 719;
+    CHECK(book.ensure(&kb, 0, 4096, set) == 719 && book.ensure(&kb, 0, 4096, set) == 719 && calls.size() == 5);
+    CHECK(book.ensure(&kb, 0, 64, set) == 0);  // what was set before the failure still counts
+    fail_with = 0;
+    CHECK(book.ensure(&kb, 0, 4096, set) == 0 && calls.size() == 6 && calls[5].k == &kb && calls[5].bytes == 4096);
+    CHECK(book.ensure(&kb, 0, 4096, set) == 0 && calls.size() == 6);
+    // a device id the book has no room for is set on every launch (never skipped)
+    CHECK(book.ensure(&kb, gx::LDS_BOOK_DEVICES, 8, set) == 0 && book.ensure(&kb, gx::LDS_BOOK_DEVICES, 8, set) == 0 && calls.size() == 8);
+    CHECK(book.ensure(&kb, -1, 8, set) == 0 && calls.size() == 9);
+    // 8 threads make the first launches of one (kernel, device): nobody "launches" before the limit covers its request
+    // (sets may be repeated; they must never be missing and never lower the limit)
+    for (int device = 0; device < 2; ++device) {
+      int kc = 0;
+      std::atomic<int> limit{0}, sets{0}, early{0}, lowered{0};
+      auto set_mt = [&](const void*, int bytes) {
+        if (bytes < limit.load()) ++lowered;
+        std::this_thread::yield();  // widen the window between "set asked for" and "set done"
+        limit.store(bytes);
+        ++sets;
+        return 0;
+      };
+      std::vector<std::thread> pool;
+      for (int t = 0; t < 8; ++t)
+        pool.emplace_back([&, t] {
+          for (int i = 0; i < 2000; ++i) {
+            const int bytes = 1024 * (1 + (i / 250)) + 16 * (t & 1);  // grows as the run goes on; two sizes in flight at a time
+            if (book.ensure(&kc, device, bytes, set_mt) != 0 || limit.load() < bytes) ++early;
+          }
+        });
+      for (auto& th : pool) th.join();
+      CHECK(early == 0 && lowered == 0);
+      CHECK(sets >= 8 && sets <= 16);  // 8 steps, each reached by the even or the odd size first
+      CHECK(limit == 1024 * 8 + 16);
+    }
   });
   run("column_view / table_view constructor checks (column_view.cpp:101-132, table_view.cpp)", [&] {
     column_view ok{data_type{type_id::INT32}, 5, fake, fake_mask, 2, 1};
