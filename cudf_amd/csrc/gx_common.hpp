@@ -260,6 +260,23 @@ __device__ __forceinline__ uint32_t lds_rank(uint32_t* counters, uint32_t d, boo
   return live ? atomicAdd(&counters[d], 1u) : 0u;
 }
 
+// lds_rank for a caller that only wants the COUNTS: the same grouping, but no atomic returns a value, so nothing waits for
+// the LDS before the next chunk's keys are looked at.
+__device__ __forceinline__ void lds_count(uint32_t* counters, uint32_t d, bool live)
+{
+  const uint64_t act = ballot(live);
+  if (act == 0) return;
+  const int leader    = __builtin_ctzll(act);
+  const uint32_t dl   = shfl(d, leader);
+  const uint64_t same = ballot(live && d == dl);
+  if (same == act || __builtin_popcountll(same) >= 8) {
+    if ((int)lane_id() == leader) atomicAdd(&counters[dl], (uint32_t)__builtin_popcountll(same));
+    if (live && d != dl) atomicAdd(&counters[d], 1u);
+    return;
+  }
+  if (live) atomicAdd(&counters[d], 1u);
+}
+
 struct SumOp {
   template <typename T>
   __device__ __forceinline__ T operator()(T a, T b) const { return a + b; }

@@ -1105,8 +1105,9 @@ struct MsdArgs {
 // no s_waitcnt in between).  4.81 / 5.44 ms per pass against 4.2 / 4.7: words read that early are mostly not
 // published yet, so the window is read twice, and the eight extra registers do not come for free
 // (profiles/r2_run20_bench_sort_lookback_prefetch.jsonl).)
+// msd_pass_tile: ONE ticket -- take it, partition the tile; false when the pass does not run or no ticket is left.
 template <typename KeyT, int KIND, bool HAS_VAL, int KPT, int LBW, int NBL>
-__global__ void __launch_bounds__(BT, (KPT <= 8 ? 8 : (KPT <= 12 ? 6 : 4))) k_msd_pass(MsdArgs a)
+__device__ __forceinline__ bool msd_pass_tile(const MsdArgs& a)
 {
   constexpr int TILE = BT * KPT;
   constexpr int NB   = 1 << NBL;  // bins of this pass: 256 (level 0, level 1 up to 8 bits) or 512 (9-bit level 1)
@@ -1136,7 +1137,7 @@ __global__ void __launch_bounds__(BT, (KPT <= 8 ? 8 : (KPT <= 12 ? 6 : 4))) k_ms
   SortPlan* plan = a.plan;
   HybridPlan& hy = plan->hy;
   const int lvl  = a.level;
-  if (!hy.attempt || plan->hf.state == 3) return;
+  if (!hy.attempt || plan->hf.state == 3) return false;
   const KeyT* kin      = static_cast<const KeyT*>(a.in);
   KeyT* kout           = static_cast<KeyT*>(a.out);
   const uint32_t* vin  = a.vin;
@@ -1180,7 +1181,7 @@ __global__ void __launch_bounds__(BT, (KPT <= 8 ? 8 : (KPT <= 12 ? 6 : 4))) k_ms
   }
   __syncthreads();
   const uint32_t gtile = s_misc[0];
-  if (gtile == 0xFFFFFFFFu) return;
+  if (gtile == 0xFFFFFFFFu) return false;
   const uint32_t seg   = s_misc[1];
   const uint32_t jt    = s_misc[2];
   const int64_t base   = (int64_t)hy.seg_start[lvl][seg] + (int64_t)jt * TILE;
@@ -1350,6 +1351,20 @@ __global__ void __launch_bounds__(BT, (KPT <= 8 ? 8 : (KPT <= 12 ? 6 : 4))) k_ms
         if (HAS_VAL) vout[dst] = s_vals[i];
       }
     }
+  }
+  return true;
+}
+
+// One ticket per workgroup; MULTI, the form of a launch in the fallback role (role_grid): a workgroup that has finished its tile takes
+// the next ticket, until none is left.  Tickets are still handed out in order and only to running workgroups, and a workgroup holds
+// one at a time, so every predecessor a tile waits for is owned by a workgroup that is running and waits for earlier tiles only.
+template <typename KeyT, int KIND, bool HAS_VAL, int KPT, int LBW, int NBL, bool MULTI = false>
+__global__ void __launch_bounds__(BT, (KPT <= 8 ? 8 : (KPT <= 12 ? 6 : 4))) k_msd_pass(MsdArgs a)
+{
+  if constexpr (MULTI) {
+    while (msd_pass_tile<KeyT, KIND, HAS_VAL, KPT, LBW, NBL>(a)) __syncthreads();  // (the next tile reuses the LDS)
+  } else {
+    msd_pass_tile<KeyT, KIND, HAS_VAL, KPT, LBW, NBL>(a);
   }
 }
 
@@ -2076,16 +2091,23 @@ __global__ void __launch_bounds__((1 << CL2) / 16, 4) k_local_sort(const IoT* in
 //                       and skipped on success) sorts the column from scratch: no host round trip on either branch
 //   k_hf_scatter<1>     level 1: the (bucket, range) regions -> padded cell slots, cursor = the cell's size
 //   k_plan2, k_local_sort as on the look-back path.
-// HBM traffic 16 + 16 + 16 = 48 B/row (+ 2 x 8/stride for the sample) against 56 with the histogram read.  A 10-bit
-// level 1 (two bins per thread) keeps 8192-key cells up to 2^31 rows: the slow window of round 2, n in (1.02e9, 2.1e9],
-// where the 9-bit pass forced 16384-key cells at half occupancy, is gone for these keys.
+// The sample reads 512 B of every stride * 512 B: at 1e9 rows 250 MB in 147.6 us (1.7 TB/s).  The access pattern is not why: a bare
+// kernel that reads the same chunks and nothing else takes 41 us (scripts/xp/xp_strided_read.hip, 6.1 TB/s).  Nor is it the 64-bit
+// division per key (the range of a row), the returning LDS atomic per key or the 4.2 M flush atomics of the round-robin chunk
+// order: without them (lds_count, contiguous runs per workgroup, 16 chunks in flight per wave instead of 8) the kernel takes
+// 137.2 us on the same box (profiles/sort_launch_chain_vs_parent.txt).  Where the remaining ~95 us go is open.
 // ------------------------------------------------------------------------------------------------------------------
 constexpr int HF_CHUNK = GX_WAVE;  // keys per sample chunk: one 512-byte wave load
 
 template <typename KeyT, int KIND, bool HIST>
 __global__ void __launch_bounds__(256) k_hf_sample(const KeyT* __restrict__ in, int64_t n, KeyT desc_mask, SortPlan* plan, int stride,
-                                                   int64_t range_rows)
+                                                   int64_t range_rows, uint4* __restrict__ zero = nullptr, size_t zero16 = 0)
 {
+  // zero (HIST = false, the first kernel of a sort): the cell tables, cleared here instead of by a memset of their own
+  if (!HIST && zero != nullptr) {
+    const size_t zs = (size_t)gridDim.x * 256;
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < zero16; i += zs) zero[i] = uint4{0u, 0u, 0u, 0u};
+  }
   HybridPlan& hy = plan->hy;
   FastPlan& hf   = plan->hf;
   // HIST = false: the masks AND a speculative histogram of the TOP byte (the level-0 digit of any column whose top bit
@@ -2099,20 +2121,31 @@ __global__ void __launch_bounds__(256) k_hf_sample(const KeyT* __restrict__ in, 
   const Digit0 dig      = HIST ? digit0_of(hy, (int)(8 * sizeof(KeyT))) : Digit0{(int)(8 * sizeof(KeyT) - 8), 0, 0xFFu, 0u};
   const int64_t step    = (int64_t)stride * HF_CHUNK;
   const int64_t nchunks = div_up(n, step);
-  const int64_t nw      = (int64_t)gridDim.x * 4;
-  constexpr int U       = 8;  // chunks in flight per wave
+  // A workgroup reads a CONTIGUOUS run of the sampled chunks, its four waves interleaved: the run lies in one input range (two at
+  // a seam), so the flush below sends 256 (512) counters to memory.  With the chunks dealt out round-robin over the whole grid every
+  // workgroup saw every range and flushed all 2048 counters: 4.2 M atomics on 2048 words.
+  const int64_t per     = div_up(nchunks, (int64_t)gridDim.x);
+  const int64_t c_lo    = (int64_t)blockIdx.x * per;
+  const int64_t c_hi    = c_lo + per < nchunks ? c_lo + per : nchunks;
+  constexpr int64_t nw  = 4;   // waves of the workgroup
+  constexpr int U       = 16;  // chunks in flight per wave
+  // first row of input range k (ranges past the last one never start): the range of a row is the number of starts at or below it,
+  // that is min(row / range_rows, NRANGE - 1) without the 64-bit division per key
+  int64_t rstart[NRANGE - 1];  // rstart[k - 1]: first row of range k, k = 1 .. NRANGE - 1
+#pragma unroll
+  for (int k = 1; k < NRANGE; ++k) rstart[k - 1] = range_rows > 0 ? (int64_t)k * range_rows : (int64_t)0;
   KeyT vor = 0, vnor = 0, vfold = 0;
-  for (int64_t c0 = (int64_t)blockIdx.x * 4 + tid / GX_WAVE; c0 < nchunks; c0 += nw * U) {
+  for (int64_t c0 = c_lo + tid / GX_WAVE; c0 < c_hi; c0 += nw * U) {
     KeyT raw[U];
 #pragma unroll
     for (int u = 0; u < U; ++u) {
       const int64_t row = (c0 + u * nw) * step + lane;
-      raw[u]            = (c0 + u * nw < nchunks && row < n) ? in[row] : KeyT(0);
+      raw[u]            = (c0 + u * nw < c_hi && row < n) ? in[row] : KeyT(0);
     }
 #pragma unroll
     for (int u = 0; u < U; ++u) {
       const int64_t row = (c0 + u * nw) * step + lane;
-      const bool live   = c0 + u * nw < nchunks && row < n;
+      const bool live   = c0 + u * nw < c_hi && row < n;
       const KeyT k      = to_sortable<KeyT, KIND>(raw[u], desc_mask);
       if (!HIST && live) {
         if constexpr (KIND == K_FTOTAL) {
@@ -2122,10 +2155,10 @@ __global__ void __launch_bounds__(256) k_hf_sample(const KeyT* __restrict__ in, 
         vnor |= (KeyT)~k;
         if (KIND == K_SIGNED) vfold |= (KeyT)(raw[u] ^ (KeyT)(KeyT(0) - (KeyT)(raw[u] >> (8 * sizeof(KeyT) - 1))));
       }
-      // a chunk never straddles two ranges (ranges are whole tiles, chunks start at multiples of 64)
-      const int64_t r64 = range_rows > 0 ? row / range_rows : (int64_t)(NRANGE - 1);
-      const int r       = r64 < NRANGE - 1 ? (int)r64 : NRANGE - 1;
-      (void)lds_rank(s_hist + r * BINS, dig(k), live);
+      int r = 0;
+#pragma unroll
+      for (int q = 1; q < NRANGE; ++q) r += row >= rstart[q - 1] ? 1 : 0;
+      lds_count(s_hist + r * BINS, dig(k), live);  // (counts only: no atomic returns a value)
     }
   }
   if (!HIST) {
@@ -3149,9 +3182,11 @@ constexpr int hf_kpt()
 
 // LVL 2 (round 4) = the RESCUE pass of the big cells: level 1 once more over the level-0 buckets that hold a big cell, but
 // only the keys of big cells are written -- compacted into X at xoff[cell] (k_big_plan), cursors in `cellcur` + 2 * BINS * NB2MAX.
+// One tile of k_hf_scatter: tile `vblock` of `nblocks` (levels 0 and 1: the workgroup's index and the grid; the rescue pass walks
+// its tiles).  Every thread of the workgroup calls it with the same tile; returns are block-uniform.
 template <typename KeyT, int KIND, int LVL, int NBL>
-__global__ void __launch_bounds__(BT, 4) k_hf_scatter(const KeyT* __restrict__ in, KeyT* __restrict__ out, KeyT desc_mask, SortPlan* plan,
-                                                     uint32_t* __restrict__ cellcur, uint32_t cellcap, int64_t n, KeyT* __restrict__ fin = nullptr)
+__device__ __forceinline__ void hf_scatter_tile(const KeyT* __restrict__ in, KeyT* __restrict__ out, KeyT desc_mask, SortPlan* plan,
+                                                uint32_t* __restrict__ cellcur, int64_t n, KeyT* __restrict__ fin, int64_t vblock, int64_t nblocks)
 {
   // fin (level 1, splitter mode): the sort's final output -- the keys of an EQUALITY bucket are copied straight to their place
   constexpr int KPT = hf_kpt<KeyT>(), TILE = BT * KPT, NB = 1 << NBL, BPT = NB > BT ? NB / BT : 1;
@@ -3173,12 +3208,12 @@ __global__ void __launch_bounds__(BT, 4) k_hf_scatter(const KeyT* __restrict__ i
   const uint32_t* xoff = cellcur + 2 * BINS * NB2MAX;  // LVL 2: first key of a big cell in X ...
   uint32_t* rescur     = cellcur + 3 * BINS * NB2MAX;  // ... and the rescue cursors (hist2 | base2 | xoff | rescur)
   const unsigned tid = threadIdx.x;
-  const int64_t v    = xcd_swizzle((int64_t)blockIdx.x, (int64_t)gridDim.x);  // XCD x works on a contiguous eighth of the tiles
+  const int64_t v    = xcd_swizzle(vblock, nblocks);  // XCD x works on a contiguous eighth of the tiles
   int64_t base;
   int nvalid;
   uint32_t seg;
   if (LVL == 0) {
-    const int64_t per = (int64_t)gridDim.x / NRANGE;  // whole tiles per range (the last range takes the rest)
+    const int64_t per = nblocks / NRANGE;  // whole tiles per range (the last range takes the rest)
     seg               = (per > 0 && v / per < NRANGE - 1) ? (uint32_t)(v / per) : (uint32_t)(NRANGE - 1);
     base              = v * TILE;
     nvalid            = (int)(n - base < (int64_t)TILE ? n - base : (int64_t)TILE);
@@ -3196,8 +3231,12 @@ __global__ void __launch_bounds__(BT, 4) k_hf_scatter(const KeyT* __restrict__ i
       }
     }
     __syncthreads();
-    const uint32_t q  = s_misc[0];
-    const uint32_t jt = s_misc[1];
+    uint32_t q  = s_misc[0];
+    uint32_t jt = s_misc[1];
+    if constexpr (LVL == 2) {  // (the walk: block-uniform by construction, said so -- the returns below are then scalar branches to the next tile)
+      q  = (uint32_t)__builtin_amdgcn_readfirstlane((int)q);
+      jt = (uint32_t)__builtin_amdgcn_readfirstlane((int)jt);
+    }
     seg               = q / NRANGE;  // the level-0 bucket
     if (LVL == 2 && !hy.bigbucket[seg]) return;  // (block-uniform: nothing of this bucket is needed again)
     base              = (int64_t)hf.reg_start[q] + (int64_t)jt * TILE;
@@ -3216,8 +3255,12 @@ __global__ void __launch_bounds__(BT, 4) k_hf_scatter(const KeyT* __restrict__ i
       }
     }
     __syncthreads();
-    const uint32_t q  = s_misc[0];
-    const uint32_t jt = s_misc[1];
+    uint32_t q  = s_misc[0];
+    uint32_t jt = s_misc[1];
+    if constexpr (LVL == 2) {
+      q  = (uint32_t)__builtin_amdgcn_readfirstlane((int)q);
+      jt = (uint32_t)__builtin_amdgcn_readfirstlane((int)jt);
+    }
     seg               = hf.x_bucket[q];  // the level-0 bucket
     if (LVL == 2 && !hy.bigbucket[seg]) return;  // (block-uniform: nothing of this bucket is needed again)
     base              = (int64_t)hf.x_start[q] + (int64_t)jt * TILE;
@@ -3431,6 +3474,28 @@ __global__ void __launch_bounds__(BT, 4) k_hf_scatter(const KeyT* __restrict__ i
     }
   };
   if (split) write_all(spdig); else write_all(dig);
+}
+
+// Levels 0 and 1: one tile per workgroup, the tile from blockIdx.  LVL 2, the rescue pass, is enqueued behind every cursor-path
+// sort and does nothing unless a cell outgrew its slot (launch_grid, fallback role): a bounded grid walks the `ntiles` tiles.
+// (the walk is compiled to the 128 registers of four waves per SIMD with 3 - 14 dwords of scratch, as k_radix_pass's MULTI form is.  Built
+// for two waves per SIMD instead -- 139 registers, no scratch, but ONE workgroup per CU where the LDS admits two -- a rescue pass that
+// runs was slower: Zipf-like keys 14.84 -> 15.10 ms per 1e9 rows (section 3 of profiles/sort_launch_chain_vs_parent.txt) against
+// 15.07 -> 14.97 with this form (section 1b).)
+template <typename KeyT, int KIND, int LVL, int NBL>
+__global__ void __launch_bounds__(BT, 4) k_hf_scatter(const KeyT* __restrict__ in, KeyT* __restrict__ out, KeyT desc_mask, SortPlan* plan,
+                                                     uint32_t* __restrict__ cellcur, uint32_t cellcap, int64_t n, KeyT* __restrict__ fin = nullptr,
+                                                     uint32_t ntiles = 0)
+{
+  if constexpr (LVL == 2) {
+    if (plan->hf.state != 3 || !(plan->hy.ok && plan->hy.lsd_mode)) return;
+    for (uint32_t t = blockIdx.x; t < ntiles; t += gridDim.x) {
+      hf_scatter_tile<KeyT, KIND, LVL, NBL>(in, out, desc_mask, plan, cellcur, n, fin, (int64_t)t, (int64_t)ntiles);
+      __syncthreads();  // the next tile reuses the LDS
+    }
+  } else {
+    hf_scatter_tile<KeyT, KIND, LVL, NBL>(in, out, desc_mask, plan, cellcur, n, fin, (int64_t)blockIdx.x, (int64_t)gridDim.x);
+  }
 }
 
 // ---- level 0 in SPLITTER mode (64-bit keys): k_hf_scatter<.., 0, 8> with bucket = sp_bucket(key) in place of the bit digit.
@@ -3662,6 +3727,26 @@ static thread_local int g_cell = 0;  // A/B knob: 0 = auto, 8192 / 16384 = force
 static inline unsigned local_sort_grid(int cells) { return (unsigned)(cells < 4096 ? cells : 4096); }
 static thread_local int g_place_grid = 0;  // A/B knob: workgroups of k_local_place; 0 = one per cell
 static inline unsigned local_place_grid(int cells) { return (unsigned)((g_place_grid > 0 && g_place_grid < cells) ? g_place_grid : cells); }
+// Launch ROLE.  The host knows when a launch is enqueued as a fallback -- behind a cursor-path sort of
+// INTEGER keys: the look-back chain, the LSD passes, the rescue pass -- though not whether the fallback will run.  A primary
+// launch keeps its grid.  A fallback launch of a kernel that walks its tiles / cells with gridDim.x as stride gets at most
+// FALLBACK_WGS_PER_CU workgroups per CU (4096 on 256 CUs: a launch of that size that returns at once costs the 5 us of any
+// empty launch): finding nothing to do costs microseconds instead of a dispatch per tile, and a fallback that does run is
+// the kernel's persistent form.  k_msd_pass and k_radix_pass hand tiles out by ticket: their MULTI forms take the next
+// ticket when a tile is done.
+// float64 keys: a column with a NaN or a -0.0 is declined by the cursor path on the device and the look-back chain is the
+// ONLY path that sorts it, so for float keys the chain stays in the primary role, launched as without the cursor path.
+// k_sp_level0's two forms are ALTERNATIVES of level 0, not fallbacks, and keep one tile per workgroup: eight tiles per
+// workgroup compile to 128 registers + 64 - 116 B of scratch where one tile takes 96, in the hot kernel of every uneven column.
+// Measured at 1e9 int64 keys, builds alternating (profiles/sort_launch_chain_vs_parent.txt): headline 11.18 -> 10.96 ms; the
+// forced fallback 17.65 -> 18.33 ms, 0.59 ms of it in the two MULTI partition passes (4.26 -> 4.35, 4.56 -> 5.00 ms).
+enum class Role { primary, fallback };
+constexpr int FALLBACK_WGS_PER_CU = 16;
+static inline unsigned role_grid(const Device& dev, Role role, int64_t want)
+{
+  const int64_t cap = (int64_t)FALLBACK_WGS_PER_CU * dev.cus;
+  return (unsigned)((role == Role::fallback && want > cap) ? cap : want);
+}
 template <typename KeyT, int KIND, bool HAS_VAL>
 static HybridCfg hybrid_cfg(int64_t n, bool iota_payload, int algo)
 {
@@ -3797,7 +3882,9 @@ int sort_impl(const void* keys_in, void* keys_out, const int32_t* vals_in, int32
   Device dev;
   GX_HIP_TRY(device(&dev));
   if (algo != 1 && !fc.on) GX_HIP_TRY(hipMemsetAsync(status, 0, status_words * sizeof(unsigned long long), stream));
-  if (cells) GX_HIP_TRY(hipMemsetAsync(hist2, 0, (size_t)4 * BINS * NB2MAX * sizeof(uint32_t), stream));
+  // the cell tables start at zero: on the cursor path its first kernel, k_hf_sample, clears them on its way
+  const size_t hist2_bytes = (size_t)4 * BINS * NB2MAX * sizeof(uint32_t);
+  if (cells && !fc.on) GX_HIP_TRY(hipMemsetAsync(hist2, 0, hist2_bytes, stream));
   const int64_t range_rows = try_hybrid ? div_up(msd_ntiles, NRANGE) * msd_tile : div_up(ntiles, NRANGE) * TILE;
 
   const KeyT desc_mask = descending ? KeyT(~KeyT(0)) : KeyT(0);
@@ -3820,7 +3907,7 @@ int sort_impl(const void* keys_in, void* keys_out, const int32_t* vals_in, int32
       const int64_t ftiles  = div_up(n, (int64_t)FT);
       const int64_t frange  = (ftiles / NRANGE) * FT;  // rows per input range (whole tiles; the last range takes the rest)
       auto lds_hf = [&](int nb) { return (size_t)FT * sizeof(KeyT) + (size_t)(3 * nb + 16 + 4) * 4 + (size_t)2 * NW * 8; };
-      typedef void (*HfK)(const KeyT*, KeyT*, KeyT, SortPlan*, uint32_t*, uint32_t, int64_t, KeyT*);
+      typedef void (*HfK)(const KeyT*, KeyT*, KeyT, SortPlan*, uint32_t*, uint32_t, int64_t, KeyT*, uint32_t);
       HfK kf0 = k_hf_scatter<KeyT, CK, 0, 8>;
       // (the level-1 kernel and the cell grids are sized for bits2_max: the device may take the extra bit)
       HfK kf1 = fc.bits2_max <= 8 ? (HfK)k_hf_scatter<KeyT, CK, 1, 8> : (fc.bits2_max == 9 ? (HfK)k_hf_scatter<KeyT, CK, 1, 9> : (HfK)k_hf_scatter<KeyT, CK, 1, 10>);
@@ -3831,7 +3918,8 @@ int sort_impl(const void* keys_in, void* keys_out, const int32_t* vals_in, int32
       if (sblocks > 2048) sblocks = 2048;
       const KeyT* kin = static_cast<const KeyT*>(keys_in);
       KeyT* bufA      = keys_out ? static_cast<KeyT*>(keys_out) : ka_scratch;
-      hipLaunchKernelGGL((k_hf_sample<KeyT, CK, false>), dim3((unsigned)sblocks), dim3(256), 0, stream, kin, n, desc_mask, plan, fc.stride, frange);
+      hipLaunchKernelGGL((k_hf_sample<KeyT, CK, false>), dim3((unsigned)sblocks), dim3(256), 0, stream, kin, n, desc_mask, plan, fc.stride, frange,
+                         reinterpret_cast<uint4*>(hist2), hist2_bytes / sizeof(uint4));
       hipLaunchKernelGGL(k_hf_plan, dim3(1), dim3(BINS), 0, stream, plan, 0, (int)(8 * sizeof(KeyT)), n, fc.bits2, 1 << 13, fc.stride, frange, FT,
                          (unsigned long long)fc.slot_rows, g_cursor_margin, MIN_SHIFT2, fc.bits2_max, 0ull, CK == K_SIGNED ? 1 : 0, (KIND == K_FLOAT) ? 0 : g_counting);
       {
@@ -3862,7 +3950,7 @@ int sort_impl(const void* keys_in, void* keys_out, const int32_t* vals_in, int32
       }
       prof_mark(1, stream);
       prof_mark_h(0, stream);
-      GX_HIP_TRY(launch_lds(dev, kf0, dim3((unsigned)ftiles), dim3(BT), lds_hf(256), stream, kin, slot0_buf, desc_mask, plan, hist2, 1u << 13, n, (KeyT*)nullptr));
+      GX_HIP_TRY(launch_lds(dev, kf0, dim3((unsigned)ftiles), dim3(BT), lds_hf(256), stream, kin, slot0_buf, desc_mask, plan, hist2, 1u << 13, n, (KeyT*)nullptr, 0u));
       if constexpr (sizeof(KeyT) == 8) {
         if (allow_split)
         {
@@ -3873,7 +3961,7 @@ int sort_impl(const void* keys_in, void* keys_out, const int32_t* vals_in, int32
       hipLaunchKernelGGL(k_hf_plan, dim3(1), dim3(BINS), 0, stream, plan, 2, (int)(8 * sizeof(KeyT)), n, fc.bits2, 1 << 13, fc.stride, frange, FT,
                          (unsigned long long)fc.slot_rows, g_cursor_margin, MIN_SHIFT2, fc.bits2_max, (unsigned long long)nb_buf);
       prof_mark_h(1, stream);
-      GX_HIP_TRY(launch_lds(dev, kf1, dim3((unsigned)(ftiles + NRANGE * BINS)), dim3(BT), lds_hf(nbf), stream, slot0_buf, kb_scratch, desc_mask, plan, hist2, 1u << 13, n, bufA));
+      GX_HIP_TRY(launch_lds(dev, kf1, dim3((unsigned)(ftiles + NRANGE * BINS)), dim3(BT), lds_hf(nbf), stream, slot0_buf, kb_scratch, desc_mask, plan, hist2, 1u << 13, n, bufA, 0u));
       prof_mark_h(2, stream);
       hipLaunchKernelGGL(k_plan2, dim3(BINS), dim3(GX_WAVE), 0, stream, plan, hist2, base2, NPASS, 1);
       prof_mark_h(3, stream);
@@ -3896,7 +3984,8 @@ int sort_impl(const void* keys_in, void* keys_out, const int32_t* vals_in, int32
       // cell has left it by now); the LSD passes below then sort X between the two halves of the level-0 buffer
       hipLaunchKernelGGL(k_big_plan, dim3(1), dim3(BINS), 0, stream, plan, (unsigned long long)(fc.slot_rows / 2));
       hipLaunchKernelGGL(k_big_cells, dim3(BINS), dim3(GX_WAVE), 0, stream, (const SortPlan*)plan, (const uint32_t*)hist2, xoff, biglist);
-      GX_HIP_TRY(launch_lds(dev, kf2, dim3((unsigned)(ftiles + NRANGE * BINS)), dim3(BT), lds_hf(nbf), stream, slot0_buf, kb_scratch, desc_mask, plan, hist2, 1u << 13, n, bufA));
+      GX_HIP_TRY(launch_lds(dev, kf2, dim3(role_grid(dev, Role::fallback, ftiles + NRANGE * BINS)), dim3(BT), lds_hf(nbf), stream, slot0_buf, kb_scratch, desc_mask, plan,
+                            hist2, 1u << 13, n, bufA, (uint32_t)(ftiles + NRANGE * BINS)));
       hipLaunchKernelGGL(k_hf_clear_status, dim3(2048), dim3(256), 0, stream, plan, reinterpret_cast<uint4*>(status), status_words / 2);
     }
   }
@@ -3936,6 +4025,19 @@ int sort_impl(const void* keys_in, void* keys_out, const int32_t* vals_in, int32
         }
       }
       if (kpt1 != hyb_kpt) return GX_EINTERNAL;  // the 9-bit pass exists for 16 keys per thread only (g_msd_kpt knob)
+      // behind a cursor-path sort of integer keys this chain is a fallback: bounded grids, the kernels walk their tiles / cells (the
+      // partition passes in their MULTI form, which exists for the default knobs; with others they keep one workgroup per ticket).
+      // Float keys: the chain is what sorts every column with a NaN or a -0.0 -- primary role, launched as without the cursor path
+      const Role lb_role = (fc.on && SMALLOK) ? Role::fallback : Role::primary;
+      bool msd_multi     = false;
+      if constexpr (!HAS_VAL && SMALLOK) {
+        if (lb_role == Role::fallback && hyb_kpt == 16 && g_lbw == 16) {
+          kmsd0 = (MsdK)k_msd_pass<KeyT, KIND, HAS_VAL, 16, 16, 8, true>;
+          kmsd1 = hc.bits2 > 8 ? (MsdK)k_msd_pass<KeyT, KIND, HAS_VAL, 16, 16, 9, true> : kmsd0;
+          msd_multi = true;
+        }
+      }
+      const Role msd_role = msd_multi ? Role::fallback : Role::primary;
       // ---- up-front: varying bits + level-0 histogram (one read of the keys), plan
       hipLaunchKernelGGL((k_hy_hist<KeyT, KIND, true>), dim3((unsigned)hblocks), dim3(BT), 0, stream,
                          static_cast<const KeyT*>(keys_in), n, desc_mask, plan, range_rows);
@@ -3968,14 +4070,14 @@ int sort_impl(const void* keys_in, void* keys_out, const int32_t* vals_in, int32
       m.spin_ticks  = (unsigned long long)g_spin_ms * 100000ull | (g_soft_fault ? SPIN_SOFT_BIT : 0ull);
       m.inject_tile = g_inject_tile;
       if (!cursor_marked) prof_mark_h(0, stream);
-      GX_HIP_TRY(launch_lds(dev, kmsd0, dim3((unsigned)(msd_ntiles + NRANGE)), dim3(BT), lds_msd(hyb_kpt, BINS), stream, m));
+      GX_HIP_TRY(launch_lds(dev, kmsd0, dim3(role_grid(dev, msd_role, msd_ntiles + NRANGE)), dim3(BT), lds_msd(hyb_kpt, BINS), stream, m));
       if (!cursor_marked) prof_mark_h(1, stream);
       m.in    = bufA;
       m.out   = bufB;
       m.vin   = valA;
       m.vout  = valB;
       m.level = 1;
-      GX_HIP_TRY(launch_lds(dev, kmsd1, dim3((unsigned)(msd_ntiles + BINS + NRANGE)), dim3(BT), lds_msd(hyb_kpt, nb1), stream, m));
+      GX_HIP_TRY(launch_lds(dev, kmsd1, dim3(role_grid(dev, msd_role, msd_ntiles + BINS + NRANGE)), dim3(BT), lds_msd(hyb_kpt, nb1), stream, m));
       if (!cursor_marked) prof_mark_h(2, stream);
       hipLaunchKernelGGL(k_plan2, dim3(BINS), dim3(GX_WAVE), 0, stream, plan, hist2, base2, NPASS, 0);
       if (!cursor_marked) prof_mark_h(3, stream);
@@ -3984,14 +4086,14 @@ int sort_impl(const void* keys_in, void* keys_out, const int32_t* vals_in, int32
       if constexpr (SMALLOK) {
         if (hc.cl2 == 13) kplace = k_local_place<KeyT, KIND, HAS_VAL, 13>;
       }
-      GX_HIP_TRY(launch_lds(dev, kplace, dim3(local_place_grid(BINS << hc.bits2)), dim3(ls_bt), place_lds_bytes(hc.cl2), stream, (const KeyT*)bufB, bufA,
+      GX_HIP_TRY(launch_lds(dev, kplace, dim3(role_grid(dev, lb_role, local_place_grid(BINS << hc.bits2))), dim3(ls_bt), place_lds_bytes(hc.cl2), stream, (const KeyT*)bufB, bufA,
                                  (const uint32_t*)valB, valA, desc_mask, plan, hist2, base2, todo, m.exp, 0));
-      GX_HIP_TRY(launch_lds(dev, kloc, dim3(local_sort_grid(BINS << hc.bits2)), dim3(ls_bt), lds_loc(hc.cl2), stream, bufB, bufA, valB, valA, desc_mask,
+      GX_HIP_TRY(launch_lds(dev, kloc, dim3(role_grid(dev, lb_role, local_sort_grid(BINS << hc.bits2))), dim3(ls_bt), lds_loc(hc.cl2), stream, bufB, bufA, valB, valA, desc_mask,
                                  plan, hist2, base2, m.exp, 0, (const uint32_t*)todo));
       if (hc.cl2_alt == 14) {  // the cell sort on 16384-key cells, should k_hy_plan have switched to them (no-ops otherwise)
-        GX_HIP_TRY(launch_lds(dev, (k_local_place<KeyT, KIND, HAS_VAL, 14>), dim3(local_place_grid(BINS << hc.bits2)), dim3((1 << 14) / 16), place_lds_bytes(14), stream,
+        GX_HIP_TRY(launch_lds(dev, (k_local_place<KeyT, KIND, HAS_VAL, 14>), dim3(role_grid(dev, lb_role, local_place_grid(BINS << hc.bits2))), dim3((1 << 14) / 16), place_lds_bytes(14), stream,
                                    (const KeyT*)bufB, bufA, (const uint32_t*)valB, valA, desc_mask, plan, hist2, base2, todo, m.exp, 0));
-        GX_HIP_TRY(launch_lds(dev, (k_local_sort<KeyT, KIND, HAS_VAL, 14>), dim3(local_sort_grid(BINS << hc.bits2)), dim3((1 << 14) / 16), lds_loc(14), stream, bufB, bufA,
+        GX_HIP_TRY(launch_lds(dev, (k_local_sort<KeyT, KIND, HAS_VAL, 14>), dim3(role_grid(dev, lb_role, local_sort_grid(BINS << hc.bits2))), dim3((1 << 14) / 16), lds_loc(14), stream, bufB, bufA,
                                    valB, valA, desc_mask, plan, hist2, base2, m.exp, 0, (const uint32_t*)todo));
       }
       if (!cursor_marked) prof_mark_h(4, stream);
@@ -4241,7 +4343,7 @@ int sortx_level0(const void* keys, int64_t n, int64_t recv_rows_max, const unsig
   hipLaunchKernelGGL((k_hf_sample<KeyT, KIND, true>), dim3((unsigned)sblocks), dim3(256), 0, stream, kin, n, KeyT(0), L.plan, cs.stride, frange);
   hipLaunchKernelGGL(k_hf_plan, dim3(1), dim3(BINS), 0, stream, L.plan, 1, (int)(8 * sizeof(KeyT)), n, bits2_hint, 1 << 13, cs.stride, frange, FT,
                      (unsigned long long)cs.slot_rows, 8.0f, MIN_SHIFT2, bits2_hint);
-  GX_HIP_TRY(launch_lds(dev, (k_hf_scatter<KeyT, KIND, 0, 8>), dim3((unsigned)ftiles), dim3(BT), lds0, stream, kin, L.level0, KeyT(0), L.plan, L.hist2, 1u << 13, n, (KeyT*)nullptr));
+  GX_HIP_TRY(launch_lds(dev, (k_hf_scatter<KeyT, KIND, 0, 8>), dim3((unsigned)ftiles), dim3(BT), lds0, stream, kin, L.level0, KeyT(0), L.plan, L.hist2, 1u << 13, n, (KeyT*)nullptr, 0u));
   hipLaunchKernelGGL(k_hf_plan, dim3(1), dim3(BINS), 0, stream, L.plan, 2, (int)(8 * sizeof(KeyT)), n, bits2_hint, 1 << 13, cs.stride, frange, FT,
                      (unsigned long long)cs.slot_rows, 8.0f, MIN_SHIFT2, bits2_hint);
   GX_LAUNCH_CHECK();
@@ -4276,7 +4378,7 @@ int sortx_finish(int64_t n_send, int64_t recv_rows_max, int64_t n, const unsigne
   constexpr int MIN_SHIFT2 = 8;
   constexpr int WORD_BYTES = (int)sizeof(typename PlaceWord<KeyT, KIND, false>::type);
   auto lds_hf = [&](int nb) { return (size_t)FT * sizeof(KeyT) + (size_t)(3 * nb + 16 + 4) * 4 + (size_t)2 * NW * 8; };
-  typedef void (*HfK)(const KeyT*, KeyT*, KeyT, SortPlan*, uint32_t*, uint32_t, int64_t, KeyT*);
+  typedef void (*HfK)(const KeyT*, KeyT*, KeyT, SortPlan*, uint32_t*, uint32_t, int64_t, KeyT*, uint32_t);
   HfK kf1 = cr.bits2_max <= 8 ? (HfK)k_hf_scatter<KeyT, KIND, 1, 8> : (cr.bits2_max == 9 ? (HfK)k_hf_scatter<KeyT, KIND, 1, 9> : (HfK)k_hf_scatter<KeyT, KIND, 1, 10>);
   HfK kf2 = cr.bits2_max <= 8 ? (HfK)k_hf_scatter<KeyT, KIND, 2, 8> : (cr.bits2_max == 9 ? (HfK)k_hf_scatter<KeyT, KIND, 2, 9> : (HfK)k_hf_scatter<KeyT, KIND, 2, 10>);
   const int nbf = cr.bits2_max <= 8 ? 256 : (1 << cr.bits2_max);
@@ -4291,7 +4393,7 @@ int sortx_finish(int64_t n_send, int64_t recv_rows_max, int64_t n, const unsigne
   hipLaunchKernelGGL(k_hfx_plan, dim3(1), dim3(BINS), 0, stream, L.plan, (long long)n, cr.bits2, cr.bits2_max, 1 << 13, MIN_SHIFT2, FT, masks2_host[0], masks2_host[1],
                      (uint32_t)nreg, (const uint32_t*)L.breg0, L.x_tile0, (const uint32_t*)L.x_start, (const uint32_t*)L.x_count, (const uint32_t*)L.x_bucket,
                      (unsigned long long)L.cells_rows);
-  GX_HIP_TRY(launch_lds(dev, kf1, dim3((unsigned)l1_grid), dim3(BT), lds_hf(nbf), stream, (const KeyT*)L.level0, L.cells, KeyT(0), L.plan, L.hist2, 1u << 13, n, (KeyT*)nullptr));
+  GX_HIP_TRY(launch_lds(dev, kf1, dim3((unsigned)l1_grid), dim3(BT), lds_hf(nbf), stream, (const KeyT*)L.level0, L.cells, KeyT(0), L.plan, L.hist2, 1u << 13, n, (KeyT*)nullptr, 0u));
   hipLaunchKernelGGL(k_plan2, dim3(BINS), dim3(GX_WAVE), 0, stream, L.plan, L.hist2, L.base2, (int)sizeof(KeyT), 1);
   GX_HIP_TRY(launch_lds(dev, (k_local_place<KeyT, KIND, false, 13>), dim3(local_place_grid(BINS << cr.bits2)), dim3((1 << 13) / 16), place_lds_bytes(13, WORD_BYTES), stream,
                              (const KeyT*)L.cells, bufA, (const uint32_t*)nullptr, (uint32_t*)nullptr, KeyT(0), L.plan, L.hist2, L.base2, L.todo, 0, 1));
@@ -4301,7 +4403,8 @@ int sortx_finish(int64_t n_send, int64_t recv_rows_max, int64_t n, const unsigne
   const size_t xcap = L.level0_rows / 2;
   hipLaunchKernelGGL(k_big_plan, dim3(1), dim3(BINS), 0, stream, L.plan, (unsigned long long)xcap);
   hipLaunchKernelGGL(k_big_cells, dim3(BINS), dim3(GX_WAVE), 0, stream, (const SortPlan*)L.plan, (const uint32_t*)L.hist2, L.xoff, L.biglist);
-  GX_HIP_TRY(launch_lds(dev, kf2, dim3((unsigned)l1_grid), dim3(BT), lds_hf(nbf), stream, (const KeyT*)L.level0, L.cells, KeyT(0), L.plan, L.hist2, 1u << 13, n, (KeyT*)nullptr));
+  GX_HIP_TRY(launch_lds(dev, kf2, dim3(role_grid(dev, Role::fallback, l1_grid)), dim3(BT), lds_hf(nbf), stream, (const KeyT*)L.level0, L.cells, KeyT(0), L.plan, L.hist2, 1u << 13, n,
+                        (KeyT*)nullptr, (uint32_t)l1_grid));
   hipLaunchKernelGGL(k_hf_clear_status, dim3(2048), dim3(256), 0, stream, L.plan, reinterpret_cast<uint4*>(L.status), L.status_words / 2);
   int64_t hblocks = div_up(n, (int64_t)BT * 8);
   if (hblocks > 2048) hblocks = 2048;
