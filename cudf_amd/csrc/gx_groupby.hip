@@ -11,7 +11,9 @@
 // compensation word, so sum + comp is the exact total up to second-order terms and the rounded
 // result is within 1 ulp of the correctly rounded sum regardless of the order in which the
 // atomics land (the reference's plain relaxed atomic add -- device_atomics.cuh:57-62 -- drifts by
-// sqrt(rows per group) ulps).  integer SUM: 64-bit wrapping atomics (exact).
+// sqrt(rows per group) ulps).  A group that holds +-inf or NaN, or whose sum overflows, gets what
+// the reference's plain addition gives (+-inf / NaN): the error term of such an addition is NaN and
+// is not accumulated.  integer SUM: 64-bit wrapping atomics (exact).
 #include <type_traits>
 
 #include "gx_common.hpp"
@@ -79,7 +81,9 @@ struct Acc<V, true> {
     const double s   = old + x;                // the value the atomic unit stored (RN)
     const double bb  = s - old;
     const double err = (old - (s - bb)) + (x - bb);
-    if (err != 0.0) atomicAdd(&comp[g], err);
+    // ordered compare: when old or x is +-inf or s overflows, bb is inf - inf and err is NaN -- skip it, so that sum[g] alone
+    // carries the +-inf / NaN that plain addition gives and comp[g] stays finite
+    if (err < 0.0 || err > 0.0) atomicAdd(&comp[g], err);
   }
 };
 template <typename V>
@@ -522,7 +526,7 @@ struct LdsAcc<V, true> {
     const double s   = old + x;
     const double bb  = s - old;
     const double err = (old - (s - bb)) + (x - bb);
-    if (err != 0.0) atomicAdd(&comp[g], err);
+    if (err < 0.0 || err > 0.0) atomicAdd(&comp[g], err);  // a NaN err (non-finite sum) is dropped: see Acc<V, true>
   }
 };
 template <typename V>
@@ -541,8 +545,8 @@ __device__ __forceinline__ void global_merge(double* sum, double* comp, int64_t 
     const double old = atomicAdd(&sum[g], psum);
     const double s   = old + psum;
     const double bb  = s - old;
-    const double err = ((old - (s - bb)) + (psum - bb)) + pcomp;
-    if (err != 0.0) atomicAdd(&comp[g], err);
+    const double err = ((old - (s - bb)) + (psum - bb)) + pcomp;  // pcomp is finite: no NaN ever enters a comp word
+    if (err < 0.0 || err > 0.0) atomicAdd(&comp[g], err);         // non-finite sum: err is NaN, and sum[g] says it all
   } else {
     unsigned long long u;
     __builtin_memcpy(&u, &psum, 8);

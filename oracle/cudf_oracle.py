@@ -542,16 +542,119 @@ def distinct_left_join(left_cols, right_cols, left_valids=None, right_valids=Non
 # ----------------------------------------------------------------------------------------------
 
 
+def _exact_total_int(x: np.ndarray):
+    """Σx for finite float64 x as an exact integer T and a scale sh: Σx = T * 2**sh.  Mantissas are summed per exponent in two
+    27-bit halves (no int64 overflow below 2^36 elements), then shifted onto the smallest exponent as Python integers."""
+    m, e = np.frexp(x)
+    M = np.ldexp(m, 53).astype(np.int64)  # exact: |m| < 1 has at most 53 significant bits
+    e = e.astype(np.int64) - 53
+    nz = M != 0
+    if not nz.any():
+        return 0, 0
+    M, e = M[nz], e[nz]
+    ue, inv = np.unique(e, return_inverse=True)
+    hi = np.zeros(len(ue), np.int64)
+    lo = np.zeros(len(ue), np.int64)
+    np.add.at(hi, inv, M >> 27)
+    np.add.at(lo, inv, M & ((1 << 27) - 1))
+    emin = int(ue[0])
+    total = 0
+    for ex, h, l in zip(ue.tolist(), hi.tolist(), lo.tolist()):
+        total += ((h << 27) + l) << (ex - emin)
+    return total, emin
+
+
+def _scaled_int_to_float(total: int, sh: int) -> float:
+    """correctly rounded float64 of total * 2**sh; ±inf outside the double range"""
+    if total == 0:
+        return 0.0
+    if total.bit_length() <= 1000:
+        try:
+            r = math.ldexp(float(total), sh)  # float(int) rounds to nearest even; the scaling is exact in the normal range
+        except OverflowError:
+            return math.inf if total > 0 else -math.inf
+        if abs(r) >= 2.2250738585072014e-308:
+            return r
+    from fractions import Fraction  # subnormal result (ldexp would round a second time) or an integer too wide for float()
+    try:
+        return float(Fraction(total) * Fraction(2) ** sh)
+    except OverflowError:
+        return math.inf if total > 0 else -math.inf
+
+
+def exact_sum(x) -> np.float64:
+    """The sum the reference's plain floating-point addition converges to, without its rounding: the correctly rounded exact sum
+    of finite input; NaN if any element is NaN or both signs of infinity occur; ±inf if one sign of infinity occurs or the exact
+    finite sum lies outside the double range (math.fsum raises in the last two cases, and on an intermediate overflow)."""
+    x = np.asarray(x, np.float64).reshape(-1)
+    fin = np.isfinite(x)
+    if not fin.all():
+        bad = x[~fin]
+        if np.isnan(bad).any() or ((bad > 0).any() and (bad < 0).any()):
+            return np.float64(np.nan)
+        return np.float64(bad[0])
+    try:
+        return np.float64(math.fsum(x))
+    except OverflowError:
+        return np.float64(_scaled_int_to_float(*_exact_total_int(x)))
+
+
+def exact_prefix_sums(x) -> np.ndarray:
+    """exact_sum of every prefix x[:i+1] (float64): a running exact integer on the smallest exponent of the column, rounded once
+    per row.  From the first NaN (or the second sign of infinity) on the prefixes are NaN; after one infinity they are that
+    infinity."""
+    x = np.asarray(x, np.float64).reshape(-1)
+    n = len(x)
+    out = np.empty(n, np.float64)
+    if n == 0:
+        return out
+    fin = np.isfinite(x)
+    m, e = np.frexp(np.where(fin, x, 0.0))
+    M = np.ldexp(m, 53).astype(np.int64)
+    e = e.astype(np.int64) - 53
+    nz = M != 0
+    emin = int(e[nz].min()) if nz.any() else 0
+    sh = np.where(nz, e - emin, 0)
+    total = 0
+    res = [0.0] * n
+    special = None  # nan / +inf / -inf once a non-finite value has entered the prefix
+    small = 2.2250738585072014e-308
+    ldexp = math.ldexp
+    allfin = bool(fin.all())
+    finl = fin.tolist()
+    xl = None if allfin else x.tolist()
+    for i, (mi, si) in enumerate(zip(M.tolist(), sh.tolist())):
+        if not allfin and not finl[i]:
+            v = xl[i]
+            if special is None:
+                special = v
+            elif special != v:  # NaN != anything; +inf != -inf
+                special = math.nan
+        if special is not None:
+            res[i] = special
+            continue
+        total += mi << si
+        try:
+            r = ldexp(float(total), emin)
+        except OverflowError:  # past the double range, or an integer too wide for float()
+            r = _scaled_int_to_float(total, emin)
+        if -small < r < small and total != 0:
+            r = _scaled_int_to_float(total, emin)
+        res[i] = r
+    out[:] = res
+    return out
+
+
 def _exact_group_sums(labels: np.ndarray, values: np.ndarray, ngroups: int) -> np.ndarray:
-    """Correctly rounded float64 sum per group (math.fsum): the parity target for f64 SUM/MEAN
-    (north_star: within 1 ulp).  The reference's own sum is an unordered relaxed atomic add
+    """Correctly rounded float64 sum per group (exact_sum: ±inf / NaN where plain addition gives them): the parity target for
+    f64 SUM/MEAN (north_star: within 1 ulp).  The reference's own sum is an unordered relaxed atomic add
     (cpp/include/cudf/detail/utilities/device_atomics.cuh:57-62), i.e. any summation order."""
     order = np.argsort(labels, kind="stable")
     sv = values[order].astype(np.float64)
     bounds = np.searchsorted(labels[order], np.arange(ngroups + 1))
     out = np.empty(ngroups, np.float64)
     for g in range(ngroups):
-        out[g] = math.fsum(sv[bounds[g] : bounds[g + 1]])
+        out[g] = exact_sum(sv[bounds[g] : bounds[g + 1]])
     return out
 
 
@@ -600,7 +703,8 @@ def groupby_agg(keys: np.ndarray, values: np.ndarray, aggs: Sequence[str],
                     s = _exact_group_sums(labels[vv], values[vv].astype(np.float64), g)
                 else:
                     s = np.bincount(labels[vv], weights=values[vv].astype(np.float64), minlength=g)
-                s = s.astype(values.dtype) if a == "sum" else s
+                with np.errstate(over="ignore"):  # a float32 SUM past FLT_MAX is ±inf
+                    s = s.astype(values.dtype) if a == "sum" else s
             else:
                 acc = np.zeros(g, np.uint64)
                 np.add.at(acc, labels[vv], values[vv].astype(np.int64).view(np.uint64))
@@ -773,7 +877,8 @@ def groupby_sort_agg(keys, values, agg: str, keys_valid=None, values_valid=None,
         return ukeys, ukv, out, ok & (svv[pos] if g else ok)
     if agg == "sum":
         if isf:
-            out = _exact_group_sums(labels[svv], sv[svv].astype(np.float64), g).astype(values.dtype)
+            with np.errstate(over="ignore"):
+                out = _exact_group_sums(labels[svv], sv[svv].astype(np.float64), g).astype(values.dtype)
         else:
             acc = np.zeros(g, np.uint64)
             np.add.at(acc, labels[svv], sv[svv].astype(np.int64).view(np.uint64))
@@ -1066,7 +1171,8 @@ def reduce(values: np.ndarray, op: str, valid=None, out_dtype=None, init=None, i
             return x.astype(out_dtype).prod(dtype=out_dtype), True
     if op == "sum":
         if out_dtype.kind == "f":
-            return out_dtype.type(math.fsum(x.astype(np.float64))), True
+            with np.errstate(over="ignore"):
+                return exact_sum(x).astype(out_dtype)[()], True
         return x.astype(out_dtype).sum(dtype=out_dtype), True
     if op == "min":
         return x[np.argmin(sortable_bits(x))].astype(out_dtype), True
@@ -1079,16 +1185,18 @@ def reduce(values: np.ndarray, op: str, valid=None, out_dtype=None, init=None, i
             out_dtype = np.dtype(np.float64)
         if out_dtype.kind != "f":
             raise ValueError("Unsupported output data type")
-        return out_dtype.type(math.fsum(x.astype(np.float64)) / len(x)), True
+        with np.errstate(over="ignore"):
+            return (exact_sum(x) / len(x)).astype(out_dtype)[()], True
     raise ValueError(op)
 
 
 def scan(values: np.ndarray, op: str = "sum", inclusive: bool = True, valid=None,
-         null_include: bool = False):
+         null_include: bool = False, exact: bool = False):
     """cudf::scan (cpp/src/reductions/scan/scan.cpp:13-54, scan_inclusive.cu:36-240,
     scan_exclusive.cu): output dtype == input dtype (ints wrap); null_policy EXCLUDE: nulls are
     replaced by the identity and stay null in the output (mask copied); INCLUDE: everything from
-    the first null on is null (mask_scan :36-61).  Returns (values, valid mask)."""
+    the first null on is null (mask_scan :36-61).  exact=True: a float SUM is the exact prefix rounded once (exact_prefix_sums) instead of
+    the sequential sum in the column type.  Returns (values, valid mask)."""
     v = np.asarray(values)
     n = len(v)
     m = np.ones(n, bool) if valid is None else np.asarray(valid, bool)
@@ -1108,8 +1216,11 @@ def scan(values: np.ndarray, op: str = "sum", inclusive: bool = True, valid=None
     else:
         raise ValueError(op)
     x = np.where(m, v, ident).astype(dt)
-    with np.errstate(over="ignore"):
-        inc = f(x, dtype=dt) if op in ("sum", "product") else f(x)
+    with np.errstate(over="ignore", invalid="ignore"):
+        if exact and op == "sum" and dt.kind == "f":
+            inc = exact_prefix_sums(x).astype(dt)
+        else:
+            inc = f(x, dtype=dt) if op in ("sum", "product") else f(x)
     if inclusive:
         out = inc
     else:
