@@ -32,6 +32,7 @@ INT8, INT16, INT32, INT64, UINT8, UINT16, UINT32, UINT64, FLOAT32, FLOAT64, BOOL
 OP_SUM, OP_PRODUCT, OP_MIN, OP_MAX, OP_COUNT_VALID, OP_COUNT_ALL = 0, 1, 2, 3, 4, 5
 OP_MEAN = 10
 CMP_EQ, CMP_NE, CMP_LT, CMP_LE, CMP_GT, CMP_GE = range(6)
+KEEP_ANY, KEEP_FIRST, KEEP_LAST, KEEP_NONE = range(4)
 
 _PROTOS = {
     "gx_version": (ctypes.c_char_p, []),
@@ -163,6 +164,10 @@ _PROTOS = {
     "gx_compare_scalar": (_i, [_i, _p, _p, _i64, _i, ctypes.c_uint64, _p, _p]),
     "gx_select_set_stages": (None, [_i]),
     "gx_compact_set_kernel": (None, [_i]),
+    # deduplicating selectors (gx_distinct.hip): the plan at the start of their scratch, the table behind it
+    "gx_select_unique": (_i, [_i, ctypes.POINTER(_i), ctypes.POINTER(_p), ctypes.POINTER(_p), ctypes.POINTER(_i64), _i64, _i, _i, _p, _p, _sz, _p]),
+    "gx_select_distinct": (_i, [_i, ctypes.POINTER(_i), ctypes.POINTER(_p), ctypes.POINTER(_p), ctypes.POINTER(_i64), _i64, _i, _i, _p, _p, _sz, _p]),
+    "gx_distinct_set_hash_bits": (None, [_i]),
 }
 
 for _name, (_res, _args) in _PROTOS.items():

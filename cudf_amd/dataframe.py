@@ -1,5 +1,5 @@
 """Thin pandas-like wrapper over the hot path (the cudf.DataFrame surface of the reference, reduced
-to the methods that land on it): sort_values, merge, groupby(...).agg, df[mask], dropna.
+to the methods that land on it): sort_values, merge, groupby(...).agg, df[mask], dropna, drop_duplicates.
 
 reference: python/cudf/cudf/core/dataframe.py (sort_values -> core/_internals/sorting.py ->
 pylibcudf.sorting.sorted_order + gather; merge -> core/join/join.py -> pylibcudf.join.inner_join /
@@ -99,6 +99,19 @@ class DataFrame:
         keys = [order.index(k) for k in names]
         need = int(thresh) if thresh is not None else (1 if how == "all" else len(keys))
         return self._from_columns(ops.dropna_rows(list(self._cols.values()), keys, need))
+
+    def drop_duplicates(self, subset: Optional[Union[str, Sequence[str]]] = None, keep: Union[str, bool] = "first") -> "DataFrame":
+        """pandas' DataFrame.drop_duplicates: of the rows that are equal in `subset` (default: every column) keep the first
+        (keep="first"), the last ("last") or none (False).  Row order is kept; nulls are equal to nulls and NaNs to NaNs, as in pandas."""
+        if keep not in ("first", "last", False):
+            raise ValueError('keep must be either "first", "last" or False')
+        names = list(self._cols) if subset is None else ([subset] if isinstance(subset, str) else list(subset))
+        for k in names:
+            if k not in self._cols:
+                raise KeyError(k)
+        order = list(self._cols)
+        keys = [order.index(k) for k in names]
+        return self._from_columns(ops.distinct(list(self._cols.values()), keys, keep=keep or "none"))
 
     def __len__(self) -> int:
         return next(iter(self._cols.values())).size if self._cols else 0

@@ -1121,6 +1121,108 @@ def dropna_rows(cols: Sequence[Column], keys: Sequence[int], keep_threshold: int
     return _compact(cols, plan, n, count)
 
 
+# ---- deduplication (cudf::unique / distinct / stable_distinct / distinct_indices / unique_count / distinct_count: stream_compaction.hpp).
+# Two more selectors (gx_distinct.hip): unique compares neighbouring rows, distinct reduces over a lock-free table of row indices.
+# Their scratch STARTS with the plan, so _compact / gx_compact_indices take it as it is.
+
+_KEEP = {"any": L.KEEP_ANY, "first": L.KEEP_FIRST, "last": L.KEEP_LAST, "none": L.KEEP_NONE}
+_F_NULLS_EQUAL, _F_NANS_EQUAL, _F_NAN_IS_NULL, _F_DROP_NULL_ROWS = 1, 2, 4, 8
+
+
+def _keep_code(keep: str) -> int:
+    if keep not in _KEEP:
+        raise ValueError(f"keep must be one of any / first / last / none, not {keep!r}")
+    return _KEEP[keep]
+
+
+def _select_dedup(fn, kc: Sequence[Column], n: int, keep: int, flags: int):
+    """(scratch that starts with the plan, selected rows) of gx_select_unique / gx_select_distinct over the key columns kc"""
+    if not 1 <= len(kc) <= 32:
+        raise ValueError("1 to 32 key columns")
+    dts = (ctypes.c_int * len(kc))(*[c.gx for c in kc])
+    datas = _ptr_array([c.data_ptr for c in kc])
+    valids = _ptr_array([c.mask_ptr if c.has_nulls() else None for c in kc])
+    cnt = _dev_i64()
+    plan = _run(fn, len(kc), dts, datas, valids, None, n, keep, flags, ptr(cnt))
+    return plan, int(cnt.item())
+
+
+def _dedup(fn, cols: Sequence[Column], keys: Sequence[int], keep: str, flags: int) -> List[Column]:
+    cols = list(cols)
+    code = _keep_code(keep)
+    kc = _keys_of(cols, keys)
+    n = cols[0].size if cols else 0
+    if n == 0 or not kc:
+        return [_copy_column(c) for c in cols]
+    plan, count = _select_dedup(fn, kc, n, code, flags)
+    return _compact(cols, plan, n, count)
+
+
+def unique(cols: Sequence[Column], keys: Sequence[int], keep: str = "any", nulls_equal: bool = True) -> List[Column]:
+    """cudf::unique: runs of CONSECUTIVE rows that are equal in the key columns cols[k], k in keys, collapse to their first row
+    (keep = "first" / "any"), their last ("last"), or vanish unless they are one row long ("none").  Row order is kept; NaNs compare
+    equal, -0.0 == +0.0; nulls compare equal unless nulls_equal is False (then a row holding a null equals no row)."""
+    return _dedup(_lib.gx_select_unique, cols, keys, keep, (_F_NULLS_EQUAL if nulls_equal else 0) | _F_NANS_EQUAL)
+
+
+def distinct(cols: Sequence[Column], keys: Sequence[int], keep: str = "any", nulls_equal: bool = True,
+             nans_equal: bool = True) -> List[Column]:
+    """cudf::distinct == cudf::stable_distinct here: one row per set of rows that are equal in the key columns -- the first of the
+    set ("first"), the last ("last"), whichever ("any"), or only the rows without a duplicate ("none") -- in INPUT ORDER (the
+    reference leaves distinct's order open).  A row holding a null (a NaN) with nulls_equal (nans_equal) False equals no row and
+    is always kept."""
+    return _dedup(_lib.gx_select_distinct, cols, keys, keep,
+                  (_F_NULLS_EQUAL if nulls_equal else 0) | (_F_NANS_EQUAL if nans_equal else 0))
+
+
+stable_distinct = distinct
+
+
+def distinct_indices(key_cols: Sequence[Column], keep: str = "any", nulls_equal: bool = True, nans_equal: bool = True) -> Column:
+    """cudf::distinct_indices: the row numbers distinct() keeps when every column of the table is a key (INT32, ascending)"""
+    kc = list(key_cols)
+    code = _keep_code(keep)
+    n = kc[0].size if kc else 0
+    if n == 0:
+        return Column.empty(np.int32, 0)
+    plan, count = _select_dedup(_lib.gx_select_distinct, kc, n, code,
+                                (_F_NULLS_EQUAL if nulls_equal else 0) | (_F_NANS_EQUAL if nans_equal else 0))
+    out = Column.empty(np.int32, count)
+    L.check(_lib.gx_compact_indices(n, ptr(plan), out.data_ptr, stream_ptr()), "gx_compact_indices")
+    return out
+
+
+def _dedup_count(fn, cols_or_col, nulls_equal: bool, null_policy: Optional[str], nan_policy: Optional[str]) -> int:
+    """table form (a sequence of key columns): nulls_equal decides, NaNs are equal.  Column form (one Column): null_policy "include"
+    / "exclude" and nan_policy "valid" (all NaNs one value) / "null" (a NaN is a null element).  The count word alone is read."""
+    if isinstance(cols_or_col, Column):
+        np_, nn = null_policy or "include", nan_policy or "valid"
+        if np_ not in ("include", "exclude") or nn not in ("valid", "null"):
+            raise ValueError("null_policy is include / exclude, nan_policy is valid / null")
+        kc = [cols_or_col]
+        flags = _F_NULLS_EQUAL | _F_NANS_EQUAL | (_F_NAN_IS_NULL if nn == "null" else 0) | (_F_DROP_NULL_ROWS if np_ == "exclude" else 0)
+    else:
+        if null_policy is not None or nan_policy is not None:
+            raise TypeError("null_policy / nan_policy belong to the column form")
+        kc = list(cols_or_col)
+        flags = (_F_NULLS_EQUAL if nulls_equal else 0) | _F_NANS_EQUAL
+    n = kc[0].size if kc else 0
+    if n == 0:
+        return 0
+    return _select_dedup(fn, kc, n, L.KEEP_ANY, flags)[1]
+
+
+def distinct_count(cols_or_col, nulls_equal: bool = True, null_policy: Optional[str] = None, nan_policy: Optional[str] = None) -> int:
+    """cudf::distinct_count: the number of rows distinct(keep="any") would keep; nothing is compacted"""
+    return _dedup_count(_lib.gx_select_distinct, cols_or_col, nulls_equal, null_policy, nan_policy)
+
+
+def unique_count(cols_or_col, nulls_equal: bool = True, null_policy: Optional[str] = None, nan_policy: Optional[str] = None) -> int:
+    """cudf::unique_count: the number of runs of consecutive equal rows.  Column form with null_policy "exclude": a null row is not
+    counted, but a row is still compared with the physically previous one ([1, null, 1] -> 2)."""
+    return _dedup_count(_lib.gx_select_unique, cols_or_col, nulls_equal, null_policy, nan_policy)
+
+
 def compare_scalar(col: Column, op: str, value) -> Column:
     """BOOL8 column of col[i] <op> value, op in eq / ne / lt / le / gt / ge (or ==, !=, <, <=, >, >=); it shares the input's validity
     (a null row stays null).  NaN compares false except under ne.  The scalar must be representable in the column's dtype."""

@@ -250,6 +250,39 @@ int gx_compare_scalar(int dtype, const void* in, const uint32_t* in_valid, int64
                       uint8_t* out_bool8, gx_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Deduplicating selectors (cudf_amd/csrc/gx_distinct.hip).  Replace the reduction over a set of row indices behind
+ * cudf::distinct / stable_distinct / distinct_indices / distinct_count (src/stream_compaction/distinct.cu,
+ * stable_distinct.cu, distinct_helpers.cu, distinct_count.cu) and the adjacent-row predicate behind cudf::unique /
+ * unique_count (src/stream_compaction/unique.cu, unique_count.cu).  Both are SELECTORS of the block above: same scratch
+ * query, same *count_dev, and the plan sits at the START of sel_tmp, so gx_compact_column / gx_compact_indices take the
+ * same pointer (whatever else a selector needs lies behind the plan).
+ * Key row = the nkeys (1..32) fixed-width columns cols_host[k] of dtypes_host[k], validity valid_ptrs_host[k] (NULL = no
+ * nulls) read from bit begin_bits_host[k] on (begin_bits_host == NULL = zeros); all three are HOST arrays.
+ * Element equality: both null and flag 1, or both valid and equal values; floats: -0.0 == +0.0, NaN == NaN (any sign,
+ * any payload) iff flag 2.  A null element's bytes are never read.  Rows are equal when all their elements are.
+ * flags: 1 nulls equal; 2 NaNs equal; 4 a NaN element counts as a null element; 8 a row holding a null key (a NaN under
+ *   flag 4 included) is not selected at all.  Without flag 1 (2) a row holding a null (a NaN) equals no row, itself
+ *   included in no class: it is always selected, under GX_KEEP_NONE as well.
+ * gx_select_unique: runs of CONSECUTIVE equal rows.  KEEP_ANY / KEEP_FIRST select the first row of a run, KEEP_LAST the
+ *   last, KEEP_NONE the runs of length 1.  Under flag 8 a row is compared with its physical neighbour all the same
+ *   ([1, null, 1] selects rows 0 and 2).
+ * gx_select_distinct: equality classes over all rows.  KEEP_FIRST selects the smallest row of a class, KEEP_LAST the
+ *   largest, KEEP_NONE the classes of one row, KEEP_ANY one row per class (whichever claimed the class's slot first).
+ *   Scratch: plan + 4 * capacity bytes of table (capacity = the power of two >= 2 n, >= 64); every keep but KEEP_ANY adds
+ *   4 n bytes of slot numbers + n / 8 of bits, KEEP_NONE another 4 * capacity: query with the `keep` of the call.
+ * Errors, before any launch: GX_EINVAL n outside [0, 2^31), nkeys outside [1, 32], keep outside gx_keep, flags outside
+ *   [0, 15], a negative begin bit, tmp_bytes == NULL, null array / column pointers with n > 0 and sel_tmp != NULL;
+ *   GX_EDTYPE an unknown dtype; GX_ETMP short scratch.  n == 0: *count_dev = 0, nothing else runs.
+ * ------------------------------------------------------------------------------------------ */
+enum gx_keep { GX_KEEP_ANY = 0, GX_KEEP_FIRST = 1, GX_KEEP_LAST = 2, GX_KEEP_NONE = 3 };
+int gx_select_unique(int nkeys, const int* dtypes_host, const void* const* cols_host, const uint32_t* const* valid_ptrs_host,
+                     const int64_t* begin_bits_host, int64_t n, int keep, int flags, int64_t* count_dev, void* sel_tmp,
+                     size_t* tmp_bytes, gx_stream_t stream);
+int gx_select_distinct(int nkeys, const int* dtypes_host, const void* const* cols_host, const uint32_t* const* valid_ptrs_host,
+                       const int64_t* begin_bits_host, int64_t n, int keep, int flags, int64_t* count_dev, void* sel_tmp,
+                       size_t* tmp_bytes, gx_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * Hashing / partitioning.
  * gx_murmur3_32: cudf::hashing::detail::MurmurHash3_x86_32<T>
  * (include/cudf/hashing/detail/murmurhash3_x86_32.cuh:22-67), null -> UINT32_MAX, and the

@@ -217,6 +217,11 @@ void gx_select_set_stages(int mask);
  * aligned output, else the direct one runs), 0 = the default choice (DESIGN.md, row filtering: the measured table). */
 void gx_compact_set_kernel(int kernel);
 
+/* TEST HOOK (process-wide) of gx_select_distinct: only the low `bits` bits of a row's hash choose its home slot.  0 (default) = the
+ * whole hash; a negative value = none of it, every row starts probing at slot 0 -- so a test can drive long probe chains through the
+ * slots of OTHER classes at small sizes. */
+void gx_distinct_set_hash_bits(int bits);
+
 #ifdef __cplusplus
 }
 #endif
