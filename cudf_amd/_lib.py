@@ -168,6 +168,15 @@ _PROTOS = {
     "gx_select_unique": (_i, [_i, ctypes.POINTER(_i), ctypes.POINTER(_p), ctypes.POINTER(_p), ctypes.POINTER(_i64), _i64, _i, _i, _p, _p, _sz, _p]),
     "gx_select_distinct": (_i, [_i, ctypes.POINTER(_i), ctypes.POINTER(_p), ctypes.POINTER(_p), ctypes.POINTER(_i64), _i64, _i, _i, _p, _p, _sz, _p]),
     "gx_distinct_set_hash_bits": (None, [_i]),
+    # merging and searching sorted rows (gx_merge.hip): two sides of key columns, one order
+    "gx_merge_tile_rows": (_i, []),
+    "gx_merge_order": (_i, [_i, ctypes.POINTER(_i), ctypes.POINTER(_p), ctypes.POINTER(_p), ctypes.POINTER(_i64), _i64,
+                            ctypes.POINTER(_p), ctypes.POINTER(_p), ctypes.POINTER(_i64), _i64, ctypes.POINTER(_i), ctypes.POINTER(_i),
+                            _p, _p, _sz, _p]),
+    "gx_gather2": (_i, [_i, _p, _p, _i64, _i64, _p, _p, _i64, _i64, _p, _i64, _p, _p, _p, _p]),
+    "gx_search_bounds": (_i, [_i, ctypes.POINTER(_i), ctypes.POINTER(_p), ctypes.POINTER(_p), ctypes.POINTER(_i64), _i64,
+                              ctypes.POINTER(_p), ctypes.POINTER(_p), ctypes.POINTER(_i64), _i64, ctypes.POINTER(_i), ctypes.POINTER(_i),
+                              _i, _p, _p]),
 }
 
 for _name, (_res, _args) in _PROTOS.items():

@@ -153,6 +153,40 @@ class DataFrame:
             order = perm if order is None else ops.gather(order, perm)
         return self._take(order)
 
+    def searchsorted(self, values, side: str = "left", ascending: Union[bool, Sequence[bool]] = True, na_position: str = "last") -> Column:
+        """cudf's DataFrame.searchsorted: the frame, sorted on ALL its columns (lexicographically, one direction per column, nulls
+        and NaNs at na_position), is the haystack; `values` -- a DataFrame or dict with the same columns, a sequence of one array /
+        Column per column, or a plain array for a frame of one column -- are the needle rows.  Returns the insertion points (INT32):
+        side="left" the first position that keeps the frame sorted (cudf::lower_bound), "right" the last (cudf::upper_bound)."""
+        if side not in ("left", "right"):
+            raise ValueError("side must be 'left' or 'right'")
+        if na_position not in ("first", "last"):
+            raise ValueError("invalid na_position")
+        names = list(self._cols)
+        if not names:
+            raise ValueError("searchsorted on a frame without columns")
+        asc = [ascending] * len(names) if isinstance(ascending, (bool, np.bool_)) else [bool(a) for a in ascending]
+        if len(asc) != len(names):
+            raise ValueError("Length of ascending must match the number of columns")
+        if isinstance(values, DataFrame):
+            values = values._cols
+        if isinstance(values, dict):
+            if list(values) != names:
+                raise ValueError("values must have the columns of the frame")
+            parts = [values[k] for k in names]
+        elif isinstance(values, Column) or (isinstance(values, np.ndarray) and values.ndim == 1):
+            parts = [values]
+        else:
+            parts = list(values)
+        if len(parts) != len(names):
+            raise ValueError("values must have one entry per column of the frame")
+        hay = [self._cols[k] for k in names]
+        needles = [p if isinstance(p, Column) else Column.from_numpy(np.asarray(p, dtype=h.dtype)) for p, h in zip(parts, hay)]
+        # NullOrder mapping of sort_values: null_before = asc ^ (na == "last")
+        null_before = [a ^ (na_position == "last") for a in asc]
+        fn = ops.lower_bound if side == "left" else ops.upper_bound
+        return fn(hay, needles, asc, null_before)
+
     def merge(self, right: "DataFrame", on: Union[str, Sequence[str]], how: str = "inner",
               suffixes=("_x", "_y")) -> "DataFrame":
         """Equi-join on one or several key columns; how in {"inner", "left", "right", "outer", "leftsemi", "leftanti"}

@@ -1223,6 +1223,134 @@ def unique_count(cols_or_col, nulls_equal: bool = True, null_policy: Optional[st
     return _dedup_count(_lib.gx_select_unique, cols_or_col, nulls_equal, null_policy, nan_policy)
 
 
+# ---- merging and searching sorted rows (cudf::merge, cudf::lower_bound / upper_bound: merge.hpp, search.hpp; gx_merge.hip).
+# The row order is the one of the multi-column sorts: one direction and one null placement per key column.
+
+def _per_key(value, k: int, what: str) -> List[bool]:
+    if isinstance(value, (bool, np.bool_)):
+        return [bool(value)] * k
+    v = [bool(x) for x in value]
+    if len(v) != k:
+        raise ValueError(f"{what}: one entry per key column")
+    return v
+
+
+def _order_args(k: int, ascending, null_before):
+    asc, nb = _per_key(ascending, k, "ascending"), _per_key(null_before, k, "null_before")
+    return (ctypes.c_int * k)(*[0 if a else 1 for a in asc]), (ctypes.c_int * k)(*[1 if b else 0 for b in nb])
+
+
+def _key_side(cols: Sequence[Column]):
+    """the host arrays of one side of key columns: data pointers, validity pointers (None = no nulls), rows"""
+    n = cols[0].size
+    for c in cols:
+        if c.size != n:
+            raise ValueError("Column size mismatch")
+    return _ptr_array([c.data_ptr for c in cols]), _ptr_array([c.mask_ptr if c.has_nulls() else None for c in cols]), n
+
+
+def _two_sides(x: Sequence[Column], y: Sequence[Column], what: str):
+    x, y = list(x), list(y)
+    if not 1 <= len(x) <= 32:
+        raise ValueError(f"{what}: 1 to 32 key columns")
+    if len(x) != len(y) or any(a.dtype != b.dtype for a, b in zip(x, y)):
+        raise TypeError(f"{what}: the column counts or types of the two tables differ")
+    return x, y, (ctypes.c_int * len(x))(*[c.gx for c in x])
+
+
+def merge_order(a_keys: Sequence[Column], b_keys: Sequence[Column], ascending=True, null_before=True) -> Column:
+    """The map of the stable merge of two sorted key tables (INT32, len(a) + len(b) entries): an entry < len(a) is a row of a, otherwise
+    len(a) + a row of b; among equivalent rows a's come first.  Both sides must be sorted under (ascending, null_before)."""
+    a, b, dts = _two_sides(a_keys, b_keys, "merge_order")
+    desc, nbf = _order_args(len(a), ascending, null_before)
+    ad, av, na = _key_side(a)
+    bd, bv, nb = _key_side(b)
+    if na + nb > 2**31 - 1:
+        raise OverflowError("the merged row count exceeds cudf::size_type")
+    out = Column.empty(np.int32, na + nb)
+    if na + nb:
+        _run(_lib.gx_merge_order, len(a), dts, ad, av, None, na, bd, bv, None, nb, desc, nbf, out.data_ptr)
+    return out
+
+
+def _gather2(a: Column, b: Column, gmap: Column, nulls: torch.Tensor, k: int) -> Column:
+    nullable = a.has_nulls() or b.has_nulls()
+    out = Column.empty(a.dtype, gmap.size, nullable=nullable)
+    L.check(_lib.gx_gather2(a.dtype.itemsize, a.data_ptr, a.mask_ptr if a.has_nulls() else None, 0, a.size, b.data_ptr,
+                            b.mask_ptr if b.has_nulls() else None, 0, b.size, gmap.data_ptr, gmap.size, out.data_ptr, out.mask_ptr,
+                            ctypes.c_void_p(nulls.data_ptr() + 8 * k), stream_ptr()), "gx_gather2")
+    return out
+
+
+def _merge_two(a: List[Column], b: List[Column], keys: Sequence[int], ascending, null_before) -> List[Column]:
+    gmap = merge_order([a[k] for k in keys], [b[k] for k in keys], ascending, null_before)
+    nulls = torch.zeros(len(a), dtype=torch.int64, device="cuda")
+    outs = [_gather2(x, y, gmap, nulls, k) for k, (x, y) in enumerate(zip(a, b))]
+    if any(o.mask is not None for o in outs):
+        host = nulls.cpu().numpy()
+        for k, o in enumerate(outs):
+            if o.mask is not None:
+                o.null_count = int(host[k])
+                if o.null_count == 0:
+                    o.mask = None
+    return outs
+
+
+def merge_sorted(tables: Sequence[Sequence[Column]], keys: Sequence[int], ascending=True, null_before=True) -> List[Column]:
+    """cudf::merge: the tables (each a list of columns, each sorted on the key columns cols[k], k in keys, under one direction and one
+    null placement per key) merged into one sorted table.  Stable: rows that compare equivalent come out by (table index, row).
+    Several tables merge as a balanced tree over NEIGHBOURING tables, which keeps that order."""
+    tables = [list(t) for t in tables]
+    if not tables:
+        return []
+    ncols = len(tables[0])
+    if ncols == 0:
+        return []
+    for t in tables:
+        if len(t) != ncols or any(x.dtype != y.dtype for x, y in zip(t, tables[0])):
+            raise TypeError("merge_sorted: the column counts or types of the tables differ")
+    if not keys:
+        raise ValueError("merge_sorted: no key columns")
+    if len(keys) > ncols:
+        raise ValueError("merge_sorted: more keys than columns")
+    _keys_of(tables[0], keys)
+    _order_args(len(keys), ascending, null_before)
+    if sum(t[0].size for t in tables if t) > 2**31 - 1:
+        raise OverflowError("the merged row count exceeds cudf::size_type")
+    level = [t for t in tables if t[0].size > 0]      # (empty tables add nothing; the others keep their relative order)
+    if len(level) <= 1:                               # a copy; like a merged column, one without nulls carries no mask
+        return [_copy_column(c) if c.has_nulls() else Column(c.data.clone(), c.dtype, c.size) for c in (level[0] if level else tables[0])]
+    while len(level) > 1:
+        nxt = [_merge_two(level[i], level[i + 1], keys, ascending, null_before) for i in range(0, len(level) - 1, 2)]
+        if len(level) % 2:
+            nxt.append(level[-1])
+        level = nxt
+    return level[0]
+
+
+def _bounds(haystack: Sequence[Column], needles: Sequence[Column], ascending, null_before, upper: bool) -> Column:
+    h, x, dts = _two_sides(haystack, needles, "upper_bound" if upper else "lower_bound")
+    desc, nbf = _order_args(len(h), ascending, null_before)
+    hd, hv, nh = _key_side(h)
+    xd, xv, nx = _key_side(x)
+    out = Column.empty(np.int32, nx)
+    if nx:
+        L.check(_lib.gx_search_bounds(len(h), dts, hd, hv, None, nh, xd, xv, None, nx, desc, nbf, int(upper), out.data_ptr, stream_ptr()),
+                "gx_search_bounds")
+    return out
+
+
+def lower_bound(haystack_cols: Sequence[Column], needle_cols: Sequence[Column], ascending=True, null_before=True) -> Column:
+    """cudf::lower_bound: for every needle row the number of haystack rows that compare strictly less (INT32): the first insertion
+    point that keeps the haystack, sorted under (ascending, null_before), sorted."""
+    return _bounds(haystack_cols, needle_cols, ascending, null_before, False)
+
+
+def upper_bound(haystack_cols: Sequence[Column], needle_cols: Sequence[Column], ascending=True, null_before=True) -> Column:
+    """cudf::upper_bound: the number of haystack rows that compare less than or equal: the last such insertion point."""
+    return _bounds(haystack_cols, needle_cols, ascending, null_before, True)
+
+
 def compare_scalar(col: Column, op: str, value) -> Column:
     """BOOL8 column of col[i] <op> value, op in eq / ne / lt / le / gt / ge (or ==, !=, <, <=, >, >=); it shares the input's validity
     (a null row stays null).  NaN compares false except under ne.  The scalar must be representable in the column's dtype."""

@@ -283,6 +283,45 @@ int gx_select_distinct(int nkeys, const int* dtypes_host, const void* const* col
                        size_t* tmp_bytes, gx_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Merging and searching sorted rows (cudf_amd/csrc/gx_merge.hip).  Replace thrust::merge over the tagged row comparator
+ * behind cudf::merge (cpp/src/merge/merge.cu) and thrust::lower_bound / upper_bound over the row comparator behind
+ * cudf::lower_bound / upper_bound (cpp/src/search/search_ordered.cu).
+ * Key rows as in the selector block: nkeys (1..32) fixed-width columns per side, HOST arrays of device pointers, validity
+ * NULL = no nulls, read from the begin bit on (begin bits NULL = zeros); both sides share dtypes_host, descending_host
+ * (NULL = all ascending) and null_before_host (NULL = nulls before, everywhere).  Row order: the lexicographic comparator of
+ * the multi-column sorts -- nulls equivalent and first iff null_before != descending, NaN == NaN greater than every number,
+ * -0.0 == +0.0; a null element's bytes are never read.
+ * gx_merge_order: A (na rows) and B (nb rows), each sorted under that order; out_map (na + nb entries) = the STABLE merge:
+ *   entry < na is a row of A, otherwise na + a row of B; among equivalent rows all of A's precede all of B's, each side in
+ *   row order.  Scratch query through tmp == NULL.  Unsorted input: an unspecified map whose entries are all inside
+ *   [0, na + nb) (without bitmaps: a permutation), and no read outside the columns.
+ * gx_gather2: out[i] = map[i] < na ? a[map[i]] : b[map[i] - na], elem_size in {1,2,4,8} (else GX_EDTYPE); out_valid
+ *   (ceil(n / 32) words, every word written) is REQUIRED when either side has a bitmap, a side without one is all valid;
+ *   *out_null_count_dev (optional, device int64) = nulls written.  A map entry outside [0, na + nb) reads nothing: a zero
+ *   element, null where there is a bitmap.
+ * gx_search_bounds: out[i] (INT32) = the number of haystack rows that compare < needle i (upper == 0: lower_bound) or
+ *   <= needle i (upper != 0: upper_bound); the haystack sorted under the same order, the needles in any order.
+ * gx_merge_tile_rows: output rows per workgroup of the merge-path tile kernel (tests size their cases from it).
+ * Errors, before any launch: GX_EINVAL negative or >= 2^31 row counts (merge, gather: the sum), nkeys outside [1, 32], no
+ *   dtypes, a negative begin bit, tmp_bytes == NULL, null array / column / output pointers where the call would launch and
+ *   the side has rows; GX_EDTYPE; GX_ETMP.  No rows to write: nothing is launched.
+ * ------------------------------------------------------------------------------------------ */
+int gx_merge_tile_rows(void);
+int gx_merge_order(int nkeys, const int* dtypes_host, const void* const* a_cols_host, const uint32_t* const* a_valid_ptrs_host,
+                   const int64_t* a_begin_bits_host, int64_t na, const void* const* b_cols_host,
+                   const uint32_t* const* b_valid_ptrs_host, const int64_t* b_begin_bits_host, int64_t nb,
+                   const int* descending_host, const int* null_before_host, int32_t* out_map, void* tmp, size_t* tmp_bytes,
+                   gx_stream_t stream);
+int gx_gather2(int elem_size, const void* a, const uint32_t* a_valid, int64_t a_begin_bit, int64_t na, const void* b,
+               const uint32_t* b_valid, int64_t b_begin_bit, int64_t nb, const int32_t* map, int64_t n, void* out,
+               uint32_t* out_valid, int64_t* out_null_count_dev, gx_stream_t stream);
+int gx_search_bounds(int nkeys, const int* dtypes_host, const void* const* hay_cols_host,
+                     const uint32_t* const* hay_valid_ptrs_host, const int64_t* hay_begin_bits_host, int64_t n_hay,
+                     const void* const* needle_cols_host, const uint32_t* const* needle_valid_ptrs_host,
+                     const int64_t* needle_begin_bits_host, int64_t n_needles, const int* descending_host,
+                     const int* null_before_host, int upper, int32_t* out, gx_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * Hashing / partitioning.
  * gx_murmur3_32: cudf::hashing::detail::MurmurHash3_x86_32<T>
  * (include/cudf/hashing/detail/murmurhash3_x86_32.cuh:22-67), null -> UINT32_MAX, and the
