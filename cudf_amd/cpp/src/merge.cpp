@@ -96,7 +96,7 @@ std::unique_ptr<table> merge(std::vector<table_view> const& tables_to_merge, std
   CUDF_EXPECTS(null_precedence.empty() || null_precedence.size() == key_cols.size(), "Mismatched size between key_cols and null_precedence");
   for (auto const& t : tables_to_merge) CUDF_EXPECTS(detail::same_types(first, t), "Mismatched column types");
   auto const keys = first.select(key_cols);  // std::out_of_range for an invalid index
-  CUDF_EXPECTS(keys.num_columns() <= detail::MAX_ORDERED_KEYS, "merge: at most 32 key columns", std::invalid_argument);
+  CUDF_EXPECTS(keys.num_columns() <= detail::MAX_KEYS, "merge: at most 32 key columns", std::invalid_argument);
   for (auto const& c : keys) detail::gx_type(c.type());  // cudf::data_type_error for a key that is no fixed-width numeric
   std::size_t total = 0;
   for (auto const& t : tables_to_merge) total += static_cast<std::size_t>(t.num_rows());

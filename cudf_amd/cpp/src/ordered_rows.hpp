@@ -1,5 +1,5 @@
-// ordered_rows.hpp -- what cudf::merge and cudf::lower_bound / upper_bound hand to gx_merge_order / gx_search_bounds: the key columns
-// of one side as the host arrays of the C ABI, and the per-key direction / null placement.
+// ordered_rows.hpp -- the key columns of one side of a call as the host arrays of the C ABI (merge, search, the selectors of the stream
+// compaction), and what cudf::merge and cudf::lower_bound / upper_bound hand over besides: the per-key direction / null placement.
 #pragma once
 #include "common.hpp"
 
@@ -10,7 +10,24 @@
 namespace cudf {
 namespace detail {
 
-constexpr size_type MAX_ORDERED_KEYS = 32;  // key columns of one call (gx.h)
+constexpr size_type MAX_KEYS = 32;  // key columns of one call (gx.h)
+
+// of a table_view or a vector of column_views: the gx dtypes (cudf::data_type_error for a type the kernels do not take) ...
+template <typename Columns>
+std::vector<int> key_dtypes(Columns const& keys)
+{
+  std::vector<int> dtypes;
+  for (auto const& c : keys) dtypes.push_back(gx_type(c.type()));
+  return dtypes;
+}
+// ... and row 0's data pointers
+template <typename Columns>
+std::vector<void const*> key_data(Columns const& keys)
+{
+  std::vector<void const*> data;
+  for (auto const& c : keys) data.push_back(row0(c));
+  return data;
+}
 
 // sliced views: row 0's data pointer, the bitmap read from the view's offset on
 struct key_side {
@@ -18,10 +35,9 @@ struct key_side {
   std::vector<uint32_t const*> valid;
   std::vector<int64_t> begin;
   int64_t rows;
-  explicit key_side(table_view const& keys) : rows{keys.num_rows()}
+  explicit key_side(table_view const& keys) : data{key_data(keys)}, rows{keys.num_rows()}
   {
     for (auto const& c : keys) {
-      data.push_back(row0(c));
       valid.push_back(c.has_nulls() ? c.null_mask() : nullptr);
       begin.push_back(c.offset());
     }
@@ -32,9 +48,9 @@ struct key_order {
   std::vector<int> dtypes, descending, null_before;
   // the caller has checked the sizes: column_order one per key, null_precedence empty (= BEFORE) or one per key
   key_order(table_view const& keys, std::vector<order> const& column_order, std::vector<null_order> const& null_precedence)
+    : dtypes{key_dtypes(keys)}
   {
     for (size_type k = 0; k < keys.num_columns(); ++k) {
-      dtypes.push_back(gx_type(keys.column(k).type()));
       descending.push_back(column_order[k] == order::DESCENDING ? 1 : 0);
       null_before.push_back(null_precedence.empty() || null_precedence[k] == null_order::BEFORE ? 1 : 0);
     }

@@ -1,6 +1,8 @@
 // row_encoding.cpp -- see row_encoding.hpp.
 #include "row_encoding.hpp"
 
+#include "ordered_rows.hpp"
+
 #include <cudf/column/column_factories.hpp>
 #include <cudf/copying.hpp>
 #include <cudf/null_mask.hpp>
@@ -34,12 +36,8 @@ std::unique_ptr<column> pack_columns(std::vector<column_view> const& cols, rmm::
   CUDF_EXPECTS(!cols.empty() && cols.size() <= 8, "pack_columns: 1 to 8 key columns");
   auto const n = cols.front().size();
   auto out     = make_numeric_column(data_type{type_id::UINT64}, n, mask_state::UNALLOCATED, stream);
-  std::vector<void const*> ptrs;
-  std::vector<int> dts;
-  for (auto const& c : cols) {
-    ptrs.push_back(row0(c));
-    dts.push_back(gx_type(c.type()));
-  }
+  auto const ptrs = key_data(cols);
+  auto const dts  = key_dtypes(cols);
   gx_check(gx_pack_keys(static_cast<int>(cols.size()), ptrs.data(), dts.data(), n,
                         out->mutable_view().data<uint64_t>(), gxs(stream)),
            "pack_keys");
@@ -51,12 +49,8 @@ std::unique_ptr<column> hash_columns(std::vector<column_view> const& cols, rmm::
   CUDF_EXPECTS(!cols.empty() && cols.size() <= 8, "hash_columns: 1 to 8 key columns");
   auto const n = cols.front().size();
   auto out     = make_numeric_column(data_type{type_id::UINT64}, n, mask_state::UNALLOCATED, stream);
-  std::vector<void const*> ptrs;
-  std::vector<int> dts;
-  for (auto const& c : cols) {
-    ptrs.push_back(row0(c));
-    dts.push_back(gx_type(c.type()));
-  }
+  auto const ptrs = key_data(cols);
+  auto const dts  = key_dtypes(cols);
   gx_check(gx_hash_rows64(static_cast<int>(cols.size()), ptrs.data(), dts.data(), n, 0, out->mutable_view().data<uint64_t>(),
                           gxs(stream)),
            "hash_rows64");
@@ -66,13 +60,8 @@ std::unique_ptr<column> hash_columns(std::vector<column_view> const& cols, rmm::
 int64_t count_row_mismatches(table_view const& left, table_view const& right, size_type const* lidx, size_type const* ridx,
                              std::size_t npairs, rmm::cuda_stream_view stream)
 {
-  std::vector<void const*> lp, rp;
-  std::vector<int> dts;
-  for (size_type k = 0; k < left.num_columns(); ++k) {
-    lp.push_back(row0(left.column(k)));
-    rp.push_back(row0(right.column(k)));
-    dts.push_back(gx_type(left.column(k).type()));
-  }
+  auto const lp = key_data(left), rp = key_data(right);
+  auto const dts = key_dtypes(left);
   rmm::device_buffer cnt{sizeof(int64_t), stream};
   gx_check(gx_rows_mismatch_count(left.num_columns(), lp.data(), rp.data(), dts.data(), lidx, ridx, static_cast<int64_t>(npairs),
                                   static_cast<int64_t*>(cnt.data()), gxs(stream)),

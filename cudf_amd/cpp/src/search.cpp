@@ -21,7 +21,7 @@ std::unique_ptr<column> search_ordered(table_view const& haystack, table_view co
   CUDF_EXPECTS(column_order.size() == static_cast<std::size_t>(haystack.num_columns()), "Mismatch between number of columns and column order.");
   CUDF_EXPECTS(null_precedence.empty() || null_precedence.size() == static_cast<std::size_t>(haystack.num_columns()),
                "Mismatch between number of columns and null_precedence size.");
-  CUDF_EXPECTS(haystack.num_columns() <= detail::MAX_ORDERED_KEYS, "search: at most 32 columns", std::invalid_argument);
+  CUDF_EXPECTS(haystack.num_columns() <= detail::MAX_KEYS, "search: at most 32 columns", std::invalid_argument);
   auto const n = needles.num_rows();
   if (n == 0 || haystack.num_columns() == 0) return make_empty_column(data_type{type_id::INT32});
   detail::key_order const ko{haystack, column_order, null_precedence};

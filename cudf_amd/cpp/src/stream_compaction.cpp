@@ -8,7 +8,7 @@
 // unique_count_tests.cpp, distinct_count_tests.cpp.
 // A selector writes the plan (selection bits + chunk starts) and the number of kept rows; that count is the one value read back
 // before the outputs are allocated, the null counts of all output columns come back in one more read behind the scatters.
-#include "common.hpp"
+#include "ordered_rows.hpp"
 
 #include <cudf/column/column_factories.hpp>
 #include <cudf/null_mask.hpp>
@@ -18,8 +18,6 @@
 
 namespace cudf {
 namespace {
-
-constexpr size_type MAX_KEYS = 32;  // key columns of one selector call (gx.h)
 
 std::unique_ptr<table> empty_like_table(table_view const& t)
 {
@@ -104,7 +102,7 @@ std::unique_ptr<table> drop_nulls(table_view const& input, std::vector<size_type
   auto const key_view = input.select(keys);  // std::out_of_range for an invalid index
   CUDF_EXPECTS(keep_threshold >= 0, "keep_threshold must not be negative", std::invalid_argument);
   if (keys.empty() || input.num_rows() == 0 || !cudf::has_nulls(key_view)) return std::make_unique<table>(input, stream, mr);
-  CUDF_EXPECTS(key_view.num_columns() <= MAX_KEYS, "drop_nulls: at most 32 key columns", std::invalid_argument);
+  CUDF_EXPECTS(key_view.num_columns() <= detail::MAX_KEYS, "drop_nulls: at most 32 key columns", std::invalid_argument);
   std::vector<uint32_t const*> valid;
   std::vector<int64_t> begin;
   for (auto const& c : key_view) {
@@ -133,21 +131,13 @@ std::unique_ptr<table> drop_nans(table_view const& input, std::vector<size_type>
   CUDF_EXPECTS(keep_threshold >= 0, "keep_threshold must not be negative", std::invalid_argument);
   if (input.num_columns() == 0 || input.num_rows() == 0 || keys.empty()) return std::make_unique<table>(input, stream, mr);
   for (auto const& c : key_view) CUDF_EXPECTS(is_floating_point(c.type()), "Key column is not of floating-point type");
-  CUDF_EXPECTS(key_view.num_columns() <= MAX_KEYS, "drop_nans: at most 32 key columns", std::invalid_argument);
-  std::vector<int> dtypes;
-  std::vector<void const*> data;
-  std::vector<uint32_t const*> valid;
-  std::vector<int64_t> begin;
-  for (auto const& c : key_view) {
-    dtypes.push_back(detail::gx_type(c.type()));
-    data.push_back(detail::row0(c));
-    valid.push_back(c.has_nulls() ? c.null_mask() : nullptr);
-    begin.push_back(c.offset());
-  }
+  CUDF_EXPECTS(key_view.num_columns() <= detail::MAX_KEYS, "drop_nans: at most 32 key columns", std::invalid_argument);
+  auto const dtypes = detail::key_dtypes(key_view);
+  detail::key_side const k{key_view};
   return select_and_compact(
     input,
     [&](int64_t* cnt, void* t, std::size_t* b) {
-      return gx_select_not_nan(static_cast<int>(dtypes.size()), dtypes.data(), data.data(), valid.data(), begin.data(), input.num_rows(),
+      return gx_select_not_nan(static_cast<int>(dtypes.size()), dtypes.data(), k.data.data(), k.valid.data(), k.begin.data(), k.rows,
                                keep_threshold, /*null_is_missing=*/0, cnt, t, b, detail::gxs(stream));
     },
     "drop_nans", stream, mr);
@@ -167,25 +157,19 @@ enum : int { F_NULLS_EQUAL = 1, F_NANS_EQUAL = 2, F_NAN_IS_NULL = 4, F_DROP_NULL
 using dedup_fn = int (*)(int, int const*, void const* const*, uint32_t const* const*, int64_t const*, int64_t, int, int, int64_t*, void*,
                          std::size_t*, gx_stream_t);
 
-// the key columns as the host arrays of the C ABI (sliced views: row 0's data pointer, the bitmap read from the view's offset on)
+// the key columns of a deduplicating selector as the host arrays of the C ABI
 struct key_arrays {
   std::vector<int> dtypes;
-  std::vector<void const*> data;
-  std::vector<uint32_t const*> valid;
-  std::vector<int64_t> begin;
-  explicit key_arrays(table_view const& keys, char const* what)
+  detail::key_side side;
+  explicit key_arrays(table_view const& keys, char const* what) : dtypes{checked_dtypes(keys, what)}, side{keys} {}
+  static std::vector<int> checked_dtypes(table_view const& keys, char const* what)
   {
-    CUDF_EXPECTS(keys.num_columns() <= MAX_KEYS, std::string{what} + ": at most 32 key columns", std::invalid_argument);
-    for (auto const& c : keys) {
-      dtypes.push_back(detail::gx_type(c.type()));
-      data.push_back(detail::row0(c));
-      valid.push_back(c.has_nulls() ? c.null_mask() : nullptr);
-      begin.push_back(c.offset());
-    }
+    CUDF_EXPECTS(keys.num_columns() <= detail::MAX_KEYS, std::string{what} + ": at most 32 key columns", std::invalid_argument);
+    return detail::key_dtypes(keys);
   }
   int call(dedup_fn fn, int64_t n, int keep, int flags, int64_t* cnt, void* t, std::size_t* b, rmm::cuda_stream_view stream) const
   {
-    return fn(static_cast<int>(dtypes.size()), dtypes.data(), data.data(), valid.data(), begin.data(), n, keep, flags, cnt, t, b,
+    return fn(static_cast<int>(dtypes.size()), dtypes.data(), side.data.data(), side.valid.data(), side.begin.data(), n, keep, flags, cnt, t, b,
               detail::gxs(stream));
   }
 };

@@ -69,32 +69,28 @@ struct MaskPred {  // BOOL8 mask at any alignment
     return mask[i] != 0 && (!valid || bit_is_set(valid, vbit0 + i));
   }
 };
-struct ValidCountPred {  // number of valid keys >= thr
-  const uint32_t* valid[MAX_KEYS];  // NULL = a column without a bitmap
-  int64_t bit0[MAX_KEYS];
-  int nkeys, thr;
+struct ValidCountPred {  // number of valid keys >= thr (the bitmaps alone: keys.col is not set)
+  rows::Cols<MAX_KEYS> keys;
+  int thr;
   __device__ __forceinline__ bool operator()(int64_t i) const
   {
     int c = 0;
-    for (int k = 0; k < nkeys; ++k) c += (!valid[k] || bit_is_set(valid[k], bit0[k] + i)) ? 1 : 0;
+    for (int k = 0; k < keys.n; ++k) c += keys.is_valid(k, i) ? 1 : 0;
     return c >= thr;
   }
 };
-struct NotNanPred {  // number of keys that are not NaN >= thr
-  const void* col[MAX_KEYS];
-  const uint32_t* valid[MAX_KEYS];
-  int64_t bit0[MAX_KEYS];
-  uint32_t is_f32, is_f64;  // bit k: the type of key k (neither: not a float, its validity alone counts)
-  int nkeys, thr, null_is_missing;
+struct NotNanPred {  // number of keys that are not NaN >= thr (a key that is no float: its validity alone counts)
+  rows::Cols<MAX_KEYS> keys;
+  int thr, null_is_missing;
   __device__ __forceinline__ bool operator()(int64_t i) const
   {
     int c = 0;
-    for (int k = 0; k < nkeys; ++k) {
-      const bool ok = !valid[k] || bit_is_set(valid[k], bit0[k] + i);
+    for (int k = 0; k < keys.n; ++k) {
+      const bool ok = keys.is_valid(k, i);
       bool nan      = false;
-      if (ok) {  // a null element is not a NaN (its bytes are not looked at)
-        if ((is_f64 >> k) & 1u) nan = (static_cast<const uint64_t*>(col[k])[i] & 0x7FFFFFFFFFFFFFFFull) > 0x7FF0000000000000ull;
-        else if ((is_f32 >> k) & 1u) nan = (static_cast<const uint32_t*>(col[k])[i] & 0x7FFFFFFFu) > 0x7F800000u;
+      if (ok && keys.kind[k] == K_FLOAT) {  // a null element is not a NaN (its bytes are not looked at)
+        if (keys.width[k] == 8) nan = rows::is_nan_bits(static_cast<const uint64_t*>(keys.col[k])[i]);
+        else nan = rows::is_nan_bits(static_cast<const uint32_t*>(keys.col[k])[i]);
       }
       c += (null_is_missing ? (ok && !nan) : !nan) ? 1 : 0;
     }
@@ -366,12 +362,12 @@ int gx_select_valid_count(int nkeys, const uint32_t* const* valid_ptrs_host, con
   int rc = 0;
   if (select_prologue(n, sel_tmp, tmp_bytes, count_dev, p, s, rc)) return rc;
   ValidCountPred pred{};
-  pred.nkeys = nkeys;
-  pred.thr   = keep_threshold;
+  pred.keys.n = nkeys;
+  pred.thr    = keep_threshold;
   for (int k = 0; k < nkeys; ++k) {
-    pred.valid[k] = valid_ptrs_host[k];
-    pred.bit0[k]  = begin_bits_host ? begin_bits_host[k] : 0;
-    if (pred.bit0[k] < 0) return GX_EINVAL;
+    pred.keys.valid[k] = valid_ptrs_host[k];
+    pred.keys.bit0[k]  = begin_bits_host ? begin_bits_host[k] : 0;
+    if (pred.keys.bit0[k] < 0) return GX_EINVAL;
   }
   return select_launch(pred, n, p, count_dev, s);
 }
@@ -384,24 +380,25 @@ int gx_select_not_nan(int nkeys, const int* dtypes_host, const void* const* cols
   if (nkeys > 0 && !dtypes_host) return GX_EINVAL;
   NotNanPred pred{};
   for (int k = 0; k < nkeys; ++k) {
-    const int dt = dtypes_host[k];
-    if (dt == GX_FLOAT32) pred.is_f32 |= 1u << k;
-    else if (dt == GX_FLOAT64) pred.is_f64 |= 1u << k;
-    else if (!null_is_missing || gx_dtype_size(dt) == 0) return GX_EDTYPE;  // only validity can make such a key missing
+    int kind, width;
+    if (rows::key_kind_width(dtypes_host[k], &kind, &width)) return GX_EDTYPE;
+    if (kind != K_FLOAT && !null_is_missing) return GX_EDTYPE;  // only validity can make such a key missing
+    pred.keys.kind[k]  = kind;
+    pred.keys.width[k] = width;
   }
   if (sel_tmp && nkeys > 0 && !cols_host) return GX_EINVAL;
   hipStream_t s = (hipStream_t)stream;
   Plan p;
   int rc = 0;
   if (select_prologue(n, sel_tmp, tmp_bytes, count_dev, p, s, rc)) return rc;
-  pred.nkeys           = nkeys;
+  pred.keys.n          = nkeys;
   pred.thr             = keep_threshold;
   pred.null_is_missing = null_is_missing ? 1 : 0;
-  for (int k = 0; k < nkeys; ++k) {
-    pred.col[k]   = cols_host[k];
-    pred.valid[k] = valid_ptrs_host ? valid_ptrs_host[k] : nullptr;
-    pred.bit0[k]  = begin_bits_host ? begin_bits_host[k] : 0;
-    if (pred.bit0[k] < 0 || (!pred.col[k] && (((pred.is_f32 | pred.is_f64) >> k) & 1u))) return GX_EINVAL;
+  for (int k = 0; k < nkeys; ++k) {  // (the data of a key that is no float is not read: it may be missing)
+    pred.keys.col[k]   = cols_host[k];
+    pred.keys.valid[k] = valid_ptrs_host ? valid_ptrs_host[k] : nullptr;
+    pred.keys.bit0[k]  = begin_bits_host ? begin_bits_host[k] : 0;
+    if (pred.keys.bit0[k] < 0 || (!pred.keys.col[k] && pred.keys.kind[k] == K_FLOAT)) return GX_EINVAL;
   }
   return select_launch(pred, n, p, count_dev, s);
 }

@@ -2,7 +2,7 @@
 // the scatters; gx_distinct.hip: the deduplicating selectors): the plan and its layout in the caller's scratch, the predicate
 // select kernel, the scan of the chunk counts behind it, the prologue of an entry point.
 #pragma once
-#include "gx_common.hpp"
+#include "gx_rows.hpp"
 #include "gx_scan.hpp"
 
 namespace gx {
@@ -10,7 +10,7 @@ namespace compact {
 
 constexpr int SEL_CHUNK = 4096;                 // rows per chunk (256 threads x 16 wave-rows of 64)
 constexpr int SEL_WORDS = SEL_CHUNK / GX_WAVE;  // ballot words per chunk
-constexpr int MAX_KEYS  = 32;                   // key columns of one selection
+using rows::MAX_KEYS;                           // key columns of one selection
 
 GX_LOCAL inline std::atomic<int> g_stages{3};  // measurement hook (gx_knobs.h): bit 0 = the select kernel runs, bit 1 = the scan
 

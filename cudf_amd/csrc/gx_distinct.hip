@@ -36,31 +36,20 @@ enum { E_VALUE = 0, E_NULL = 1, E_NAN = 2 };
 static std::atomic<int> g_hash_bits{0};  // test hook (gx_knobs.h): 0 = the whole hash, > 0 = its low bits, < 0 = none of it
 
 struct Keys {
-  const void* col[MAX_KEYS];
-  const uint32_t* valid[MAX_KEYS];  // NULL = a column without a bitmap
-  int64_t bit0[MAX_KEYS];
-  uint8_t size[MAX_KEYS];
-  uint32_t is_float;  // bit k: key k is FLOAT32 / FLOAT64
-  int nkeys, flags;
+  rows::Cols<MAX_KEYS> c;
+  int flags;
 
-  // element k of row i as (kind, bits): floats normalised (-0.0 -> +0.0, every NaN one value or, under F_NAN_IS_NULL, a null);
-  // a null element's bytes are not read
+  // element k of row i as (E_ kind, bits): the element rules of gx_rows.hpp, with a NaN told apart (it is one value, or a null under
+  // F_NAN_IS_NULL) because the flags decide what it equals
   __device__ __forceinline__ int load(int k, int64_t i, uint64_t& b) const
   {
     b = 0;
-    if (valid[k] && !bit_is_set(valid[k], bit0[k] + i)) return E_NULL;
-    const int sz = size[k];
-    switch (sz) {
-      case 1: b = static_cast<const uint8_t*>(col[k])[i]; break;
-      case 2: b = static_cast<const uint16_t*>(col[k])[i]; break;
-      case 4: b = static_cast<const uint32_t*>(col[k])[i]; break;
-      default: b = static_cast<const uint64_t*>(col[k])[i]; break;
-    }
-    if ((is_float >> k) & 1u) {
-      const uint64_t mag = sz == 4 ? (b & 0x7FFFFFFFull) : (b & 0x7FFFFFFFFFFFFFFFull);
-      const uint64_t inf = sz == 4 ? 0x7F800000ull : 0x7FF0000000000000ull;
-      if (mag == 0) b = 0;
-      else if (mag > inf) {
+    if (!c.is_valid(k, i)) return E_NULL;
+    b = c.bits(k, i);
+    if (c.kind[k] == K_FLOAT) {
+      const int w = c.width[k];
+      if (rows::is_zero_elem(b, w)) b = 0;
+      else if (rows::is_nan_elem(b, w)) {
         b = 0;
         return (flags & F_NAN_IS_NULL) ? E_NULL : E_NAN;
       }
@@ -69,7 +58,7 @@ struct Keys {
   }
   __device__ __forceinline__ bool equal(int64_t i, int64_t j) const
   {
-    for (int k = 0; k < nkeys; ++k) {
+    for (int k = 0; k < c.n; ++k) {
       uint64_t x, y;
       const int kx = load(k, i, x), ky = load(k, j, y);
       if (kx != ky || x != y) return false;
@@ -83,7 +72,7 @@ struct Keys {
   {
     uint64_t h = 0x243F6A8885A308D3ull;
     has_null = has_nan = false;
-    for (int k = 0; k < nkeys; ++k) {
+    for (int k = 0; k < c.n; ++k) {
       uint64_t b;
       const int kind = load(k, i, b);
       if (kind == E_NULL) {
@@ -93,13 +82,7 @@ struct Keys {
         has_nan = true;
         b       = 0x7FF8000000000000ull;
       }
-      uint64_t x = h + 0x9E3779B97F4A7C15ull + b;  // the fold of k_hash_rows (gx_rank.hip): fmix64 per column
-      x ^= x >> 33;
-      x *= 0xFF51AFD7ED558CCDull;
-      x ^= x >> 33;
-      x *= 0xC4CEB9FE1A85EC53ull;
-      x ^= x >> 33;
-      h = x ^ (h << 1 | h >> 63);
+      h = rows::fold_hash(h, b);
     }
     return h;
   }
@@ -113,7 +96,7 @@ struct UniquePred {
   __device__ __forceinline__ bool operator()(int64_t i) const
   {
     if (keys.flags & F_DROP_NULL_ROWS) {
-      for (int k = 0; k < keys.nkeys; ++k) {
+      for (int k = 0; k < keys.c.n; ++k) {
         uint64_t b;
         if (keys.load(k, i, b) == E_NULL) return false;
       }
@@ -240,28 +223,10 @@ static int check_args(int nkeys, const int* dtypes_host, const void* const* cols
                       const int64_t* begin_bits_host, int64_t n, int keep, int flags, const void* sel_tmp, const size_t* tmp_bytes,
                       Keys& keys)
 {
-  if (compact::check_rows(n) || !tmp_bytes || nkeys < 1 || nkeys > MAX_KEYS) return GX_EINVAL;
-  if (keep < GX_KEEP_ANY || keep > GX_KEEP_NONE || flags < 0 || flags > F_ALL || !dtypes_host) return GX_EINVAL;
-  keys       = Keys{};
-  keys.nkeys = nkeys;
+  if (compact::check_rows(n) || !tmp_bytes) return GX_EINVAL;
+  if (keep < GX_KEEP_ANY || keep > GX_KEEP_NONE || flags < 0 || flags > F_ALL) return GX_EINVAL;
   keys.flags = flags;
-  for (int k = 0; k < nkeys; ++k) {
-    const int sz = gx_dtype_size(dtypes_host[k]);
-    if (sz == 0) return GX_EDTYPE;
-    keys.size[k] = (uint8_t)sz;
-    if (dtypes_host[k] == GX_FLOAT32 || dtypes_host[k] == GX_FLOAT64) keys.is_float |= 1u << k;
-    keys.bit0[k] = begin_bits_host ? begin_bits_host[k] : 0;
-    if (keys.bit0[k] < 0) return GX_EINVAL;
-  }
-  if (sel_tmp && n > 0) {
-    if (!cols_host) return GX_EINVAL;
-    for (int k = 0; k < nkeys; ++k) {
-      if (!cols_host[k]) return GX_EINVAL;
-      keys.col[k]   = cols_host[k];
-      keys.valid[k] = valid_ptrs_host ? valid_ptrs_host[k] : nullptr;
-    }
-  }
-  return 0;
+  return rows::fill_cols(keys.c, nkeys, dtypes_host, cols_host, valid_ptrs_host, begin_bits_host, sel_tmp && n > 0);
 }
 
 static int zero_count(int64_t* count_dev, hipStream_t s)

@@ -6,7 +6,7 @@
 // gx_hash_partition_map is cudf::hash_partition (cpp/src/partitioning/partitioning.cu:568-660)
 // in index form: partition id = hash % P, rows keep their relative order -- implemented as ONE
 // stable radix pass over 1/2/4-byte partition ids with an iota payload (gx_sort_pairs).
-#include "gx_common.hpp"
+#include "gx_rows.hpp"
 
 #include <type_traits>
 
@@ -46,14 +46,7 @@ __global__ void __launch_bounds__(256) k_murmur3(const U* __restrict__ in, const
     } else {
       U v = in[i];
       if (MODE == 1) v = v ? U(1) : U(0);
-      if (MODE == 2) {
-        constexpr U SIGN = U(1) << (sizeof(U) * 8 - 1);
-        constexpr U EXP  = (sizeof(U) == 8) ? U(0x7FF0000000000000ull) : U(0x7F800000u);
-        constexpr U QNAN = (sizeof(U) == 8) ? U(0x7FF8000000000000ull) : U(0x7FC00000u);
-        const U mag      = v & U(~SIGN);
-        if (mag > EXP) v = QNAN;
-        else if (mag == 0) v = 0;
-      }
+      if (MODE == 2) v = (U)rows::normalise_float(v, (int)sizeof(U));
       h = Hasher<U>::run(v, seed);
     }
     out[i] = combine ? hash_combine32(out[i], h) : h;

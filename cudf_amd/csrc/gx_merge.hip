@@ -3,9 +3,9 @@
 // (cpp/src/merge/merge.cu) and its thrust::lower_bound / upper_bound over the row comparator (cpp/src/search/search_ordered.cu).
 //
 // Row order: the lexicographic comparator of the multi-column sorts.  Per key column an element is (placement, sortable bits):
-// sortable = to_sortable (gx_common.hpp) with the descending mask folded in, 0 for a null (whose bytes are never read);
+// sortable = rows::sortable_elem (gx_rows.hpp, where the element rules are stated) with the descending mask folded in, 0 for a null;
 // placement = 1 for a valid element and 0 for a null when nulls come first (null_before != descending), the other way round when they
-// come last.  Two rows compare column by column on that pair; NaN == NaN > every number, -0.0 == +0.0, null == null.
+// come last.  Two rows compare column by column on that pair.
 //
 // merge (gx_merge_order), no key column with a bitmap on either side -- merge path, two launches:
 //   k_mp_partition  one thread per tile: the split of its diagonal d = t * TILE, a_split[t] = the number of rows of A among the first d
@@ -30,60 +30,33 @@
 //   One key column without bitmaps: the needle's sortable form is computed once and the loop reads one haystack element per step.
 // gx_gather2: out[i] = map[i] < na ? a[map[i]] : b[map[i] - na], validity likewise (a side without a bitmap is all valid); a map entry
 //   outside [0, na + nb) reads nothing and gives a null / zero element.
-#include "gx_common.hpp"
+#include "gx_rows.hpp"
 
 namespace gx {
 namespace merge {
 
-constexpr int MAX_KEYS = 32;
 constexpr int BT       = 256;         // threads of a tile workgroup
 constexpr int ITEMS    = 8;           // outputs per thread
 constexpr int TILE     = BT * ITEMS;  // outputs per workgroup: 16 KiB of leading keys in LDS, 8 workgroups (all 32 waves) per CU
 
-// one side's key columns (sliced views: col = row 0, the bitmap read from bit0 on)
-struct Side {
-  const void* col[MAX_KEYS];
-  const uint32_t* valid[MAX_KEYS];  // NULL = no nulls
-  int64_t bit0[MAX_KEYS];
-};
-struct Meta {
-  uint8_t width[MAX_KEYS];
-  uint8_t kind[MAX_KEYS];  // KeyKind
-  uint32_t desc;           // bit k: column k descending
-  uint32_t nulls_first;    // bit k: null_before != descending
+using Side = rows::Cols<rows::MAX_KEYS>;  // one side's key columns
+struct Meta {                              // the order of the rows; the two sides of a call agree in n, width and kind
+  uint32_t desc;                           // bit k: column k descending
+  uint32_t nulls_first;                    // bit k: null_before != descending
   int nkeys;
 };
 
-// element k of row i as sortable bits (narrow types zero-extended); place: see the header.  A null's bytes are not read.
+// element k of row i as sortable bits; place: see the header.  A null's bytes are not read.
 template <bool NULLABLE>
 __device__ __forceinline__ uint64_t elem(const Side& s, const Meta& m, int k, int64_t i, uint32_t& place)
 {
   const uint32_t nf = (m.nulls_first >> k) & 1u;
   place             = nf;
-  if (NULLABLE && s.valid[k] && !bit_is_set(s.valid[k], s.bit0[k] + i)) {
+  if (NULLABLE && !s.is_valid(k, i)) {
     place = nf ^ 1u;
     return 0;
   }
-  const bool desc = (m.desc >> k) & 1u;
-  const int kind  = m.kind[k];
-  switch (m.width[k]) {
-    case 8: {
-      const uint64_t b = static_cast<const uint64_t*>(s.col[k])[i], dm = desc ? ~0ull : 0ull;
-      return kind == K_FLOAT ? to_sortable<uint64_t, K_FLOAT>(b, dm) : kind == K_SIGNED ? to_sortable<uint64_t, K_SIGNED>(b, dm) : (b ^ dm);
-    }
-    case 4: {
-      const uint32_t b = static_cast<const uint32_t*>(s.col[k])[i], dm = desc ? ~0u : 0u;
-      return kind == K_FLOAT ? to_sortable<uint32_t, K_FLOAT>(b, dm) : kind == K_SIGNED ? to_sortable<uint32_t, K_SIGNED>(b, dm) : (b ^ dm);
-    }
-    case 2: {
-      const uint16_t b = static_cast<const uint16_t*>(s.col[k])[i], dm = desc ? (uint16_t)0xFFFF : (uint16_t)0;
-      return kind == K_SIGNED ? to_sortable<uint16_t, K_SIGNED>(b, dm) : (uint16_t)(b ^ dm);
-    }
-    default: {
-      const uint8_t b = static_cast<const uint8_t*>(s.col[k])[i], dm = desc ? (uint8_t)0xFF : (uint8_t)0;
-      return kind == K_SIGNED ? to_sortable<uint8_t, K_SIGNED>(b, dm) : (uint8_t)(b ^ dm);
-    }
-  }
+  return rows::sortable_elem(s.col[k], s.width[k], s.kind[k], ((m.desc >> k) & 1u) ? ~0ull : 0ull, i);
 }
 
 // row i of x against row j of y from column k0 on: < 0, 0, > 0
@@ -297,46 +270,16 @@ __global__ void __launch_bounds__(256) k_gather2(const T* __restrict__ a, const 
 }
 
 // ---------------------------------------------------------------------------------------------- host
-static int fill_meta(int nkeys, const int* dtypes, const int* descending, const int* null_before, Meta& m)
+static Meta fill_meta(int nkeys, const int* descending, const int* null_before)
 {
-  if (nkeys < 1 || nkeys > MAX_KEYS || !dtypes) return GX_EINVAL;
-  m       = Meta{};
+  Meta m{};
   m.nkeys = nkeys;
   for (int k = 0; k < nkeys; ++k) {
-    int kind;
-    switch (dtypes[k]) {
-      case GX_INT8: case GX_INT16: case GX_INT32: case GX_INT64: kind = K_SIGNED; break;
-      case GX_UINT8: case GX_UINT16: case GX_UINT32: case GX_UINT64: case GX_BOOL8: kind = K_UNSIGNED; break;
-      case GX_FLOAT32: case GX_FLOAT64: kind = K_FLOAT; break;
-      default: return GX_EDTYPE;
-    }
-    m.kind[k]  = (uint8_t)kind;
-    m.width[k] = (uint8_t)gx_dtype_size(dtypes[k]);
     const bool desc = descending && descending[k] != 0, before = !null_before || null_before[k] != 0;
     if (desc) m.desc |= 1u << k;
     if (before != desc) m.nulls_first |= 1u << k;
   }
-  return 0;
-}
-
-// fills one side; *nullable |= a column has a bitmap.  Pointers are only demanded when the side has rows and the call will launch.
-static int fill_side(int nkeys, const void* const* cols, const uint32_t* const* valid, const int64_t* bits, int64_t rows, bool launching, Side& s,
-                     bool* nullable)
-{
-  s = Side{};
-  for (int k = 0; k < nkeys; ++k) {
-    s.bit0[k] = bits ? bits[k] : 0;
-    if (s.bit0[k] < 0) return GX_EINVAL;
-  }
-  if (!launching || rows == 0) return 0;
-  if (!cols) return GX_EINVAL;
-  for (int k = 0; k < nkeys; ++k) {
-    if (!cols[k]) return GX_EINVAL;
-    s.col[k]   = cols[k];
-    s.valid[k] = valid ? valid[k] : nullptr;
-    if (s.valid[k]) *nullable = true;
-  }
-  return 0;
+  return m;
 }
 
 struct Scratch {
@@ -378,14 +321,13 @@ int gx_merge_order(int nkeys, const int* dtypes_host, const void* const* a_cols_
                    size_t* tmp_bytes, gx_stream_t stream)
 {
   if (!tmp_bytes || na < 0 || nb < 0 || na > 0x7FFFFFFFll || nb > 0x7FFFFFFFll || na + nb > 0x7FFFFFFFll) return GX_EINVAL;
-  Meta m;
-  if (int rc = fill_meta(nkeys, dtypes_host, descending_host, null_before_host, m)) return rc;
   const int64_t n      = na + nb;
   const bool launching = tmp != nullptr && n > 0;
-  Side A, B;
-  bool nullable = false;
-  if (int rc = fill_side(nkeys, a_cols_host, a_valid_ptrs_host, a_begin_bits_host, na, launching, A, &nullable)) return rc;
-  if (int rc = fill_side(nkeys, b_cols_host, b_valid_ptrs_host, b_begin_bits_host, nb, launching, B, &nullable)) return rc;
+  Side A, B;  // pointers are only demanded when the side has rows and the call will launch
+  if (int rc = rows::fill_cols(A, nkeys, dtypes_host, a_cols_host, a_valid_ptrs_host, a_begin_bits_host, launching && na > 0)) return rc;
+  if (int rc = rows::fill_cols(B, nkeys, dtypes_host, b_cols_host, b_valid_ptrs_host, b_begin_bits_host, launching && nb > 0)) return rc;
+  const Meta m        = fill_meta(nkeys, descending_host, null_before_host);
+  const bool nullable = A.has_bitmaps() || B.has_bitmaps();
   const Scratch sc = carve(tmp, n);
   if (!tmp) {
     *tmp_bytes = sc.bytes;
@@ -418,12 +360,11 @@ int gx_search_bounds(int nkeys, const int* dtypes_host, const void* const* hay_c
                      const int* descending_host, const int* null_before_host, int upper, int32_t* out, gx_stream_t stream)
 {
   if (n_hay < 0 || n_needles < 0 || n_hay > 0x7FFFFFFFll || n_needles > 0x7FFFFFFFll) return GX_EINVAL;
-  Meta m;
-  if (int rc = fill_meta(nkeys, dtypes_host, descending_host, null_before_host, m)) return rc;
   Side H, N;
-  bool nullable = false;
-  if (int rc = fill_side(nkeys, hay_cols_host, hay_valid_ptrs_host, hay_begin_bits_host, n_hay, n_needles > 0, H, &nullable)) return rc;
-  if (int rc = fill_side(nkeys, needle_cols_host, needle_valid_ptrs_host, needle_begin_bits_host, n_needles, true, N, &nullable)) return rc;
+  if (int rc = rows::fill_cols(H, nkeys, dtypes_host, hay_cols_host, hay_valid_ptrs_host, hay_begin_bits_host, n_needles > 0 && n_hay > 0)) return rc;
+  if (int rc = rows::fill_cols(N, nkeys, dtypes_host, needle_cols_host, needle_valid_ptrs_host, needle_begin_bits_host, n_needles > 0)) return rc;
+  const Meta m        = fill_meta(nkeys, descending_host, null_before_host);
+  const bool nullable = H.has_bitmaps() || N.has_bitmaps();
   if (n_needles == 0) return 0;
   if (!out) return GX_EINVAL;
   hipStream_t s       = (hipStream_t)stream;

@@ -32,7 +32,7 @@
 // Cost per 1e9 rows: plan 0.3 + map 16 B/row + word sort 48 B/row (11-15 ms) + finish 12 B/row + the runs' gathers; descending order and
 // float64 (NaN last and equal to each other, -0.0 == 0.0: to_sortable<K_FLOAT>) go through the same sortable form, ties by row in both
 // directions (sorted_order_radix.cu:81; sort_column_impl.cuh:35-57 for the NaN / zero rule).
-#include "gx_common.hpp"
+#include "gx_rows.hpp"
 
 extern "C" size_t gx_sort_plan_bytes(void);  // gx_sort.hip: sizeof(SortPlan) -- the header at the start of a sort's scratch (status word inside)
 
@@ -350,7 +350,7 @@ __global__ void __launch_bounds__(1024) k_om_map(const uint64_t* __restrict__ ke
     for (int u = 0; u < U; ++u) {
       const int64_t i = i0 + (int64_t)u * 1024;
       if (i < n) {
-        if (KIND == K_FLOAT && (k[u] & 0x7FFFFFFFFFFFFFFFull) > 0x7FF0000000000000ull) ++nans;
+        if (KIND == K_FLOAT && rows::is_nan_bits(k[u])) ++nans;
         const uint64_t r = om_rank(s_lo, s_lut, s_meta, s_base, s_mul, gsh, to_sortable<uint64_t, KIND>(k[u], desc_mask), (uint64_t)i, invn);
         __builtin_nontemporal_store((r << ib) | (uint64_t)i, &words[i]);
       }
@@ -512,28 +512,8 @@ struct TableDesc {
   int ncols;
 };
 
-template <typename U>
-__device__ __forceinline__ uint64_t col_sortable_w(const ColDesc& c, int64_t i)
-{
-  const U b = static_cast<const U*>(c.data)[i];
-  const U m = (U)c.desc_mask;
-  if (c.kind == K_SIGNED) return (uint64_t)to_sortable<U, K_SIGNED>(b, m);
-  return (uint64_t)to_sortable<U, K_UNSIGNED>(b, m);
-}
-// the column's value in row i as a 64-bit unsigned key (narrow types zero-extended: the order is what matters)
-__device__ __forceinline__ uint64_t col_sortable(const ColDesc& c, int64_t i)
-{
-  switch (c.width) {
-    case 8:
-      if (c.kind == K_FLOAT) return to_sortable<uint64_t, K_FLOAT>(static_cast<const uint64_t*>(c.data)[i], c.desc_mask);
-      return col_sortable_w<uint64_t>(c, i);
-    case 4:
-      if (c.kind == K_FLOAT) return (uint64_t)to_sortable<uint32_t, K_FLOAT>(static_cast<const uint32_t*>(c.data)[i], (uint32_t)c.desc_mask);
-      return col_sortable_w<uint32_t>(c, i);
-    case 2: return col_sortable_w<uint16_t>(c, i);
-    default: return col_sortable_w<uint8_t>(c, i);
-  }
-}
+// the column's value in row i as a 64-bit unsigned key: the element the merge and search comparators see (gx_rows.hpp)
+__device__ __forceinline__ uint64_t col_sortable(const ColDesc& c, int64_t i) { return rows::sortable_elem(c.data, c.width, c.kind, c.desc_mask, i); }
 
 __global__ void __launch_bounds__(256) k_omt_sample(ColDesc c, int64_t n, uint64_t* __restrict__ samp)
 {
@@ -1009,19 +989,7 @@ static int sorted_order_words(const void* keys, int64_t n, int descending, int32
 static int col_desc(int dtype, const void* data, int descending, ColDesc& c)
 {
   c.data = data;
-  switch (dtype) {
-    case GX_INT8: c.kind = K_SIGNED; c.width = 1; break;
-    case GX_INT16: c.kind = K_SIGNED; c.width = 2; break;
-    case GX_INT32: c.kind = K_SIGNED; c.width = 4; break;
-    case GX_INT64: c.kind = K_SIGNED; c.width = 8; break;
-    case GX_UINT8: case GX_BOOL8: c.kind = K_UNSIGNED; c.width = 1; break;
-    case GX_UINT16: c.kind = K_UNSIGNED; c.width = 2; break;
-    case GX_UINT32: c.kind = K_UNSIGNED; c.width = 4; break;
-    case GX_UINT64: c.kind = K_UNSIGNED; c.width = 8; break;
-    case GX_FLOAT32: c.kind = K_FLOAT; c.width = 4; break;
-    case GX_FLOAT64: c.kind = K_FLOAT; c.width = 8; break;
-    default: return GX_EDTYPE;
-  }
+  if (int rc = rows::key_kind_width(dtype, &c.kind, &c.width)) return rc;
   c.desc_mask = descending ? (c.width == 8 ? ~0ull : ((1ull << (8 * c.width)) - 1)) : 0ull;
   return 0;
 }

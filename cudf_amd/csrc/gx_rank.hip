@@ -13,55 +13,25 @@
 //                       (id, id) pairs again -- cudf's own key_remapping (include/cudf/join/
 //                       key_remapping.hpp) serves the same purpose.  Built on the radix sort:
 //                       sorted_order -> adjacent-difference flags -> scan -> scatter.
-#include "gx_common.hpp"
-
-#include <cstring>
+#include "gx_rows.hpp"
 
 namespace gx {
 namespace rank {
 
-struct PackCols {
-  const void* p[8];
-  int size[8];
-  int is_float[8];
-  int shift[8];
-  int ncols;
+constexpr int MAX_COLS = 8;
+using Cols = rows::Cols<MAX_COLS>;  // (these calls take no bitmaps: the caller ANDs the columns' validity itself)
+using rows::normalise_float;
+
+struct Shifts {
+  int s[MAX_COLS];  // column k of a packed key sits at bits [s[k], s[k] + 8 width_k)
 };
 
-__device__ __forceinline__ uint64_t load_bits(const void* p, int size, int64_t i)
-{
-  switch (size) {
-    case 1: return static_cast<const uint8_t*>(p)[i];
-    case 2: return static_cast<const uint16_t*>(p)[i];
-    case 4: return static_cast<const uint32_t*>(p)[i];
-    default: return static_cast<const uint64_t*>(p)[i];
-  }
-}
-
-// equality classes of the row comparator for floats: one zero, one NaN
-__device__ __forceinline__ uint64_t normalise_float(uint64_t b, int size)
-{
-  if (size == 4) {
-    const uint32_t x = (uint32_t)b;
-    if ((x & 0x7FFFFFFFu) == 0) return 0;
-    if ((x & 0x7FFFFFFFu) > 0x7F800000u) return 0x7FC00000u;
-    return x;
-  }
-  if ((b & 0x7FFFFFFFFFFFFFFFull) == 0) return 0;
-  if ((b & 0x7FFFFFFFFFFFFFFFull) > 0x7FF0000000000000ull) return 0x7FF8000000000000ull;
-  return b;
-}
-
-__global__ void __launch_bounds__(256) k_pack(PackCols c, int64_t n, uint64_t* __restrict__ out)
+__global__ void __launch_bounds__(256) k_pack(Cols c, Shifts sh, int64_t n, uint64_t* __restrict__ out)
 {
   const int64_t stride = (int64_t)gridDim.x * 256;
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += stride) {
     uint64_t v = 0;
-    for (int k = 0; k < c.ncols; ++k) {
-      uint64_t b = load_bits(c.p[k], c.size[k], i);
-      if (c.is_float[k]) b = normalise_float(b, c.size[k]);
-      v |= b << c.shift[k];
-    }
+    for (int k = 0; k < c.n; ++k) v |= c.normalised(k, i) << sh.s[k];
     out[i] = v;
   }
 }
@@ -125,25 +95,20 @@ static inline unsigned grid_for(int64_t n)
 }
 
 
-// inverse of k_pack: column k of row i = bits [shift_k, shift_k + 8 size_k) of packed[i]
-struct UnpackCols {
-  void* p[8];
-  int size[8];
-  int shift[8];
-  int ncols;
-};
-__global__ void __launch_bounds__(256) k_unpack(UnpackCols c, int64_t n, const uint64_t* __restrict__ packed)
+// inverse of k_pack: column k of row i = bits [shift_k, shift_k + 8 width_k) of packed[i]; c.col are the OUTPUT columns
+__global__ void __launch_bounds__(256) k_unpack(Cols c, Shifts sh, int64_t n, const uint64_t* __restrict__ packed)
 {
   const int64_t stride = (int64_t)gridDim.x * 256;
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += stride) {
     const uint64_t v = packed[i];
-    for (int k = 0; k < c.ncols; ++k) {
-      const uint64_t b = v >> c.shift[k];
-      switch (c.size[k]) {
-        case 1: static_cast<uint8_t*>(c.p[k])[i] = (uint8_t)b; break;
-        case 2: static_cast<uint16_t*>(c.p[k])[i] = (uint16_t)b; break;
-        case 4: static_cast<uint32_t*>(c.p[k])[i] = (uint32_t)b; break;
-        default: static_cast<uint64_t*>(c.p[k])[i] = b; break;
+    for (int k = 0; k < c.n; ++k) {
+      const uint64_t b = v >> sh.s[k];
+      void* p          = const_cast<void*>(c.col[k]);
+      switch (c.width[k]) {
+        case 1: static_cast<uint8_t*>(p)[i] = (uint8_t)b; break;
+        case 2: static_cast<uint16_t*>(p)[i] = (uint16_t)b; break;
+        case 4: static_cast<uint32_t*>(p)[i] = (uint32_t)b; break;
+        default: static_cast<uint64_t*>(p)[i] = b; break;
       }
     }
   }
@@ -154,30 +119,17 @@ __global__ void __launch_bounds__(256) k_unpack(UnpackCols c, int64_t n, const u
 // is exact, and the caller falls back to the dense-rank encoding in the (2^-64 per pair) case of a collision.
 // One pass over the key columns instead of one radix sort per column; the reference hashes the row once as well
 // (cpp/include/cudf/detail/row_operator/primitive_row_operators.cuh:247-268) and compares on every probe (:95-163).
-__device__ __forceinline__ uint64_t fmix64(uint64_t x)
-{
-  x ^= x >> 33;
-  x *= 0xFF51AFD7ED558CCDull;
-  x ^= x >> 33;
-  x *= 0xC4CEB9FE1A85EC53ull;
-  x ^= x >> 33;
-  return x;
-}
-__global__ void __launch_bounds__(256) k_hash_rows(PackCols c, int64_t n, uint64_t seed, uint64_t* __restrict__ out)
+__global__ void __launch_bounds__(256) k_hash_rows(Cols c, int64_t n, uint64_t seed, uint64_t* __restrict__ out)
 {
   const int64_t stride = (int64_t)gridDim.x * 256;
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += stride) {
     uint64_t h = seed;
-    for (int k = 0; k < c.ncols; ++k) {
-      uint64_t b = load_bits(c.p[k], c.size[k], i);
-      if (c.is_float[k]) b = normalise_float(b, c.size[k]);
-      h = fmix64(h + 0x9E3779B97F4A7C15ull + b) ^ (h << 1 | h >> 63);
-    }
+    for (int k = 0; k < c.n; ++k) h = rows::fold_hash(h, c.normalised(k, i));
     out[i] = h;
   }
 }
 // pairs (lidx[i], ridx[i]) -- NULL = row i itself; a negative index = no row, skipped -- whose rows differ in a column
-__global__ void __launch_bounds__(256) k_rows_mismatch(PackCols l, PackCols r, const int32_t* __restrict__ lidx,
+__global__ void __launch_bounds__(256) k_rows_mismatch(Cols l, Cols r, const int32_t* __restrict__ lidx,
                                                        const int32_t* __restrict__ ridx, int64_t npairs, unsigned long long* count)
 {
   const int64_t stride = (int64_t)gridDim.x * 256;
@@ -186,32 +138,25 @@ __global__ void __launch_bounds__(256) k_rows_mismatch(PackCols l, PackCols r, c
     const int64_t a = lidx ? (int64_t)lidx[i] : i, b = ridx ? (int64_t)ridx[i] : i;
     if (a < 0 || b < 0) continue;
     bool diff = false;
-    for (int k = 0; k < l.ncols; ++k) {
-      uint64_t x = load_bits(l.p[k], l.size[k], a), y = load_bits(r.p[k], r.size[k], b);
-      if (l.is_float[k]) {
-        x = normalise_float(x, l.size[k]);
-        y = normalise_float(y, l.size[k]);
-      }
-      diff = diff || x != y;
-    }
+    for (int k = 0; k < l.n; ++k) diff = diff || l.normalised(k, a) != r.normalised(k, b);
     bad += diff ? 1ull : 0ull;
   }
   bad = wave_reduce(bad, SumOp());
   if (lane_id() == 0 && bad) atomicAdd(count, bad);
 }
-static inline int fill_cols(PackCols& c, int ncols, const void* const* cols, const int* dtypes, int64_t n)
+static inline int fill_cols(Cols& c, int ncols, const void* const* cols, const int* dtypes, int64_t n)
 {
-  std::memset(&c, 0, sizeof(c));
-  for (int k = 0; k < ncols; ++k) {
-    const int sz = gx_dtype_size(dtypes[k]);
-    if (sz <= 0) return GX_EDTYPE;
-    if (n > 0 && !cols[k]) return GX_EINVAL;
-    c.p[k]        = cols[k];
-    c.size[k]     = sz;
-    c.is_float[k] = dtypes[k] == GX_FLOAT32 || dtypes[k] == GX_FLOAT64;
+  return rows::fill_cols(c, ncols, dtypes, cols, nullptr, nullptr, n > 0);
+}
+// the layout of a packed key: first column in the most significant position
+static inline int fill_shifts(const Cols& c, Shifts& sh)
+{
+  int bits = 0;
+  for (int k = c.n - 1; k >= 0; --k) {
+    sh.s[k] = bits;
+    bits += c.width[k] * 8;
   }
-  c.ncols = ncols;
-  return 0;
+  return bits > 64 ? GX_EINVAL : 0;
 }
 
 }  // namespace rank
@@ -222,23 +167,12 @@ extern "C" {
 int gx_pack_keys(int ncols, const void* const* cols, const int* dtypes, int64_t n, uint64_t* out, gx_stream_t s)
 {
   if (ncols < 1 || ncols > 8 || !cols || !dtypes || n < 0 || (n > 0 && !out)) return GX_EINVAL;
-  gx::rank::PackCols c;
-  std::memset(&c, 0, sizeof(c));
-  int bits = 0;
-  for (int k = ncols - 1; k >= 0; --k) {  // first column in the most significant position
-    const int sz = gx_dtype_size(dtypes[k]);
-    if (sz <= 0) return GX_EDTYPE;
-    if (n > 0 && !cols[k]) return GX_EINVAL;
-    c.p[k]        = cols[k];
-    c.size[k]     = sz;
-    c.is_float[k] = dtypes[k] == GX_FLOAT32 || dtypes[k] == GX_FLOAT64;
-    c.shift[k]    = bits;
-    bits += sz * 8;
-  }
-  if (bits > 64) return GX_EINVAL;
-  c.ncols = ncols;
+  gx::rank::Cols c;
+  gx::rank::Shifts sh{};
+  if (int rc = gx::rank::fill_cols(c, ncols, cols, dtypes, n)) return rc;
+  if (int rc = gx::rank::fill_shifts(c, sh)) return rc;
   if (n == 0) return 0;
-  hipLaunchKernelGGL(gx::rank::k_pack, dim3(gx::rank::grid_for(n)), dim3(256), 0, s, c, n, out);
+  hipLaunchKernelGGL(gx::rank::k_pack, dim3(gx::rank::grid_for(n)), dim3(256), 0, s, c, sh, n, out);
   GX_LAUNCH_CHECK();
   return 0;
 }
@@ -246,22 +180,12 @@ int gx_pack_keys(int ncols, const void* const* cols, const int* dtypes, int64_t 
 int gx_unpack_keys(int ncols, void* const* out_cols, const int* dtypes, int64_t n, const uint64_t* packed, gx_stream_t s)
 {
   if (ncols < 1 || ncols > 8 || !out_cols || !dtypes || n < 0 || (n > 0 && !packed)) return GX_EINVAL;
-  gx::rank::UnpackCols c;
-  std::memset(&c, 0, sizeof(c));
-  int bits = 0;
-  for (int k = ncols - 1; k >= 0; --k) {  // the layout of gx_pack_keys: first column most significant
-    const int sz = gx_dtype_size(dtypes[k]);
-    if (sz <= 0) return GX_EDTYPE;
-    if (n > 0 && !out_cols[k]) return GX_EINVAL;
-    c.p[k]     = out_cols[k];
-    c.size[k]  = sz;
-    c.shift[k] = bits;
-    bits += sz * 8;
-  }
-  if (bits > 64) return GX_EINVAL;
-  c.ncols = ncols;
+  gx::rank::Cols c;
+  gx::rank::Shifts sh{};
+  if (int rc = gx::rank::fill_cols(c, ncols, out_cols, dtypes, n)) return rc;
+  if (int rc = gx::rank::fill_shifts(c, sh)) return rc;
   if (n == 0) return 0;
-  hipLaunchKernelGGL(gx::rank::k_unpack, dim3(gx::rank::grid_for(n)), dim3(256), 0, s, c, n, packed);
+  hipLaunchKernelGGL(gx::rank::k_unpack, dim3(gx::rank::grid_for(n)), dim3(256), 0, s, c, sh, n, packed);
   GX_LAUNCH_CHECK();
   return 0;
 }
@@ -269,7 +193,7 @@ int gx_unpack_keys(int ncols, void* const* out_cols, const int* dtypes, int64_t 
 int gx_hash_rows64(int ncols, const void* const* cols, const int* dtypes, int64_t n, uint64_t seed, uint64_t* out, gx_stream_t s)
 {
   if (ncols < 1 || ncols > 8 || !cols || !dtypes || n < 0 || (n > 0 && !out)) return GX_EINVAL;
-  gx::rank::PackCols c;
+  gx::rank::Cols c;
   if (int rc = gx::rank::fill_cols(c, ncols, cols, dtypes, n)) return rc;
   if (n == 0) return 0;
   hipLaunchKernelGGL(gx::rank::k_hash_rows, dim3(gx::rank::grid_for(n)), dim3(256), 0, s, c, n, seed, out);
@@ -281,7 +205,7 @@ int gx_rows_mismatch_count(int ncols, const void* const* lcols, const void* cons
                            const int32_t* ridx, int64_t npairs, int64_t* mismatch_dev, gx_stream_t s)
 {
   if (ncols < 1 || ncols > 8 || !lcols || !rcols || !dtypes || npairs < 0 || !mismatch_dev) return GX_EINVAL;
-  gx::rank::PackCols l, r;
+  gx::rank::Cols l, r;
   if (int rc = gx::rank::fill_cols(l, ncols, lcols, dtypes, npairs)) return rc;
   if (int rc = gx::rank::fill_cols(r, ncols, rcols, dtypes, npairs)) return rc;
   GX_HIP_TRY(hipMemsetAsync(mismatch_dev, 0, sizeof(int64_t), s));

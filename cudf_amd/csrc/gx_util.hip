@@ -61,22 +61,6 @@ __global__ void __launch_bounds__(256) k_sequence_i32(int32_t* out, int64_t n, i
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) out[i] = start + (int32_t)i;
 }
 
-// total order used by the sortedness check (same rule as gx_sort's to_sortable, ascending)
-template <typename U, int KIND>
-__device__ __forceinline__ U sortable(U bits)
-{
-  constexpr U SIGN = U(1) << (sizeof(U) * 8 - 1);
-  if (KIND == 1) return bits ^ SIGN;
-  if (KIND == 2) {
-    constexpr U EXP = (sizeof(U) == 8) ? U(0x7FF0000000000000ull) : U(0x7F800000u);
-    const U mag     = bits & U(~SIGN);
-    if (mag > EXP) return U(~U(0));
-    if (mag == 0) bits = 0;
-    return bits ^ ((bits & SIGN) ? U(~U(0)) : SIGN);
-  }
-  return bits;
-}
-
 template <typename U, int KIND>
 __global__ void __launch_bounds__(256) k_checksum(const U* in, int64_t n, int descending, unsigned long long* res)
 {
@@ -88,7 +72,7 @@ __global__ void __launch_bounds__(256) k_checksum(const U* in, int64_t n, int de
     sum += h;
     x ^= h;
     if (i + 1 < n) {
-      const U a = sortable<U, KIND>(v), b = sortable<U, KIND>(in[i + 1]);
+      const U a = to_sortable<U, KIND>(v, U(0)), b = to_sortable<U, KIND>(in[i + 1], U(0));  // the sort's own total order, ascending
       if (descending ? (a < b) : (b < a)) ++bad;
     }
   }
