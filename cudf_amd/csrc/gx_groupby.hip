@@ -1,4 +1,5 @@
-// gx_groupby.hip -- hash groupby SUM / COUNT for gfx950 (single int32/int64 key column).
+// gx_groupby.hip -- hash groupby SUM / COUNT and MIN / MAX for gfx950 (single int32/int64 key column): one path, written
+// against an aggregator policy (SumCount / MinMax below).
 //
 // Replaces cudf's hash groupby core (cpp/src/groupby/hash/compute_groupby.cu:50-155,
 // compute_global_memory_aggs.cuh:123-157, single_pass_functors.cuh:85-157): the reference
@@ -70,47 +71,261 @@ __device__ __forceinline__ int64_t find_or_insert(unsigned long long* table, uin
   return -1;
 }
 
+// The compensated add, once: sum[i] += x with a RETURNING f64 atomic, the rounding error of that addition (two_sum) to comp[i].
+// `carried` is the compensation a partial sum brings along when it is merged (finite: no NaN ever enters a comp word); its default
+// -0.0 is the identity of IEEE addition, so a plain row pays no extra add.  Inlined per call site: `sum` / `comp` are LDS arrays at
+// some sites and global arrays at others, and the address space has to stay known at each (ds_add_rtn_f64 / global_atomic_add_f64).
+__device__ __forceinline__ void comp_add(double* sum, double* comp, int64_t i, double x, double carried = -0.0)
+{
+  const double old = atomicAdd(&sum[i], x);  // returning add: old is what this x was added to
+  const double s   = old + x;                // the value the atomic unit stored (RN)
+  const double bb  = s - old;
+  const double err = ((old - (s - bb)) + (x - bb)) + carried;
+  // ordered compare: when old or x is +-inf or s overflows, bb is inf - inf and err is NaN -- skip it, so that sum[i] alone
+  // carries the +-inf / NaN that plain addition gives and comp[i] stays finite
+  if (err < 0.0 || err > 0.0) atomicAdd(&comp[i], err);
+}
+
+// one value into a SUM accumulator (LDS or global): floats compensated, integers as 64-bit wrapping words in the same array
 template <typename V, bool IS_FLOAT>
-struct Acc;
-template <typename V>
-struct Acc<V, true> {
-  static __device__ __forceinline__ void add(double* sum, double* comp, int64_t g, V v)
-  {
-    const double x   = (double)v;
-    const double old = atomicAdd(&sum[g], x);  // returning add: old is what this x was added to
-    const double s   = old + x;                // the value the atomic unit stored (RN)
-    const double bb  = s - old;
-    const double err = (old - (s - bb)) + (x - bb);
-    // ordered compare: when old or x is +-inf or s overflows, bb is inf - inf and err is NaN -- skip it, so that sum[g] alone
-    // carries the +-inf / NaN that plain addition gives and comp[g] stays finite
-    if (err < 0.0 || err > 0.0) atomicAdd(&comp[g], err);
+__device__ __forceinline__ void sum_add(double* sum, double* comp, int64_t i, V v)
+{
+  if constexpr (IS_FLOAT) comp_add(sum, comp, i, (double)v);
+  else atomicAdd(reinterpret_cast<unsigned long long*>(sum) + i, (unsigned long long)(long long)v);
+}
+
+// merge one partially aggregated group into the global accumulators
+template <bool IS_FLOAT>
+__device__ __forceinline__ void global_merge(double* sum, double* comp, int64_t g, double psum, double pcomp)
+{
+  if constexpr (IS_FLOAT) {
+    comp_add(sum, comp, g, psum, pcomp);
+  } else {
+    unsigned long long u;
+    __builtin_memcpy(&u, &psum, 8);
+    atomicAdd(reinterpret_cast<unsigned long long*>(sum) + g, u);
   }
-};
+}
+
+// MIN / MAX (cpp/src/groupby/hash/global_memory_aggregator.cuh:18-238: atomic min/max per group).  Values are widened to a 64-bit
+// word whose unsigned order is the value order (sign flip for signed integers, the IEEE total-order flip for floats with
+// -0.0 -> +0.0 and every NaN above +Inf, the row comparator's order: include/cudf/detail/row_operator/common_utils.cuh:157-169),
+// so one native 64-bit unsigned atomic min / max per row serves every value type.
 template <typename V>
-struct Acc<V, false> {
-  static __device__ __forceinline__ void add(double* sum, double*, int64_t g, V v)
+__device__ __forceinline__ unsigned long long mm_encode(V v)
+{
+  if constexpr (sizeof(V) == 8 && !std::is_integral<V>::value) {
+    unsigned long long b;
+    __builtin_memcpy(&b, &v, 8);
+    return to_sortable<unsigned long long, K_FLOAT>(b, 0ull);
+  } else if constexpr (!std::is_integral<V>::value) {
+    const double d = (double)v;  // float -> double is exact and order preserving
+    unsigned long long b;
+    __builtin_memcpy(&b, &d, 8);
+    return to_sortable<unsigned long long, K_FLOAT>(b, 0ull);
+  } else if constexpr (std::is_signed<V>::value) {
+    return (unsigned long long)(long long)v ^ 0x8000000000000000ull;
+  } else {
+    return (unsigned long long)v;
+  }
+}
+template <typename V>
+__device__ __forceinline__ V mm_decode(unsigned long long s)
+{
+  if constexpr (!std::is_integral<V>::value) {
+    const unsigned long long b = (s & 0x8000000000000000ull) ? (s ^ 0x8000000000000000ull) : ~s;
+    double d;
+    __builtin_memcpy(&d, &b, 8);
+    return (V)d;
+  } else if constexpr (std::is_signed<V>::value) {
+    return (V)(long long)(s ^ 0x8000000000000000ull);
+  } else {
+    return (V)s;
+  }
+}
+
+// ------------------------------------------------------------------------------------------------
+// The two aggregates of the single-key path.  Everything below -- the global-table row kernel, the LDS fold of the partitioned
+// path, the compact kernel, the launch sequence, the scratch layout -- exists once and is written against one of these policies;
+// a policy holds only what differs: its accumulators (global: a bundle of pointers passed by value; LDS: carved from the two
+// accumulator regions of a table of n = S + 1 slots), what one row and one merged group do to them, and what a group emits.
+//   Global / Out      accumulator and output bundles          carve / ones / select   scratch order, the 0xFF block, unused outputs
+//   lds / reset       the LDS accumulators of one table       lds_row / global_row    one row into an LDS slot / a global group
+//   merge             LDS slot i into global group g          emit                    group i to output position p
+//   vec_rows          the four-rows-per-lane loader of k_part_fold (4-byte keys, speculative pass, nsplit == 1)
+//   dense             direct addressing for dense ids and per-call partition bits (PartPlan::dense / pbits)
+// ------------------------------------------------------------------------------------------------
+struct SumGlobal { double* sum; double* comp; uint32_t* cnt_valid; uint32_t* cnt_all; };
+struct SumOut { void* sum; int32_t* cv; int32_t* ca; };
+struct MinMaxGlobal { unsigned long long* mn; unsigned long long* mx; uint32_t* cnt_valid; };
+struct MinMaxOut { void* mn; void* mx; int32_t* cv; };
+
+template <typename V, bool IS_FLOAT, bool HAS_VV>
+struct SumCount {
+  typedef SumGlobal Global;
+  typedef SumOut Out;
+  typedef SumCount<V, IS_FLOAT, true> WithNulls;
+  static constexpr bool has_vv          = HAS_VV;
+  static constexpr bool vec_rows        = sizeof(V) == 8 && !HAS_VV;
+  static constexpr bool dense           = true;
+  static constexpr bool values_optional = true;  // COUNT alone passes no values (and stays on the global table)
+  static constexpr int bytes8 = 16, bytes4 = HAS_VV ? 8 : 4;  // per LDS slot: sum, compensation; count_valid (+ count_all)
+  struct Lds { double* sum; double* comp; uint32_t* cv; uint32_t* ca; };
+
+  static Global carve(Carver& c, uint64_t cap)
   {
-    atomicAdd(reinterpret_cast<unsigned long long*>(sum) + g, (unsigned long long)(long long)v);
+    Global g;
+    g.sum       = c.take<double>(cap + 1);
+    g.comp      = c.take<double>(cap + 1);
+    g.cnt_valid = c.take<uint32_t>(cap + 1);
+    g.cnt_all   = c.take<uint32_t>(cap + 1);
+    return g;
+  }
+  static void* ones(const Global&) { return nullptr; }                  // every accumulator starts at zero
+  static bool carve_flags(bool has_nulls) { return has_nulls; }
+  static void select(Global& g, const Out& o) { if (!o.ca) g.cnt_all = nullptr; }  // COUNT_ALL is kept only on request
+
+  static __device__ __forceinline__ Lds lds(char* w8, char* w4, int n)
+  {
+    return Lds{reinterpret_cast<double*>(w8), reinterpret_cast<double*>(w8) + n, reinterpret_cast<uint32_t*>(w4), reinterpret_cast<uint32_t*>(w4) + n};
+  }
+  static __device__ __forceinline__ void reset(const Lds& l, int i)
+  {
+    l.sum[i]  = 0.0;
+    l.comp[i] = 0.0;
+    l.cv[i]   = 0;
+    if (HAS_VV) l.ca[i] = 0;
+  }
+  static __device__ __forceinline__ void lds_row(const Lds& l, int slot, V val, uint8_t fl)
+  {
+    // (workgroup scope: an ordinary atomicAdd here is merged with the one on the global counters of global_row into ONE
+    //  flat_atomic_add through a selected pointer -- every row then pays a FLAT access, and a pending FLAT access makes the compiler
+    //  wait with vmcnt(0) lgkmcnt(0) for everything)
+    if (HAS_VV) __hip_atomic_fetch_add(&l.ca[slot], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    if (fl) {
+      sum_add<V, IS_FLOAT>(l.sum, l.comp, slot, val);
+      __hip_atomic_fetch_add(&l.cv[slot], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    }
+  }
+  static __device__ __forceinline__ void global_row(const Global& a, int64_t g, V val, bool fl)
+  {
+    if (a.cnt_all) atomicAdd(&a.cnt_all[g], 1u);
+    if (fl) {
+      sum_add<V, IS_FLOAT>(a.sum, a.comp, g, val);
+      atomicAdd(&a.cnt_valid[g], 1u);
+    }
+  }
+  static __device__ __forceinline__ void merge(const Lds& l, int i, const Global& a, int64_t g)
+  {
+    const uint32_t cv = l.cv[i];
+    if (a.cnt_all) atomicAdd(&a.cnt_all[g], HAS_VV ? l.ca[i] : cv);
+    if (cv) {
+      atomicAdd(&a.cnt_valid[g], cv);
+      global_merge<IS_FLOAT>(a.sum, a.comp, g, l.sum[i], l.comp[i]);
+    }
+  }
+  static __device__ __forceinline__ void emit(const Global& a, int64_t i, int64_t p, const Out& o)
+  {
+    if (o.sum) {
+      if (IS_FLOAT) {
+        const double r = a.sum[i] + a.comp[i];
+        if (sizeof(V) == 4) static_cast<float*>(o.sum)[p] = (float)r; else static_cast<double*>(o.sum)[p] = r;
+      } else {
+        static_cast<long long*>(o.sum)[p] = reinterpret_cast<const long long*>(a.sum)[i];
+      }
+    }
+    if (o.cv) o.cv[p] = (int32_t)a.cnt_valid[i];
+    if (o.ca) o.ca[p] = (int32_t)a.cnt_all[i];
   }
 };
 
-template <typename K, typename V, bool IS_FLOAT>
+template <typename V, bool HAS_VV>
+struct MinMax {
+  typedef MinMaxGlobal Global;
+  typedef MinMaxOut Out;
+  typedef MinMax<V, true> WithNulls;
+  static constexpr bool has_vv          = HAS_VV;
+  static constexpr bool vec_rows        = false;  // (turning either on is a change of speed, not of structure)
+  static constexpr bool dense           = false;
+  static constexpr bool values_optional = false;
+  static constexpr int bytes8 = 16, bytes4 = 4;  // per LDS slot: min, max; count_valid
+  struct Lds { unsigned long long* mn; unsigned long long* mx; uint32_t* cv; };
+
+  static Global carve(Carver& c, uint64_t cap)
+  {
+    Global g;
+    g.cnt_valid = c.take<uint32_t>(cap + 1);
+    g.mx        = c.take<unsigned long long>(cap + 1);  // zero-initialised with the block above
+    g.mn        = c.take<unsigned long long>(cap + 1);  // all-ones
+    return g;
+  }
+  static void* ones(const Global& g) { return g.mn; }
+  static bool carve_flags(bool) { return true; }  // (the flag array is carved with or without value nulls: callers size their scratch by it)
+  static void select(Global&, const Out&) {}
+
+  static __device__ __forceinline__ Lds lds(char* w8, char* w4, int n)
+  {
+    return Lds{reinterpret_cast<unsigned long long*>(w8), reinterpret_cast<unsigned long long*>(w8) + n, reinterpret_cast<uint32_t*>(w4)};
+  }
+  static __device__ __forceinline__ void reset(const Lds& l, int i)
+  {
+    l.mn[i] = ~0ull;
+    l.mx[i] = 0ull;
+    l.cv[i] = 0;
+  }
+  static __device__ __forceinline__ void lds_row(const Lds& l, int slot, V val, uint8_t fl)
+  {
+    const unsigned long long e = mm_encode<V>(val);
+    // (workgroup scope, as in SumCount::lds_row and for the same reason: lds_row and global_row are the same three atomics, and
+    //  written alike the compiler sinks them into ONE flat_atomic_umin / umax / add through a selected pointer.  The instructions
+    //  are the ds_min_u64 / ds_max_u64 / ds_add_u32 that agent scope gives on LDS.)
+    if (fl) {
+      __hip_atomic_fetch_min(&l.mn[slot], e, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+      __hip_atomic_fetch_max(&l.mx[slot], e, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+      __hip_atomic_fetch_add(&l.cv[slot], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    }
+  }
+  static __device__ __forceinline__ void global_row(const Global& a, int64_t g, V val, bool fl)
+  {
+    const unsigned long long e = mm_encode<V>(val);
+    if (fl) {
+      atomicMin(&a.mn[g], e);
+      atomicMax(&a.mx[g], e);
+      atomicAdd(&a.cnt_valid[g], 1u);
+    }
+  }
+  static __device__ __forceinline__ void merge(const Lds& l, int i, const Global& a, int64_t g)
+  {
+    const uint32_t cv = l.cv[i];  // (a group with only null values still got its slot in the global table)
+    if (cv) {
+      atomicMin(&a.mn[g], l.mn[i]);
+      atomicMax(&a.mx[g], l.mx[i]);
+      atomicAdd(&a.cnt_valid[g], cv);
+    }
+  }
+  static __device__ __forceinline__ void emit(const Global& a, int64_t i, int64_t p, const Out& o)
+  {
+    const bool has = a.cnt_valid[i] > 0;
+    if (o.mn) static_cast<V*>(o.mn)[p] = has ? mm_decode<V>(a.mn[i]) : V(0);
+    if (o.mx) static_cast<V*>(o.mx)[p] = has ? mm_decode<V>(a.mx[i]) : V(0);
+    if (o.cv) o.cv[p] = (int32_t)a.cnt_valid[i];
+  }
+};
+
+// small inputs (and gx_groupby_set_algorithm(1)): every row straight into the global table
+template <typename K, typename V, typename Agg>
 __global__ void __launch_bounds__(GBT) k_aggregate(const K* __restrict__ keys, const uint32_t* __restrict__ kvalid,
                                                    const V* __restrict__ vals, const uint32_t* __restrict__ vvalid,
                                                    int64_t n, unsigned long long* table, uint32_t log2cap,
-                                                   double* sum, double* comp, uint32_t* cnt_valid,
-                                                   uint32_t* cnt_all, GbState* st)
+                                                   typename Agg::Global acc, GbState* st)
 {
   const int64_t stride = (int64_t)gridDim.x * GBT;
   for (int64_t i = (int64_t)blockIdx.x * GBT + threadIdx.x; i < n; i += stride) {
     if (kvalid && !bit_is_set(kvalid, i)) continue;  // null_policy::EXCLUDE (compute_groupby.cu:62-66)
     const int64_t g = find_or_insert<K>(table, log2cap, keys[i], st);
     if (g < 0) continue;
-    if (cnt_all) atomicAdd(&cnt_all[g], 1u);
-    if (vals && (!vvalid || bit_is_set(vvalid, i))) {
-      Acc<V, IS_FLOAT>::add(sum, comp, g, vals[i]);
-      atomicAdd(&cnt_valid[g], 1u);
-    }
+    const bool fl = vals && (!vvalid || bit_is_set(vvalid, i));
+    Agg::global_row(acc, g, fl ? vals[i] : V(0), fl);
   }
 }
 
@@ -125,14 +340,11 @@ struct OccLoader {
   }
 };
 
-template <typename K, typename V, bool IS_FLOAT>
+template <typename K, typename Agg>
 __global__ void __launch_bounds__(GBT) k_compact(const unsigned long long* __restrict__ table, uint64_t cap,
                                                  const uint32_t* __restrict__ pos, const uint32_t* __restrict__ total,
-                                                 const double* __restrict__ sum, const double* __restrict__ comp,
-                                                 const uint32_t* __restrict__ cnt_valid,
-                                                 const uint32_t* __restrict__ cnt_all, const GbState* st,
-                                                 int64_t max_groups, K* out_keys, void* out_sum, int32_t* out_cv,
-                                                 int32_t* out_ca, long long* ngroups)
+                                                 typename Agg::Global acc, const GbState* st, int64_t max_groups, K* out_keys,
+                                                 typename Agg::Out out, long long* ngroups)
 {
   const int64_t stride = (int64_t)gridDim.x * GBT;
   for (int64_t i = (int64_t)blockIdx.x * GBT + threadIdx.x; i <= (int64_t)cap; i += stride) {
@@ -150,16 +362,7 @@ __global__ void __launch_bounds__(GBT) k_compact(const unsigned long long* __res
     const int64_t p = pos[i];
     if (p >= max_groups) continue;
     out_keys[p] = key;
-    if (out_sum) {
-      if (IS_FLOAT) {
-        const double r = sum[i] + comp[i];
-        if (sizeof(V) == 4) static_cast<float*>(out_sum)[p] = (float)r; else static_cast<double*>(out_sum)[p] = r;
-      } else {
-        static_cast<long long*>(out_sum)[p] = reinterpret_cast<const long long*>(sum)[i];
-      }
-    }
-    if (out_cv) out_cv[p] = (int32_t)cnt_valid[i];
-    if (out_ca) out_ca[p] = (int32_t)cnt_all[i];
+    Agg::emit(acc, i, p, out);
   }
   if (blockIdx.x == 0 && threadIdx.x == 0) {
     const long long g = (long long)*total;
@@ -176,11 +379,13 @@ __global__ void __launch_bounds__(GBT) k_compact(const unsigned long long* __res
 //                      (tile ranked with LDS atomics, re-ordered in LDS so that every partition
 //                      leaves the tile as one contiguous run, global space reserved with one atomic
 //                      per (tile, partition)); order inside a partition is irrelevant for groupby;
-//   3. k_part_aggregate one 1024-thread workgroup per partition owns an open-addressing table in
-//                      LDS ({key, count, sum, compensation} per group) and streams its rows through
-//                      LDS atomics (ds_add_rtn_f64 with the same two_sum compensation as above);
+//   3. k_part_fold     one 1024-thread workgroup per partition owns an open-addressing table in
+//                      LDS ({key, count, sum, compensation} or {key, min, max, count} per group) and
+//                      streams its rows through LDS atomics (SUM: ds_add_rtn_f64 with the same two_sum
+//                      compensation as above; MIN / MAX: ds_min_u64 / ds_max_u64 on mm_encode's words);
 //                      at the end the few thousand groups of the partition are merged into the
-//                      global table, which also takes any row the LDS table could not hold
+//                      global table (one find_or_insert + three global atomics per group instead of
+//                      per row), which also takes any row the LDS table could not hold
 //                      (more distinct keys than slots): correctness never depends on the fit.
 // HBM traffic: sizeof(K) + 3*(sizeof(K)+sizeof(V)) per row against the algorithmic
 // sizeof(K)+sizeof(V), but every access is streaming; the global-atomic path above does ~4 random
@@ -507,85 +712,106 @@ __global__ void __launch_bounds__(PBT, 2) k_part_scatter(const K* __restrict__ k
   }
 }
 
-template <typename K, bool HAS_VV>
+// ---- the LDS table of one workgroup: S slots {key, the aggregate's words} + the dedicated slot S of the all-ones key, which
+// marks an empty slot
+template <typename K, typename Agg>
 constexpr int lds_slots()
 {
-  // per slot: key + count_valid + sum + comp (+ count_all)
-  constexpr int slot = (int)sizeof(K) + 4 + 8 + 8 + (HAS_VV ? 4 : 0);
-  return (LDS_BUDGET / slot) / 256 * 256;
+  return (LDS_BUDGET / ((int)sizeof(K) + Agg::bytes8 + Agg::bytes4)) / 256 * 256;
 }
-
-template <typename V, bool IS_FLOAT>
-struct LdsAcc;
-template <typename V>
-struct LdsAcc<V, true> {
-  static __device__ __forceinline__ void add(double* sum, double* comp, int g, V v)
-  {
-    const double x   = (double)v;
-    const double old = atomicAdd(&sum[g], x);  // ds_add_rtn_f64
-    const double s   = old + x;
-    const double bb  = s - old;
-    const double err = (old - (s - bb)) + (x - bb);
-    if (err < 0.0 || err > 0.0) atomicAdd(&comp[g], err);  // a NaN err (non-finite sum) is dropped: see Acc<V, true>
-  }
-};
-template <typename V>
-struct LdsAcc<V, false> {
-  static __device__ __forceinline__ void add(double* sum, double*, int g, V v)
-  {
-    atomicAdd(reinterpret_cast<unsigned long long*>(sum) + g, (unsigned long long)(long long)v);
-  }
-};
-
-// merge one partially aggregated group into the global accumulators
-template <bool IS_FLOAT>
-__device__ __forceinline__ void global_merge(double* sum, double* comp, int64_t g, double psum, double pcomp)
+template <typename K, typename Agg>
+constexpr size_t lds_table_bytes()
 {
-  if (IS_FLOAT) {
-    const double old = atomicAdd(&sum[g], psum);
-    const double s   = old + psum;
-    const double bb  = s - old;
-    const double err = ((old - (s - bb)) + (psum - bb)) + pcomp;  // pcomp is finite: no NaN ever enters a comp word
-    if (err < 0.0 || err > 0.0) atomicAdd(&comp[g], err);         // non-finite sum: err is NaN, and sum[g] says it all
-  } else {
-    unsigned long long u;
-    __builtin_memcpy(&u, &psum, 8);
-    atomicAdd(reinterpret_cast<unsigned long long*>(sum) + g, u);
-  }
+  constexpr int S = lds_slots<K, Agg>();
+  return (size_t)(S + 1) * Agg::bytes8 + (size_t)(S + 2) * sizeof(K) + (size_t)(S + 1) * Agg::bytes4;
 }
 
-template <typename K, typename V, bool IS_FLOAT, bool HAS_VV>
-__global__ void __launch_bounds__(ABT) k_part_aggregate(const K* __restrict__ pkeys, const V* __restrict__ pvals,
-                                                        const uint8_t* __restrict__ pflags, const PartPlan* plan,
-                                                        int nsplit, int nsub, unsigned long long* table, uint32_t log2cap,
-                                                        double* sum, double* comp, uint32_t* cnt_valid,
-                                                        uint32_t* cnt_all, GbState* st, uint32_t cap = 0, int gated = 0, int nsub8 = 0)
+// home slot: the hash bits below the pb partition bits, scaled to [0, S)
+template <typename K, int S>
+__device__ __forceinline__ uint32_t lds_slot_hash(K key, int pb)
+{
+  return (uint32_t)(((part_hash<K>(key) >> (32 - pb)) & 0xFFFFFFFFull) * (uint64_t)S >> 32);
+}
+
+// linear probing from h0; -1: the table is (nearly) full and the key is not in it -- the row goes to the global table
+template <typename K, int S>
+__device__ __forceinline__ int lds_find_or_insert(K* l_key, uint32_t* s_nkeys, K key, uint32_t h0)
+{
+  constexpr K EMPTYK         = K(~K(0));
+  constexpr uint32_t MAXKEYS = (uint32_t)(S - S / 8);  // stop inserting new keys above 87.5 % load
+  uint32_t h                 = h0;
+  int slot                   = -1;
+  for (int probes = 0; probes < S; ++probes) {
+    K cur = l_key[h];
+    if (cur == EMPTYK) {
+      if (*s_nkeys >= MAXKEYS) break;  // table (nearly) full: this row goes to the global table
+      cur = atomicCAS(&l_key[h], EMPTYK, key);
+      if (cur == EMPTYK) {
+        atomicAdd(s_nkeys, 1u);
+        slot = (int)h;
+        break;
+      }
+    }
+    if (cur == key) {
+      slot = (int)h;
+      break;
+    }
+    h = (h + 1 == (uint32_t)S) ? 0u : h + 1;
+  }
+  return slot;
+}
+
+// The rows [r0, r1) that split `split` of `nsplit` reads from region rg of partition `part`.  cap != 0: the speculative pass, region
+// = the padded slot (rg, part), filled up to its cursor; cap == 0: the exact pass, one region = the partition.  (WidePlan has the
+// same three slot arrays and no exact pass.)
+template <typename Plan>
+__device__ __forceinline__ void part_rows(const Plan* plan, uint32_t cap, int rg, int part, int split, int nsplit,
+                                          unsigned long long* r0, unsigned long long* r1)
+{
+  unsigned long long p0 = 0, p1 = 0;
+  if (cap) {
+    const unsigned long long fill = plan->cursor[rg][part];
+    const unsigned long long scap = plan->cap0[rg][part];
+    p0 = plan->slot0[rg][part];
+    p1 = p0 + (fill < scap ? fill : scap);
+  } else if constexpr (std::is_same<Plan, PartPlan>::value) {
+    p0 = plan->offset[part];
+    p1 = plan->offset[part + 1];
+  }
+  const unsigned long long len = p1 - p0;
+  const unsigned long long per = (len + nsplit - 1) / nsplit;
+  *r0 = p0 + per * split < p1 ? p0 + per * split : p1;
+  *r1 = *r0 + per < p1 ? *r0 + per : p1;
+}
+
+template <typename K, typename V, typename Agg>
+__global__ void __launch_bounds__(ABT) k_part_fold(const K* __restrict__ pkeys, const V* __restrict__ pvals,
+                                                   const uint8_t* __restrict__ pflags, const PartPlan* plan,
+                                                   int nsplit, int nsub, unsigned long long* table, uint32_t log2cap,
+                                                   typename Agg::Global acc, GbState* st, uint32_t cap, int gated, int nsub8)
 {
   // cap > 0: the speculative pass (skipped when a slot overflowed); cap == 0 && gated: the exact pass behind it
-  if (cap ? (plan->overflow != 0 || plan->dense != 0) : (gated && plan->overflow == 0)) return;  // (dense: k_dense_aggregate has the speculative pass)
-  // the grid is sized for the process-wide partition bits; a call whose plan chose 8 (dense ids) uses nsub8 workgroups per
-  // partition and the surplus workgroups leave
+  if (cap ? (plan->overflow != 0 || (Agg::dense && plan->dense != 0)) : (gated && plan->overflow == 0)) return;  // (dense: k_dense_aggregate has the speculative pass)
   const int pb = part_pbits(plan);
-  if (plan->pbits == 8 && nsub8 > 0) nsub = nsub8;
-  if (blockIdx.x >= (unsigned)((1 << pb) * nsplit * nsub)) return;
-  constexpr int S     = lds_slots<K, HAS_VV>();
-  constexpr K EMPTYK  = K(~K(0));   // rows with this key use the dedicated slot S
+  if constexpr (Agg::dense) {
+    // the grid is sized for the process-wide partition bits; a call whose plan chose 8 (dense ids) uses nsub8 workgroups per
+    // partition and the surplus workgroups leave
+    if (plan->pbits == 8 && nsub8 > 0) nsub = nsub8;
+    if (blockIdx.x >= (unsigned)((1 << pb) * nsplit * nsub)) return;
+  }
+  constexpr bool HAS_VV = Agg::has_vv;
+  constexpr int S       = lds_slots<K, Agg>();
+  constexpr K EMPTYK    = K(~K(0));   // rows with this key use the dedicated slot S
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  double* l_sum    = reinterpret_cast<double*>(smem);            // S + 1
-  double* l_comp   = l_sum + (S + 1);                             // S + 1
-  K* l_key         = reinterpret_cast<K*>(l_comp + (S + 1));      // S + 1 (+1 pad)
-  uint32_t* l_cv   = reinterpret_cast<uint32_t*>(l_key + (S + 2));  // S + 1
-  uint32_t* l_ca   = l_cv + (S + 1);                              // S + 1 (HAS_VV)
+  K* l_key = reinterpret_cast<K*>(smem + (size_t)(S + 1) * Agg::bytes8);  // S + 1 (+1 pad), between the 8-byte and the 4-byte words
+  const typename Agg::Lds lds = Agg::lds(smem, reinterpret_cast<char*>(l_key + (S + 2)), S + 1);
   __shared__ uint32_t s_nkeys;
   __shared__ uint32_t s_special;
 
   const unsigned tid = threadIdx.x;
   for (int i = tid; i <= S; i += ABT) {
-    l_sum[i]  = 0.0;
-    l_comp[i] = 0.0;
-    l_key[i]  = EMPTYK;
-    l_cv[i]   = 0;
-    if (HAS_VV) l_ca[i] = 0;
+    Agg::reset(lds, i);
+    l_key[i] = EMPTYK;
   }
   if (tid == 0) {
     s_nkeys   = 0;
@@ -600,139 +826,90 @@ __global__ void __launch_bounds__(ABT) k_part_aggregate(const K* __restrict__ pk
   const int split = (int)(blockIdx.x / (unsigned)nsub) % nsplit;
   // the rows of this partition: the NRANGE padded slots of the speculative pass, or the exact partition
   const int nreg = cap ? NRANGE : 1;
-  constexpr uint32_t MAXKEYS = (uint32_t)(S - S / 8);  // stop inserting new keys above 87.5 % load
 
   constexpr int U = 8;
   for (int rg = 0; rg < nreg; ++rg) {
-  unsigned long long p0, p1;
-  if (cap) {
-    const unsigned long long fill = plan->cursor[rg][part];
-    const unsigned long long scap = plan->cap0[rg][part];
-    p0 = plan->slot0[rg][part];
-    p1 = p0 + (fill < scap ? fill : scap);
-  } else {
-    p0 = plan->offset[part];
-    p1 = plan->offset[part + 1];
-  }
-  const unsigned long long len = p1 - p0;
-  const unsigned long long per = (len + nsplit - 1) / nsplit;
-  const unsigned long long r0  = p0 + per * split < p1 ? p0 + per * split : p1;
-  const unsigned long long r1  = r0 + per < p1 ? r0 + per : p1;
-  auto process = [&](const K key, const V val, const uint8_t fl) {
+    unsigned long long r0, r1;
+    part_rows(plan, cap, rg, part, split, nsplit, &r0, &r1);
+    auto process = [&](const K key, const V val, const uint8_t fl) {
       if (nsub > 1 && (int)((part_hash<K>(key) >> 16) & (uint64_t)(nsub - 1)) != sub) return;
-      int slot    = -1;
+      int slot;
       if (key == EMPTYK) {
         slot      = S;
         s_special = 1u;  // benign race: every writer stores 1
       } else {
-        uint32_t h = (uint32_t)(((part_hash<K>(key) >> (32 - pb)) & 0xFFFFFFFFull) * (uint64_t)S >> 32);
-        for (int probes = 0; probes < S; ++probes) {
-          K cur = l_key[h];
-          if (cur == EMPTYK) {
-            if (s_nkeys >= MAXKEYS) break;  // table (nearly) full: this row goes to the global table
-            cur = atomicCAS(&l_key[h], EMPTYK, key);
-            if (cur == EMPTYK) {
-              atomicAdd(&s_nkeys, 1u);
-              slot = (int)h;
-              break;
-            }
-          }
-          if (cur == key) {
-            slot = (int)h;
-            break;
-          }
-          h = (h + 1 == (uint32_t)S) ? 0u : h + 1;
-        }
+        slot = lds_find_or_insert<K, S>(l_key, &s_nkeys, key, lds_slot_hash<K, S>(key, pb));
       }
       if (slot >= 0) {
-        // (workgroup scope: an ordinary atomicAdd here is merged with the one on the global counters of the other branch into ONE
-        //  flat_atomic_add through a selected pointer -- every row then pays a FLAT access, and a pending FLAT access makes the compiler
-        //  wait with vmcnt(0) lgkmcnt(0) for everything)
-        if (HAS_VV) __hip_atomic_fetch_add(&l_ca[slot], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-        if (fl) {
-          LdsAcc<V, IS_FLOAT>::add(l_sum, l_comp, slot, val);
-          __hip_atomic_fetch_add(&l_cv[slot], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-        }
+        Agg::lds_row(lds, slot, val, fl);
       } else {
         const int64_t g = find_or_insert<K>(table, log2cap, key, st);
-        if (g >= 0) {
-          if (cnt_all) atomicAdd(&cnt_all[g], 1u);
-          if (fl) {
-            Acc<V, IS_FLOAT>::add(sum, comp, g, val);
-            atomicAdd(&cnt_valid[g], 1u);
+        if (g >= 0) Agg::global_row(acc, g, val, fl != 0);
+      }
+    };
+    if (Agg::vec_rows && sizeof(K) == 4 && cap && nsplit == 1) {
+      // round 6: four consecutive rows per lane and access (one 16-byte load of keys, two of values; the speculative slots start at
+      // multiples of 16 rows) -- the form that took the dense path's aggregate from 3.1 to 1.9 ms
+      typedef K k4 __attribute__((ext_vector_type(4)));
+      typedef V v2 __attribute__((ext_vector_type(2)));
+      constexpr int Q = U / 4;
+      for (unsigned long long i0 = r0 + 4ull * tid; i0 < r1; i0 += 4ull * ABT * Q) {
+        k4 kq[Q];
+        v2 va[Q], vb[Q];
+#pragma unroll
+        for (int u = 0; u < Q; ++u) {
+          const unsigned long long i = i0 + 4ull * ABT * u;
+          if (i + 3 < r1) {
+            kq[u] = *reinterpret_cast<const k4*>(pkeys + i);
+            va[u] = *reinterpret_cast<const v2*>(pvals + i);
+            vb[u] = *reinterpret_cast<const v2*>(pvals + i + 2);
+          } else {
+            kq[u] = k4{i < r1 ? pkeys[i] : K(0), i + 1 < r1 ? pkeys[i + 1] : K(0), i + 2 < r1 ? pkeys[i + 2] : K(0), K(0)};
+            va[u] = v2{i < r1 ? pvals[i] : V(0), i + 1 < r1 ? pvals[i + 1] : V(0)};
+            vb[u] = v2{i + 2 < r1 ? pvals[i + 2] : V(0), V(0)};
           }
         }
-      }
-  };
-  constexpr bool VEC = sizeof(K) == 4 && sizeof(V) == 8 && !HAS_VV;
-  if (VEC && cap && nsplit == 1) {
-    // round 6: four consecutive rows per lane and access (one 16-byte load of keys, two of values; the speculative slots start at
-    // multiples of 16 rows) -- the form that took the dense path's aggregate from 3.1 to 1.9 ms
-    typedef K k4 __attribute__((ext_vector_type(4)));
-    typedef V v2 __attribute__((ext_vector_type(2)));
-    constexpr int Q = U / 4;
-    for (unsigned long long i0 = r0 + 4ull * tid; i0 < r1; i0 += 4ull * ABT * Q) {
-      k4 kq[Q];
-      v2 va[Q], vb[Q];
 #pragma unroll
-      for (int u = 0; u < Q; ++u) {
-        const unsigned long long i = i0 + 4ull * ABT * u;
-        if (i + 3 < r1) {
-          kq[u] = *reinterpret_cast<const k4*>(pkeys + i);
-          va[u] = *reinterpret_cast<const v2*>(pvals + i);
-          vb[u] = *reinterpret_cast<const v2*>(pvals + i + 2);
-        } else {
-          kq[u] = k4{i < r1 ? pkeys[i] : K(0), i + 1 < r1 ? pkeys[i + 1] : K(0), i + 2 < r1 ? pkeys[i + 2] : K(0), K(0)};
-          va[u] = v2{i < r1 ? pvals[i] : V(0), i + 1 < r1 ? pvals[i + 1] : V(0)};
-          vb[u] = v2{i + 2 < r1 ? pvals[i + 2] : V(0), V(0)};
+        for (int u = 0; u < Q; ++u) {
+          const unsigned long long i = i0 + 4ull * ABT * u;
+          const K kk[4] = {kq[u].x, kq[u].y, kq[u].z, kq[u].w};
+          const V vv[4] = {va[u].x, va[u].y, vb[u].x, vb[u].y};
+#pragma unroll
+          for (int e = 0; e < 4; ++e)
+            if (i + e < r1) process(kk[e], vv[e], (uint8_t)1);
         }
       }
+    } else {
+      for (unsigned long long i0 = r0 + tid; i0 < r1; i0 += (unsigned long long)ABT * U) {
+        K k[U];
+        V v[U];
+        uint8_t f[U];
 #pragma unroll
-      for (int u = 0; u < Q; ++u) {
-        const unsigned long long i = i0 + 4ull * ABT * u;
-        const K kk[4] = {kq[u].x, kq[u].y, kq[u].z, kq[u].w};
-        const V vv[4] = {va[u].x, va[u].y, vb[u].x, vb[u].y};
+        for (int u = 0; u < U; ++u) {
+          const unsigned long long i = i0 + (unsigned long long)u * ABT;
+          const bool in              = i < r1;
+          k[u]                       = in ? pkeys[i] : K(0);
+          v[u]                       = in ? pvals[i] : V(0);
+          f[u]                       = HAS_VV ? (in ? pflags[i] : (uint8_t)0) : (uint8_t)1;
+        }
 #pragma unroll
-        for (int e = 0; e < 4; ++e)
-          if (i + e < r1) process(kk[e], vv[e], (uint8_t)1);
+        for (int u = 0; u < U; ++u) {
+          const unsigned long long i = i0 + (unsigned long long)u * ABT;
+          if (i >= r1) continue;
+          process(k[u], v[u], f[u]);
+        }
       }
     }
-  } else {
-  for (unsigned long long i0 = r0 + tid; i0 < r1; i0 += (unsigned long long)ABT * U) {
-    K k[U];
-    V v[U];
-    uint8_t f[U];
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-      const unsigned long long i = i0 + (unsigned long long)u * ABT;
-      const bool in              = i < r1;
-      k[u]                       = in ? pkeys[i] : K(0);
-      v[u]                       = in ? pvals[i] : V(0);
-      f[u]                       = HAS_VV ? (in ? pflags[i] : (uint8_t)0) : (uint8_t)1;
-    }
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-      const unsigned long long i = i0 + (unsigned long long)u * ABT;
-      if (i >= r1) continue;
-      process(k[u], v[u], f[u]);
-    }
-  }
-  }
   }  // regions
   __syncthreads();
-  // ---- merge this workgroup's groups into the global table
+  // ---- merge this workgroup's groups into the global table (a group with only null values still gets its slot)
   for (int i = tid; i <= S; i += ABT) {
     const K key = l_key[i];
     const bool occ = (i < S) ? (key != EMPTYK) : (s_special != 0u);
     if (!occ) continue;
     const int64_t g = find_or_insert<K>(table, log2cap, (i < S) ? key : EMPTYK, st);
     if (g < 0) continue;
-    const uint32_t cv = l_cv[i];
-    if (cnt_all) atomicAdd(&cnt_all[g], HAS_VV ? l_ca[i] : cv);
-    if (cv) {
-      atomicAdd(&cnt_valid[g], cv);
-      global_merge<IS_FLOAT>(sum, comp, g, l_sum[i], l_comp[i]);
-    }
+    Agg::merge(lds, i, acc, g);
   }
 }
 
@@ -760,10 +937,8 @@ __global__ void __launch_bounds__(ABT) k_dense_aggregate(const unsigned short* _
   const int part  = (int)blockIdx.x;
   constexpr int U = 8;
   for (int rg = 0; rg < NRANGE; ++rg) {
-    const unsigned long long fill = plan->cursor[rg][part];
-    const unsigned long long scap = plan->cap0[rg][part];
-    const unsigned long long p0   = plan->slot0[rg][part];
-    const unsigned long long p1   = p0 + (fill < scap ? fill : scap);
+    unsigned long long p0, p1;
+    part_rows(plan, 1u, rg, part, 0, 1, &p0, &p1);
     // four consecutive rows per lane and access: an 8-byte load of remainders, two 16-byte loads of values (slots start at multiples of
     // 16 rows); 2-byte loads -- 128 B per wave instruction -- left the pass at 3.2 TB/s
     typedef unsigned short u16x4 __attribute__((ext_vector_type(4)));
@@ -793,7 +968,7 @@ __global__ void __launch_bounds__(ABT) k_dense_aggregate(const unsigned short* _
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
           if (i + e >= p1) continue;
-          LdsAcc<V, IS_FLOAT>::add(l_sum, l_comp, (int)rr[e], vv[e]);
+          sum_add<V, IS_FLOAT>(l_sum, l_comp, (int)rr[e], vv[e]);
           atomicAdd(&l_cv[rr[e]], 1u);
         }
       }
@@ -1023,48 +1198,53 @@ __global__ void __launch_bounds__(NPART) k_part_reset_cursors(PartPlan* plan)
   for (int r = 0; r < NRANGE; ++r) plan->cursor[r][threadIdx.x] = 0;
 }
 
-template <typename K, typename V, bool IS_FLOAT, bool HAS_VV>
+template <typename K, typename V, typename Agg>
 int launch_partitioned(const K* keys, const uint32_t* kvalid, const V* vals, const uint32_t* vvalid, int64_t n,
                        PartPlan* plan, K* pkeys, V* pvals, uint8_t* pflags, unsigned long long* table, uint32_t lg,
-                       double* sum, double* comp, uint32_t* cv, uint32_t* ca, GbState* st, int64_t max_groups, hipStream_t s)
+                       typename Agg::Global acc, GbState* st, int64_t max_groups, hipStream_t s)
 {
   GX_HIP_TRY(hipMemsetAsync(plan, 0, sizeof(PartPlan), s));
   int64_t hb = div_up(n, 256 * 8 * 4 * NRANGE);
   if (hb > 256) hb = 256;
   if (hb < 1) hb = 1;
+  constexpr bool HAS_VV  = Agg::has_vv;
   constexpr int ESZ      = sizeof(K) > sizeof(V) ? sizeof(K) : sizeof(V);
   constexpr size_t lds_s = (size_t)PTILE * ESZ + (HAS_VV ? PTILE : 0) + NPART * 4 * 2 + NPART * 8 * 2 + 64;
   auto ks                = k_part_scatter<K, V, HAS_VV>;
-  constexpr int S        = lds_slots<K, HAS_VV>();
-  constexpr size_t lds_a = (size_t)(S + 1) * 16 + (size_t)(S + 2) * sizeof(K) + (size_t)(S + 1) * 4 * (HAS_VV ? 2 : 1);
-  auto ka                = k_part_aggregate<K, V, IS_FLOAT, HAS_VV>;
+  constexpr int S        = lds_slots<K, Agg>();
+  constexpr size_t lds_a = lds_table_bytes<K, Agg>();
+  auto ka                = k_part_fold<K, V, Agg>;
   Device dev;
   GX_HIP_TRY(device(&dev));
   const int nsplit    = g_gb_nsplit;
   const int nsub      = lds_nsub(max_groups, S);
-  // the plan of a call may choose 8 bits (dense ids): workgroups per partition for that case; the grid covers both
-  int nsub8 = 1;
-  while (nsub8 < 16 && (double)(max_groups < 1 ? 1 : max_groups) / 256.0 / nsub8 > 0.65 * S) nsub8 *= 2;
   const unsigned sgrd = (unsigned)div_up(n, PTILE);
   unsigned agrd       = (unsigned)((1 << g_gb_pbits) * nsplit * nsub);
-  if (g_gb_auto && g_gb_pbits == 9 && (unsigned)(256 * nsplit * nsub8) > agrd) agrd = (unsigned)(256 * nsplit * nsub8);
-  const bool spec     = part_speculative(n);
-  int gated           = 0;
+  // Agg::dense: the plan of a call may choose 8 partition bits (dense ids, PartPlan::pbits)
+  const bool auto_pbits = Agg::dense && g_gb_auto && g_gb_pbits == 9;
+  int nsub8             = 0;
+  if constexpr (Agg::dense) {  // workgroups per partition for that case; the grid covers both
+    nsub8 = 1;
+    while (nsub8 < 16 && (double)(max_groups < 1 ? 1 : max_groups) / 256.0 / nsub8 > 0.65 * S) nsub8 *= 2;
+    if (auto_pbits && (unsigned)(256 * nsplit * nsub8) > agrd) agrd = (unsigned)(256 * nsplit * nsub8);
+  }
+  const bool spec = part_speculative(n);
+  int gated       = 0;
   if (spec) {  // speculative pass: no histogram, padded slots (see PartPlan)
     const uint32_t cap       = 1u;  // != 0: the speculative form (slot tables in the plan)
     const int stride         = slot_stride(n);
     const int64_t range_rows = range_tiles(n) * PTILE;
     int64_t sblocks          = div_up(div_up(n, (int64_t)stride * GX_WAVE), (int64_t)4 * 8);
     if (sblocks > 2048) sblocks = 2048;
-    if (g_gb_auto && g_gb_pbits == 9) {  // let k_slot_plan choose the partition bits of this call (PartPlan::pbits)
+    if (auto_pbits) {  // let k_slot_plan choose the partition bits of this call
       static const int one = 1;
       static const unsigned long long all_ones = ~0ull;
       GX_HIP_TRY(hipMemcpyAsync(&plan->auto_pbits, &one, sizeof(int), hipMemcpyHostToDevice, s));
       GX_HIP_TRY(hipMemcpyAsync(&plan->kmin, &all_ones, sizeof(all_ones), hipMemcpyHostToDevice, s));  // (the plan was cleared: a minimum starts at the top)
     }
     // round 6: dense ids by direct address (PartPlan::dense) -- 8-byte values without nulls, keys of 4 or 8 bytes, knob on
-    constexpr bool dense_types = !HAS_VV && sizeof(V) == 8 && sizeof(K) >= 4 && std::is_integral<K>::value;
-    const bool dense_ok        = dense_types && g_gb_dense && g_gb_auto && g_gb_pbits == 9 && nsplit == 1;
+    constexpr bool dense_types = Agg::dense && !HAS_VV && sizeof(V) == 8 && sizeof(K) >= 4 && std::is_integral<K>::value;
+    const bool dense_ok        = dense_types && g_gb_dense && auto_pbits && nsplit == 1;
     if (dense_ok) {
       static const int one = 1;
       GX_HIP_TRY(hipMemcpyAsync(&plan->dense_allowed, &one, sizeof(int), hipMemcpyHostToDevice, s));
@@ -1076,98 +1256,116 @@ int launch_partitioned(const K* keys, const uint32_t* kvalid, const V* vals, con
       if (dense_ok) {  // every kernel of the path the plan did not choose leaves at once
         constexpr size_t lds_d = (size_t)DD_GMAX * 20;
         auto ksd               = k_part_scatter<K, V, false, true>;
-        auto kad               = k_dense_aggregate<K, V, IS_FLOAT>;
+        auto kad               = k_dense_aggregate<K, V, !std::is_integral<V>::value>;
         hipLaunchKernelGGL((k_dense_sample<K>), dim3((unsigned)sblocks), dim3(256), 0, s, keys, kvalid, n, plan, stride, range_rows);
         hipLaunchKernelGGL((k_slot_plan<PartPlan>), dim3(1), dim3(NPART), 0, s, plan, n, stride, range_rows, (unsigned long long)slot_elems(n, stride),
                            (long long)max_groups, 1);
         GX_HIP_TRY(launch_lds(dev, ksd, dim3(sgrd), dim3(PBT), lds_s, s, keys, kvalid, vals, vvalid, n, plan, pkeys, pvals, pflags, NRANGE, cap, 0));
         GX_HIP_TRY(launch_lds(dev, kad, dim3(DD_PARTS), dim3(ABT), lds_d, s, reinterpret_cast<const unsigned short*>(pkeys), (const V*)pvals, (const PartPlan*)plan, table, lg,
-                                   sum, comp, cv, ca, st));
+                                   acc.sum, acc.comp, acc.cnt_valid, acc.cnt_all, st));
       }
     }
     GX_HIP_TRY(launch_lds(dev, ks, dim3(sgrd), dim3(PBT), lds_s, s, keys, kvalid, vals, vvalid, n, plan, pkeys, pvals, pflags, NRANGE, cap, 0));
-    GX_HIP_TRY(launch_lds(dev, ka, dim3(agrd), dim3(ABT), lds_a, s, pkeys, pvals, pflags, plan, nsplit, nsub, table, lg, sum, comp, cv, ca, st, cap,
-                               0, nsub8));
+    GX_HIP_TRY(launch_lds(dev, ka, dim3(agrd), dim3(ABT), lds_a, s, pkeys, pvals, pflags, plan, nsplit, nsub, table, lg, acc, st, cap, 0, nsub8));
     hipLaunchKernelGGL(k_part_reset_cursors, dim3(1), dim3(NPART), 0, s, plan);
     gated = 1;  // the exact sequence below runs only if a slot overflowed
   }
   hipLaunchKernelGGL((k_part_hist<K>), dim3((unsigned)(hb * NRANGE)), dim3(256), 0, s, keys, kvalid, n, plan, g_gb_nrange, gated);
   hipLaunchKernelGGL(k_part_offsets, dim3(1), dim3(NPART), 0, s, plan, gated);
   GX_HIP_TRY(launch_lds(dev, ks, dim3(sgrd), dim3(PBT), lds_s, s, keys, kvalid, vals, vvalid, n, plan, pkeys, pvals, pflags, g_gb_nrange, 0u, gated));
-  GX_HIP_TRY(launch_lds(dev, ka, dim3(agrd), dim3(ABT), lds_a, s, pkeys, pvals, pflags, plan, nsplit, nsub, table, lg, sum, comp, cv, ca, st, 0u,
-                             gated, nsub8));
+  GX_HIP_TRY(launch_lds(dev, ka, dim3(agrd), dim3(ABT), lds_a, s, pkeys, pvals, pflags, plan, nsplit, nsub, table, lg, acc, st, 0u, gated, nsub8));
   GX_LAUNCH_CHECK();
   return 0;
 }
 
-template <typename K, typename V, bool IS_FLOAT>
-int groupby_impl(const void* keys, const uint32_t* kvalid, const void* vals, const uint32_t* vvalid, int64_t n,
-                 int64_t max_groups, void* out_keys, void* out_sum, int32_t* out_cv, int32_t* out_ca,
-                 int64_t* ngroups, void* tmp, size_t* tmp_bytes, hipStream_t s)
+// The scratch of one call.  Its size is part of the contract of both entry points (tests/test_groupby_scratch_host.py), and
+// gx_groupby_plan_info finds the plan through it: what lies in front of the plan is sized by max_groups and by the AGGREGATE (its
+// accumulators: 28 bytes per group for SUM / COUNT, 24 for MIN / MAX), not by the key or value type.
+template <typename K, typename V, typename Agg>
+struct Scratch {
+  GbState* st;
+  unsigned long long* table;
+  typename Agg::Global acc;
+  uint32_t* pos;
+  uint32_t* partials;
+  PartPlan* plan;
+  K* pkeys;
+  V* pvals;
+  uint8_t* pflags;
+  size_t total;
+  Scratch(void* tmp, uint64_t cap, int64_t n, bool partitioned, bool value_nulls)
+  {
+    Carver c(tmp);
+    st       = c.take<GbState>(1);
+    table    = c.take<unsigned long long>(cap);
+    acc      = Agg::carve(c, cap);
+    pos      = c.take<uint32_t>(cap + 1);
+    partials = c.take<uint32_t>(scan::partials_count(cap + 1));
+    plan     = c.take<PartPlan>(1);
+    pkeys    = partitioned ? c.take<K>(part_elems(n)) : nullptr;
+    pvals    = partitioned ? c.take<V>(part_elems(n)) : nullptr;
+    pflags   = (partitioned && Agg::carve_flags(value_nulls)) ? c.take<uint8_t>(part_elems(n)) : nullptr;
+    total    = c.total();
+  }
+};
+
+template <typename K, typename V, typename Agg>
+int groupby_impl(const void* keys, const uint32_t* kvalid, const void* vals, const uint32_t* vvalid, int64_t n, int64_t max_groups,
+                 void* out_keys, typename Agg::Out out, int64_t* ngroups, void* tmp, size_t* tmp_bytes, hipStream_t s)
 {
   const uint32_t lg  = log2_cap(max_groups);
   const uint64_t cap = 1ull << lg;
-  // the partitioned path needs a values column and pays off only on large inputs
-  const bool partitioned = vals != nullptr && g_gb_algorithm != 1 && n > 0 &&
+  // the partitioned path needs a values column and pays off only on large inputs (the size query cannot see more than the
+  // call does: callers pass the same arguments to both)
+  const bool partitioned = (!Agg::values_optional || vals != nullptr) && g_gb_algorithm != 1 && n > 0 &&
                            (g_gb_algorithm == 2 || n >= PART_MIN_ROWS);
-  Carver c(tmp);
-  GbState* st               = c.take<GbState>(1);
-  unsigned long long* table = c.take<unsigned long long>(cap);
-  double* sum               = c.take<double>(cap + 1);
-  double* comp              = c.take<double>(cap + 1);
-  uint32_t* cv              = c.take<uint32_t>(cap + 1);
-  uint32_t* ca              = c.take<uint32_t>(cap + 1);
-  uint32_t* pos             = c.take<uint32_t>(cap + 1);
-  uint32_t* partials        = c.take<uint32_t>(scan::partials_count(cap + 1));
-  // the size query cannot see `vals` (callers pass the same arguments, so it can): keep both layouts equal
-  PartPlan* plan  = c.take<PartPlan>(1);
-  K* pkeys        = partitioned ? c.take<K>(part_elems(n)) : nullptr;
-  V* pvals        = partitioned ? c.take<V>(part_elems(n)) : nullptr;
-  uint8_t* pflags = (partitioned && vvalid) ? c.take<uint8_t>(part_elems(n)) : nullptr;
+  Scratch<K, V, Agg> sc(tmp, cap, n, partitioned, vvalid != nullptr);
   if (!tmp) {
-    *tmp_bytes = c.total();
+    *tmp_bytes = sc.total;
     return 0;
   }
-  if (*tmp_bytes < c.total()) return GX_ETMP;
-  // one memset covers state, table and accumulators (they are contiguous up to `pos`)
-  GX_HIP_TRY(hipMemsetAsync(tmp, 0, (size_t)(reinterpret_cast<char*>(pos) - static_cast<char*>(tmp)), s));
+  if (*tmp_bytes < sc.total) return GX_ETMP;
+  // state, table and the zero-initialised accumulators are contiguous: one memset up to the all-ones block (MIN) or `pos`
+  char* ones = static_cast<char*>(Agg::ones(sc.acc));
+  GX_HIP_TRY(hipMemsetAsync(tmp, 0, (size_t)((ones ? ones : reinterpret_cast<char*>(sc.pos)) - static_cast<char*>(tmp)), s));
+  if (ones) GX_HIP_TRY(hipMemsetAsync(ones, 0xFF, (cap + 1) * sizeof(unsigned long long), s));
+  typename Agg::Global acc = sc.acc;
+  Agg::select(acc, out);
+  const K* k = static_cast<const K*>(keys);
+  const V* v = static_cast<const V*>(vals);
   if (partitioned) {
-    int rc;
-    if (vvalid)
-      rc = launch_partitioned<K, V, IS_FLOAT, true>(static_cast<const K*>(keys), kvalid, static_cast<const V*>(vals),
-                                                    vvalid, n, plan, pkeys, pvals, pflags, table, lg, sum, comp, cv,
-                                                    out_ca ? ca : nullptr, st, max_groups, s);
-    else
-      rc = launch_partitioned<K, V, IS_FLOAT, false>(static_cast<const K*>(keys), kvalid, static_cast<const V*>(vals),
-                                                     vvalid, n, plan, pkeys, pvals, pflags, table, lg, sum, comp, cv,
-                                                     out_ca ? ca : nullptr, st, max_groups, s);
+    const int rc = vvalid ? launch_partitioned<K, V, typename Agg::WithNulls>(k, kvalid, v, vvalid, n, sc.plan, sc.pkeys, sc.pvals, sc.pflags, sc.table, lg, acc, sc.st, max_groups, s)
+                          : launch_partitioned<K, V, Agg>(k, kvalid, v, vvalid, n, sc.plan, sc.pkeys, sc.pvals, sc.pflags, sc.table, lg, acc, sc.st, max_groups, s);
     if (rc) return rc;
   } else if (n > 0) {
     int64_t blocks = div_up(n, GBT * 8);
     if (blocks > 256 * 16) blocks = 256 * 16;
-    hipLaunchKernelGGL((k_aggregate<K, V, IS_FLOAT>), dim3((unsigned)blocks), dim3(GBT), 0, s,
-                       static_cast<const K*>(keys), kvalid, static_cast<const V*>(vals), vvalid, n, table, lg, sum,
-                       comp, cv, out_ca ? ca : nullptr, st);
+    hipLaunchKernelGGL((k_aggregate<K, V, Agg>), dim3((unsigned)blocks), dim3(GBT), 0, s, k, kvalid, v, vvalid, n, sc.table, lg, acc, sc.st);
   }
-  OccLoader ld{table, cap, st};
-  int rc = scan::device_scan<uint32_t, uint32_t>(ld, (int64_t)cap + 1, 0u, SumOp(), false, pos, partials, s);
+  OccLoader ld{sc.table, cap, sc.st};
+  int rc = scan::device_scan<uint32_t, uint32_t>(ld, (int64_t)cap + 1, 0u, SumOp(), false, sc.pos, sc.partials, s);
   if (rc) return rc;
   int64_t blocks = div_up((int64_t)cap + 1, GBT * 4);
   if (blocks > 4096) blocks = 4096;
-  hipLaunchKernelGGL((k_compact<K, V, IS_FLOAT>), dim3((unsigned)blocks), dim3(GBT), 0, s, table, cap, pos,
-                     partials + scan::num_chunks((int64_t)cap + 1), sum, comp, cv, ca, st, max_groups,
-                     static_cast<K*>(out_keys), out_sum, out_cv, out_ca, reinterpret_cast<long long*>(ngroups));
+  hipLaunchKernelGGL((k_compact<K, Agg>), dim3((unsigned)blocks), dim3(GBT), 0, s, sc.table, cap, sc.pos,
+                     sc.partials + scan::num_chunks((int64_t)cap + 1), sc.acc, sc.st, max_groups, static_cast<K*>(out_keys), out,
+                     reinterpret_cast<long long*>(ngroups));
   GX_LAUNCH_CHECK();
   return 0;
 }
 
-template <typename K>
+// the policy of a value type, without value nulls (groupby_impl switches to its WithNulls twin)
+template <typename V, bool IS_FLOAT>
+using SumCountOf = SumCount<V, IS_FLOAT, false>;
+template <typename V, bool>
+using MinMaxOf = MinMax<V, false>;
+
+template <typename K, template <typename, bool> class AggOf, typename Out>
 int dispatch_val(int val_dtype, const void* keys, const uint32_t* kvalid, const void* vals, const uint32_t* vvalid,
-                 int64_t n, int64_t max_groups, void* out_keys, void* out_sum, int32_t* out_cv, int32_t* out_ca,
-                 int64_t* ngroups, void* tmp, size_t* tmp_bytes, hipStream_t s)
+                 int64_t n, int64_t max_groups, void* out_keys, Out out, int64_t* ngroups, void* tmp, size_t* tmp_bytes, hipStream_t s)
 {
 #define GX_GB(V, F) \
-  return groupby_impl<K, V, F>(keys, kvalid, vals, vvalid, n, max_groups, out_keys, out_sum, out_cv, out_ca, ngroups, tmp, tmp_bytes, s)
+  return groupby_impl<K, V, AggOf<V, F>>(keys, kvalid, vals, vvalid, n, max_groups, out_keys, out, ngroups, tmp, tmp_bytes, s)
   switch (val_dtype) {
     case GX_INT8: GX_GB(int8_t, false);
     case GX_INT16: GX_GB(int16_t, false);
@@ -1185,6 +1383,21 @@ int dispatch_val(int val_dtype, const void* keys, const uint32_t* kvalid, const 
 #undef GX_GB
 }
 
+template <template <typename, bool> class AggOf, typename Out>
+int dispatch(int key_dtype, int val_dtype, const void* keys, const uint32_t* kvalid, const void* vals, const uint32_t* vvalid,
+             int64_t n, int64_t max_groups, void* out_keys, Out out, int64_t* ngroups, void* tmp, size_t* tmp_bytes, hipStream_t s)
+{
+  switch (key_dtype) {
+    case GX_INT32:
+    case GX_UINT32:
+      return dispatch_val<uint32_t, AggOf>(val_dtype, keys, kvalid, vals, vvalid, n, max_groups, out_keys, out, ngroups, tmp, tmp_bytes, s);
+    case GX_INT64:
+    case GX_UINT64:
+      return dispatch_val<uint64_t, AggOf>(val_dtype, keys, kvalid, vals, vvalid, n, max_groups, out_keys, out, ngroups, tmp, tmp_bytes, s);
+    default: return GX_EDTYPE;
+  }
+}
+
 }  // namespace gb
 }  // namespace gx
 
@@ -1197,17 +1410,20 @@ int gx_groupby_sum_count(int key_dtype, const void* keys, const uint32_t* keys_v
 {
   if (n < 0 || max_groups < 0 || !tmp_bytes) return GX_EINVAL;
   if (tmp && (!ngroups_dev || (n > 0 && !keys) || (max_groups > 0 && !out_keys))) return GX_EINVAL;
-  switch (key_dtype) {
-    case GX_INT32:
-    case GX_UINT32:
-      return gx::gb::dispatch_val<uint32_t>(val_dtype, keys, keys_valid, vals, vals_valid, n, max_groups, out_keys,
-                                            out_sum, out_count_valid, out_count_all, ngroups_dev, tmp, tmp_bytes, s);
-    case GX_INT64:
-    case GX_UINT64:
-      return gx::gb::dispatch_val<uint64_t>(val_dtype, keys, keys_valid, vals, vals_valid, n, max_groups, out_keys,
-                                            out_sum, out_count_valid, out_count_all, ngroups_dev, tmp, tmp_bytes, s);
-    default: return GX_EDTYPE;
-  }
+  return gx::gb::dispatch<gx::gb::SumCountOf>(key_dtype, val_dtype, keys, keys_valid, vals, vals_valid, n, max_groups, out_keys,
+                                              gx::gb::SumOut{out_sum, out_count_valid, out_count_all}, ngroups_dev, tmp, tmp_bytes, s);
+}
+
+// groupby MIN / MAX: small inputs use the global table directly, large ones the LDS-partitioned path (see MinMax)
+int gx_groupby_min_max(int key_dtype, const void* keys, const uint32_t* keys_valid, int val_dtype, const void* vals,
+                       const uint32_t* vals_valid, int64_t n, int64_t max_groups, void* out_keys, void* out_min,
+                       void* out_max, int32_t* out_count_valid, int64_t* ngroups_dev, void* tmp, size_t* tmp_bytes,
+                       gx_stream_t s)
+{
+  if (n < 0 || max_groups < 0 || !tmp_bytes) return GX_EINVAL;
+  if (tmp && (!ngroups_dev || (n > 0 && (!keys || !vals)) || (max_groups > 0 && !out_keys))) return GX_EINVAL;
+  return gx::gb::dispatch<gx::gb::MinMaxOf>(key_dtype, val_dtype, keys, keys_valid, vals, vals_valid, n, max_groups, out_keys,
+                                            gx::gb::MinMaxOut{out_min, out_max, out_count_valid}, ngroups_dev, tmp, tmp_bytes, s);
 }
 
 void gx_groupby_set_partition_mode(int speculative) { gx::gb::g_gb_spec = speculative == 2 ? 2 : (speculative ? 1 : 0); }
@@ -1233,16 +1449,9 @@ int gx_groupby_plan_info(const void* tmp, int64_t max_groups, int32_t* info4_hos
   using namespace gx::gb;
   if (!tmp || !info4_host) return GX_EINVAL;
   const uint64_t cap = 1ull << log2_cap(max_groups);
-  Carver c(const_cast<void*>(tmp));
-  (void)c.take<GbState>(1);
-  (void)c.take<unsigned long long>(cap);
-  (void)c.take<double>(cap + 1);
-  (void)c.take<double>(cap + 1);
-  (void)c.take<uint32_t>(cap + 1);
-  (void)c.take<uint32_t>(cap + 1);
-  (void)c.take<uint32_t>(cap + 1);
-  (void)c.take<uint32_t>(scan::partials_count(cap + 1));
-  const PartPlan* plan = c.take<PartPlan>(1);
+  // a SUM / COUNT scratch only (as documented above: MIN / MAX carves other accumulators in front of its plan); key and value type
+  // only size what lies behind the plan, so any SumCount instantiation finds it
+  const PartPlan* plan = Scratch<uint32_t, double, SumCountOf<double, true>>(const_cast<void*>(tmp), cap, 0, false, false).plan;
   static thread_local PartPlan h;
   GX_HIP_TRY(hipMemcpyAsync(&h, plan, sizeof(PartPlan), hipMemcpyDeviceToHost, (hipStream_t)s));
   GX_HIP_TRY(hipStreamSynchronize((hipStream_t)s));
@@ -1332,398 +1541,6 @@ int gx_mean_from_sum(int sum_dtype, const void* sum, const int32_t* count, int64
   }
   GX_LAUNCH_CHECK();
   return 0;
-}
-
-}  // extern "C"
-
-// ------------------------------------------------------------------------------------------------
-// groupby MIN / MAX (cpp/src/groupby/hash/global_memory_aggregator.cuh:18-238: atomic min/max per
-// group).  Values are widened to a 64-bit word whose unsigned order is the value order (sign flip
-// for signed integers, the IEEE total-order flip for floats with -0.0 -> +0.0 and every NaN above
-// +Inf, the row comparator's order: include/cudf/detail/row_operator/common_utils.cuh:157-169), so one
-// native 64-bit unsigned atomic min / max per row serves every value type.  Small inputs use the global table
-// directly, large ones the LDS-partitioned path below (k_part_minmax).
-// ------------------------------------------------------------------------------------------------
-namespace gx {
-namespace gb {
-
-template <typename V>
-__device__ __forceinline__ unsigned long long mm_encode(V v)
-{
-  if constexpr (sizeof(V) == 8 && !std::is_integral<V>::value) {
-    unsigned long long b;
-    __builtin_memcpy(&b, &v, 8);
-    return to_sortable<unsigned long long, K_FLOAT>(b, 0ull);
-  } else if constexpr (!std::is_integral<V>::value) {
-    const double d = (double)v;  // float -> double is exact and order preserving
-    unsigned long long b;
-    __builtin_memcpy(&b, &d, 8);
-    return to_sortable<unsigned long long, K_FLOAT>(b, 0ull);
-  } else if constexpr (std::is_signed<V>::value) {
-    return (unsigned long long)(long long)v ^ 0x8000000000000000ull;
-  } else {
-    return (unsigned long long)v;
-  }
-}
-template <typename V>
-__device__ __forceinline__ V mm_decode(unsigned long long s)
-{
-  if constexpr (!std::is_integral<V>::value) {
-    const unsigned long long b = (s & 0x8000000000000000ull) ? (s ^ 0x8000000000000000ull) : ~s;
-    double d;
-    __builtin_memcpy(&d, &b, 8);
-    return (V)d;
-  } else if constexpr (std::is_signed<V>::value) {
-    return (V)(long long)(s ^ 0x8000000000000000ull);
-  } else {
-    return (V)s;
-  }
-}
-
-template <typename K, typename V>
-__global__ void __launch_bounds__(GBT) k_minmax(const K* __restrict__ keys, const uint32_t* __restrict__ kvalid,
-                                                const V* __restrict__ vals, const uint32_t* __restrict__ vvalid, int64_t n,
-                                                unsigned long long* table, uint32_t log2cap, unsigned long long* mn,
-                                                unsigned long long* mx, uint32_t* cnt_valid, GbState* st)
-{
-  const int64_t stride = (int64_t)gridDim.x * GBT;
-  for (int64_t i = (int64_t)blockIdx.x * GBT + threadIdx.x; i < n; i += stride) {
-    if (kvalid && !bit_is_set(kvalid, i)) continue;
-    const int64_t g = find_or_insert<K>(table, log2cap, keys[i], st);
-    if (g < 0) continue;
-    if (!vvalid || bit_is_set(vvalid, i)) {
-      const unsigned long long e = mm_encode<V>(vals[i]);
-      atomicMin(&mn[g], e);
-      atomicMax(&mx[g], e);
-      atomicAdd(&cnt_valid[g], 1u);
-    }
-  }
-}
-
-template <typename K, typename V>
-__global__ void __launch_bounds__(GBT) k_minmax_compact(const unsigned long long* __restrict__ table, uint64_t cap,
-                                                        const uint32_t* __restrict__ pos, const uint32_t* __restrict__ total,
-                                                        const unsigned long long* __restrict__ mn,
-                                                        const unsigned long long* __restrict__ mx,
-                                                        const uint32_t* __restrict__ cnt_valid, const GbState* st,
-                                                        int64_t max_groups, K* out_keys, V* out_min, V* out_max,
-                                                        int32_t* out_cv, long long* ngroups)
-{
-  const int64_t stride = (int64_t)gridDim.x * GBT;
-  for (int64_t i = (int64_t)blockIdx.x * GBT + threadIdx.x; i <= (int64_t)cap; i += stride) {
-    bool occ;
-    K key;
-    if ((uint64_t)i < cap) {
-      const unsigned long long s = table[i];
-      occ                        = s != 0ull;
-      key                        = (K)(s - 1ull);
-    } else {
-      occ = st->special_used != 0ull;
-      key = (K)(~0ull);
-    }
-    if (!occ) continue;
-    const int64_t p = pos[i];
-    if (p >= max_groups) continue;
-    out_keys[p] = key;
-    const bool has = cnt_valid[i] > 0;
-    if (out_min) out_min[p] = has ? mm_decode<V>(mn[i]) : V(0);
-    if (out_max) out_max[p] = has ? mm_decode<V>(mx[i]) : V(0);
-    if (out_cv) out_cv[p] = (int32_t)cnt_valid[i];
-  }
-  if (blockIdx.x == 0 && threadIdx.x == 0) *ngroups = st->overflow ? -1ll : (long long)*total;
-}
-
-// LDS-partitioned MIN / MAX: the same radix partition of (key, value) rows as the SUM path (k_part_hist /
-// k_part_scatter), then one workgroup per partition folding its rows into an LDS table of {key, min, max, count}
-// with ds_min_u64 / ds_max_u64 on the order-preserving 64-bit encoding; a group reaches the global table once per
-// partition (one find_or_insert + three global atomics) instead of once per row.  Rows that do not fit the LDS
-// table (more than 7/8 of its slots in use) take the global path row by row, as in k_part_aggregate.
-template <typename K, bool HAS_VV>
-constexpr int lds_slots_mm()
-{
-  constexpr int slot = (int)sizeof(K) + 8 + 8 + 4;
-  return (LDS_BUDGET / slot) / 256 * 256;
-}
-
-template <typename K, typename V, bool HAS_VV>
-__global__ void __launch_bounds__(ABT) k_part_minmax(const K* __restrict__ pkeys, const V* __restrict__ pvals,
-                                                     const uint8_t* __restrict__ pflags, const PartPlan* plan, int nsplit, int nsub,
-                                                     unsigned long long* table, uint32_t log2cap, unsigned long long* mn,
-                                                     unsigned long long* mx, uint32_t* cnt_valid, GbState* st, uint32_t cap = 0,
-                                                     int gated = 0)
-{
-  if (cap ? plan->overflow != 0 : (gated && plan->overflow == 0)) return;
-  constexpr int S    = lds_slots_mm<K, HAS_VV>();
-  constexpr K EMPTYK = K(~K(0));  // rows with this key use the dedicated slot S
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  unsigned long long* l_mn = reinterpret_cast<unsigned long long*>(smem);  // S + 1
-  unsigned long long* l_mx = l_mn + (S + 1);                                // S + 1
-  K* l_key                 = reinterpret_cast<K*>(l_mx + (S + 1));          // S + 1 (+1 pad)
-  uint32_t* l_cv           = reinterpret_cast<uint32_t*>(l_key + (S + 2));  // S + 1
-  __shared__ uint32_t s_nkeys;
-  __shared__ uint32_t s_special;
-
-  const unsigned tid = threadIdx.x;
-  for (int i = tid; i <= S; i += ABT) {
-    l_mn[i]  = ~0ull;
-    l_mx[i]  = 0ull;
-    l_key[i] = EMPTYK;
-    l_cv[i]  = 0;
-  }
-  if (tid == 0) {
-    s_nkeys   = 0;
-    s_special = 0;
-  }
-  __syncthreads();
-
-  // nsub > 1: the keys of a partition are dealt to nsub workgroups by hash bits the partition and the LDS slot do
-  // not use; each reads the whole slice and keeps its own keys, so its LDS table sees 1/nsub of the groups
-  const int sub   = (int)(blockIdx.x % (unsigned)nsub);
-  const int part  = (int)(blockIdx.x / (unsigned)nsub) / nsplit;
-  const int split = (int)(blockIdx.x / (unsigned)nsub) % nsplit;
-  // the rows of this partition: the NRANGE padded slots of the speculative pass, or the exact partition
-  const int nreg = cap ? NRANGE : 1;
-  constexpr uint32_t MAXKEYS   = (uint32_t)(S - S / 8);
-
-  constexpr int U = 8;
-  for (int rg = 0; rg < nreg; ++rg) {
-  unsigned long long p0, p1;
-  if (cap) {
-    const unsigned long long fill = plan->cursor[rg][part];
-    const unsigned long long scap = plan->cap0[rg][part];
-    p0 = plan->slot0[rg][part];
-    p1 = p0 + (fill < scap ? fill : scap);
-  } else {
-    p0 = plan->offset[part];
-    p1 = plan->offset[part + 1];
-  }
-  const unsigned long long len = p1 - p0;
-  const unsigned long long per = (len + nsplit - 1) / nsplit;
-  const unsigned long long r0  = p0 + per * split < p1 ? p0 + per * split : p1;
-  const unsigned long long r1  = r0 + per < p1 ? r0 + per : p1;
-  for (unsigned long long i0 = r0 + tid; i0 < r1; i0 += (unsigned long long)ABT * U) {
-    K k[U];
-    V v[U];
-    uint8_t f[U];
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-      const unsigned long long i = i0 + (unsigned long long)u * ABT;
-      const bool in              = i < r1;
-      k[u]                       = in ? pkeys[i] : K(0);
-      v[u]                       = in ? pvals[i] : V(0);
-      f[u]                       = HAS_VV ? (in ? pflags[i] : (uint8_t)0) : (uint8_t)1;
-    }
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-      const unsigned long long i = i0 + (unsigned long long)u * ABT;
-      if (i >= r1) continue;
-      const K key = k[u];
-      if (nsub > 1 && (int)((part_hash<K>(key) >> 16) & (uint64_t)(nsub - 1)) != sub) continue;
-      int slot    = -1;
-      if (key == EMPTYK) {
-        slot      = S;
-        s_special = 1u;  // benign race: every writer stores 1
-      } else {
-        uint32_t h = (uint32_t)(((part_hash<K>(key) >> (32 - d_gb_pbits)) & 0xFFFFFFFFull) * (uint64_t)S >> 32);
-        for (int probes = 0; probes < S; ++probes) {
-          K cur = l_key[h];
-          if (cur == EMPTYK) {
-            if (s_nkeys >= MAXKEYS) break;
-            cur = atomicCAS(&l_key[h], EMPTYK, key);
-            if (cur == EMPTYK) {
-              atomicAdd(&s_nkeys, 1u);
-              slot = (int)h;
-              break;
-            }
-          }
-          if (cur == key) {
-            slot = (int)h;
-            break;
-          }
-          h = (h + 1 == (uint32_t)S) ? 0u : h + 1;
-        }
-      }
-      const unsigned long long e = mm_encode<V>(v[u]);
-      if (slot >= 0) {
-        if (f[u]) {
-          atomicMin(&l_mn[slot], e);
-          atomicMax(&l_mx[slot], e);
-          atomicAdd(&l_cv[slot], 1u);
-        }
-      } else {
-        const int64_t g = find_or_insert<K>(table, log2cap, key, st);
-        if (g >= 0 && f[u]) {
-          atomicMin(&mn[g], e);
-          atomicMax(&mx[g], e);
-          atomicAdd(&cnt_valid[g], 1u);
-        }
-      }
-    }
-  }
-  }  // regions
-  __syncthreads();
-  // ---- merge this workgroup's groups into the global table (a group with only null values still gets its slot)
-  for (int i = tid; i <= S; i += ABT) {
-    const K key    = l_key[i];
-    const bool occ = (i < S) ? (key != EMPTYK) : (s_special != 0u);
-    if (!occ) continue;
-    const int64_t g = find_or_insert<K>(table, log2cap, (i < S) ? key : EMPTYK, st);
-    if (g < 0) continue;
-    const uint32_t cv = l_cv[i];
-    if (cv) {
-      atomicMin(&mn[g], l_mn[i]);
-      atomicMax(&mx[g], l_mx[i]);
-      atomicAdd(&cnt_valid[g], cv);
-    }
-  }
-}
-
-template <typename K, typename V, bool HAS_VV>
-int launch_partitioned_minmax(const K* keys, const uint32_t* kvalid, const V* vals, const uint32_t* vvalid, int64_t n, PartPlan* plan,
-                              K* pkeys, V* pvals, uint8_t* pflags, unsigned long long* table, uint32_t lg, unsigned long long* mn,
-                              unsigned long long* mx, uint32_t* cv, GbState* st, int64_t max_groups, hipStream_t s)
-{
-  GX_HIP_TRY(hipMemsetAsync(plan, 0, sizeof(PartPlan), s));
-  int64_t hb = div_up(n, 256 * 8 * 4 * NRANGE);
-  if (hb > 256) hb = 256;
-  if (hb < 1) hb = 1;
-  constexpr int ESZ      = sizeof(K) > sizeof(V) ? sizeof(K) : sizeof(V);
-  constexpr size_t lds_s = (size_t)PTILE * ESZ + (HAS_VV ? PTILE : 0) + NPART * 4 * 2 + NPART * 8 * 2 + 64;
-  auto ks                = k_part_scatter<K, V, HAS_VV>;
-  constexpr int S        = lds_slots_mm<K, HAS_VV>();
-  constexpr size_t lds_a = (size_t)(S + 1) * 16 + (size_t)(S + 2) * sizeof(K) + (size_t)(S + 1) * 4;
-  auto ka                = k_part_minmax<K, V, HAS_VV>;
-  Device dev;
-  GX_HIP_TRY(device(&dev));
-  const int nsplit    = g_gb_nsplit;
-  const int nsub      = lds_nsub(max_groups, S);
-  const unsigned sgrd = (unsigned)div_up(n, PTILE);
-  const unsigned agrd = (unsigned)((1 << g_gb_pbits) * nsplit * nsub);
-  const bool spec     = part_speculative(n);
-  int gated           = 0;
-  if (spec) {
-    const uint32_t cap       = 1u;  // != 0: the speculative form (slot tables in the plan)
-    const int stride         = slot_stride(n);
-    const int64_t range_rows = range_tiles(n) * PTILE;
-    int64_t sblocks          = div_up(div_up(n, (int64_t)stride * GX_WAVE), (int64_t)4 * 8);
-    if (sblocks > 2048) sblocks = 2048;
-    hipLaunchKernelGGL((k_slot_sample<K>), dim3((unsigned)sblocks), dim3(256), 0, s, keys, kvalid, n, plan, stride, range_rows);
-    hipLaunchKernelGGL((k_slot_plan<PartPlan>), dim3(1), dim3(NPART), 0, s, plan, n, stride, range_rows, (unsigned long long)slot_elems(n, stride));
-    GX_HIP_TRY(launch_lds(dev, ks, dim3(sgrd), dim3(PBT), lds_s, s, keys, kvalid, vals, vvalid, n, plan, pkeys, pvals, pflags, NRANGE, cap, 0));
-    GX_HIP_TRY(launch_lds(dev, ka, dim3(agrd), dim3(ABT), lds_a, s, pkeys, pvals, pflags, plan, nsplit, nsub, table, lg, mn, mx, cv, st, cap, 0));
-    hipLaunchKernelGGL(k_part_reset_cursors, dim3(1), dim3(NPART), 0, s, plan);
-    gated = 1;
-  }
-  hipLaunchKernelGGL((k_part_hist<K>), dim3((unsigned)(hb * NRANGE)), dim3(256), 0, s, keys, kvalid, n, plan, g_gb_nrange, gated);
-  hipLaunchKernelGGL(k_part_offsets, dim3(1), dim3(NPART), 0, s, plan, gated);
-  GX_HIP_TRY(launch_lds(dev, ks, dim3(sgrd), dim3(PBT), lds_s, s, keys, kvalid, vals, vvalid, n, plan, pkeys, pvals, pflags, g_gb_nrange, 0u, gated));
-  GX_HIP_TRY(launch_lds(dev, ka, dim3(agrd), dim3(ABT), lds_a, s, pkeys, pvals, pflags, plan, nsplit, nsub, table, lg, mn, mx, cv, st, 0u, gated));
-  GX_LAUNCH_CHECK();
-  return 0;
-}
-
-template <typename K, typename V>
-int minmax_impl(const void* keys, const uint32_t* kvalid, const void* vals, const uint32_t* vvalid, int64_t n,
-                int64_t max_groups, void* out_keys, void* out_min, void* out_max, int32_t* out_cv, int64_t* ngroups,
-                void* tmp, size_t* tmp_bytes, hipStream_t s)
-{
-  const uint32_t lg  = log2_cap(max_groups);
-  const uint64_t cap = 1ull << lg;
-  Carver c(tmp);
-  GbState* st               = c.take<GbState>(1);
-  unsigned long long* table = c.take<unsigned long long>(cap);
-  uint32_t* cv              = c.take<uint32_t>(cap + 1);
-  unsigned long long* mx    = c.take<unsigned long long>(cap + 1);  // zero-initialised with the block above
-  unsigned long long* mn    = c.take<unsigned long long>(cap + 1);  // all-ones
-  uint32_t* pos             = c.take<uint32_t>(cap + 1);
-  uint32_t* partials        = c.take<uint32_t>(scan::partials_count(cap + 1));
-  // large inputs: radix-partition the rows and fold each partition in LDS (the scratch layout depends on n only,
-  // so the size query and the call agree)
-  const bool partitioned = g_gb_algorithm != 1 && n > 0 && (g_gb_algorithm == 2 || n >= PART_MIN_ROWS);
-  PartPlan* plan         = c.take<PartPlan>(1);
-  K* pkeys               = partitioned ? c.take<K>(part_elems(n)) : nullptr;
-  V* pvals               = partitioned ? c.take<V>(part_elems(n)) : nullptr;
-  uint8_t* pflags        = partitioned ? c.take<uint8_t>(part_elems(n)) : nullptr;
-  if (!tmp) {
-    *tmp_bytes = c.total();
-    return 0;
-  }
-  if (*tmp_bytes < c.total()) return GX_ETMP;
-  GX_HIP_TRY(hipMemsetAsync(tmp, 0, (size_t)(reinterpret_cast<char*>(mn) - static_cast<char*>(tmp)), s));
-  GX_HIP_TRY(hipMemsetAsync(mn, 0xFF, (cap + 1) * sizeof(unsigned long long), s));
-  if (partitioned) {
-    int prc;
-    if (vvalid)
-      prc = launch_partitioned_minmax<K, V, true>(static_cast<const K*>(keys), kvalid, static_cast<const V*>(vals), vvalid, n, plan,
-                                                  pkeys, pvals, pflags, table, lg, mn, mx, cv, st, max_groups, s);
-    else
-      prc = launch_partitioned_minmax<K, V, false>(static_cast<const K*>(keys), kvalid, static_cast<const V*>(vals), vvalid, n, plan,
-                                                   pkeys, pvals, pflags, table, lg, mn, mx, cv, st, max_groups, s);
-    if (prc) return prc;
-  } else if (n > 0) {
-    int64_t blocks = div_up(n, GBT * 8);
-    if (blocks > 256 * 16) blocks = 256 * 16;
-    hipLaunchKernelGGL((k_minmax<K, V>), dim3((unsigned)blocks), dim3(GBT), 0, s, static_cast<const K*>(keys), kvalid,
-                       static_cast<const V*>(vals), vvalid, n, table, lg, mn, mx, cv, st);
-  }
-  OccLoader ld{table, cap, st};
-  int rc = scan::device_scan<uint32_t, uint32_t>(ld, (int64_t)cap + 1, 0u, SumOp(), false, pos, partials, s);
-  if (rc) return rc;
-  int64_t blocks = div_up((int64_t)cap + 1, GBT * 4);
-  if (blocks > 4096) blocks = 4096;
-  hipLaunchKernelGGL((k_minmax_compact<K, V>), dim3((unsigned)blocks), dim3(GBT), 0, s, table, cap, pos,
-                     partials + scan::num_chunks((int64_t)cap + 1), mn, mx, cv, st, max_groups, static_cast<K*>(out_keys),
-                     static_cast<V*>(out_min), static_cast<V*>(out_max), out_cv, reinterpret_cast<long long*>(ngroups));
-  GX_LAUNCH_CHECK();
-  return 0;
-}
-
-template <typename K>
-int minmax_dispatch(int val_dtype, const void* keys, const uint32_t* kvalid, const void* vals, const uint32_t* vvalid,
-                    int64_t n, int64_t max_groups, void* out_keys, void* out_min, void* out_max, int32_t* out_cv,
-                    int64_t* ngroups, void* tmp, size_t* tmp_bytes, hipStream_t s)
-{
-#define GX_MM(V) return minmax_impl<K, V>(keys, kvalid, vals, vvalid, n, max_groups, out_keys, out_min, out_max, out_cv, ngroups, tmp, tmp_bytes, s)
-  switch (val_dtype) {
-    case GX_INT8: GX_MM(int8_t);
-    case GX_INT16: GX_MM(int16_t);
-    case GX_INT32: GX_MM(int32_t);
-    case GX_INT64: GX_MM(int64_t);
-    case GX_BOOL8:
-    case GX_UINT8: GX_MM(uint8_t);
-    case GX_UINT16: GX_MM(uint16_t);
-    case GX_UINT32: GX_MM(uint32_t);
-    case GX_UINT64: GX_MM(uint64_t);
-    case GX_FLOAT32: GX_MM(float);
-    case GX_FLOAT64: GX_MM(double);
-    default: return GX_EDTYPE;
-  }
-#undef GX_MM
-}
-
-}  // namespace gb
-}  // namespace gx
-
-extern "C" {
-
-int gx_groupby_min_max(int key_dtype, const void* keys, const uint32_t* keys_valid, int val_dtype, const void* vals,
-                       const uint32_t* vals_valid, int64_t n, int64_t max_groups, void* out_keys, void* out_min,
-                       void* out_max, int32_t* out_count_valid, int64_t* ngroups_dev, void* tmp, size_t* tmp_bytes,
-                       gx_stream_t s)
-{
-  if (n < 0 || max_groups < 0 || !tmp_bytes) return GX_EINVAL;
-  if (tmp && (!ngroups_dev || (n > 0 && (!keys || !vals)) || (max_groups > 0 && !out_keys))) return GX_EINVAL;
-  switch (key_dtype) {
-    case GX_INT32:
-    case GX_UINT32:
-      return gx::gb::minmax_dispatch<uint32_t>(val_dtype, keys, keys_valid, vals, vals_valid, n, max_groups, out_keys, out_min,
-                                               out_max, out_count_valid, ngroups_dev, tmp, tmp_bytes, s);
-    case GX_INT64:
-    case GX_UINT64:
-      return gx::gb::minmax_dispatch<uint64_t>(val_dtype, keys, keys_valid, vals, vals_valid, n, max_groups, out_keys, out_min,
-                                               out_max, out_count_valid, ngroups_dev, tmp, tmp_bytes, s);
-    default: return GX_EDTYPE;
-  }
 }
 
 }  // extern "C"
@@ -2150,10 +1967,8 @@ __global__ void __launch_bounds__(ABT) k_wide_aggregate(WideOut pkeys, const V* 
   const int pb   = d_gb_pbits;
   constexpr int U = 4;
   for (int rg = 0; rg < NRANGE; ++rg) {
-    const unsigned long long fill = plan->cursor[rg][part];
-    const unsigned long long cap  = plan->cap0[rg][part];
-    const unsigned long long p0   = plan->slot0[rg][part];
-    const unsigned long long p1   = p0 + (fill < cap ? fill : cap);
+    unsigned long long p0, p1;
+    part_rows(plan, 1u, rg, part, 0, 1, &p0, &p1);
     for (unsigned long long i0 = p0 + tid; i0 < p1; i0 += (unsigned long long)ABT * U) {
       unsigned long long k[U][W];
       V v[U];
@@ -2220,7 +2035,7 @@ __global__ void __launch_bounds__(ABT) k_wide_aggregate(WideOut pkeys, const V* 
           plan->overflow = 1u;
           continue;
         }
-        LdsAcc<V, IS_FLOAT>::add(l_sum, l_comp, slot, v[u]);
+        sum_add<V, IS_FLOAT>(l_sum, l_comp, slot, v[u]);
         atomicAdd(&l_cv[slot], 1u);
       }
     }

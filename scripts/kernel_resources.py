@@ -14,8 +14,9 @@ WANT = re.compile(r"k_hy_hist<unsigned long, 0|k_hy_plan|k_plan2|k_msd_pass<unsi
                   r"k_radix_pass<unsigned long, 0, false|k_hist_all<unsigned long, 0|"
                   r"k_pj_hist<unsigned long, gx::join::TableTop|k_pj_scatter<unsigned long, 16, 1024, gx::join::TableTop|k_pj_probe_pipe<unsigned long>|"
                   r"k_pj_build<unsigned long>|k_tags<unsigned long>|k_lookup<unsigned long>|"
-                  r"k_part_hist<unsigned int>|k_part_scatter<unsigned int, double, false>|k_part_aggregate<unsigned int, double, true, false>|"
-                  r"k_part_minmax<unsigned int, double, false>|k_part_minmax<unsigned long, long, false>|k_part_aggregate<unsigned long, double, true, false>|"
+                  r"k_part_hist<unsigned int>|k_part_scatter<unsigned int, double, false>|k_part_fold<unsigned int, double, gx::gb::SumCount<double, true, false> ?>|"
+                  r"k_part_fold<unsigned int, double, gx::gb::MinMax<double, false> ?>|k_part_fold<unsigned long, long, gx::gb::MinMax<long, false> ?>|"
+                  r"k_part_fold<unsigned long, double, gx::gb::SumCount<double, true, false> ?>|"
                   r"k_lookback_scan<unsigned long, long, gx::SumOp.*true>|k_stream_reduce<.*DD|k_stream_reduce<double|"
                   r"k_hash_rows|k_rows_mismatch|k_gather<unsigned long, false>")
 

@@ -37,11 +37,11 @@ GROUPS = {  # group -> (workload, base names whose LARGEST dispatch is summed)
                                       "k_hf_sample", "k_hf_plan", "k_hf_scatter level 0", "k_hf_scatter level 1",
                                       "k_hy_hist", "k_msd_pass level 0", "k_msd_pass level 1", "k_plan2", "k_local_place", "k_local_sort"]),
     "join probe phase (exact two-pass)": ("join", ["k_pj_hist", "k_pj_offsets", "k_pj_scatter", "k_pj_probe_pipe"]),
-    # (round 6: the dense-id path's kernels -- k_dense_* -- run INSTEAD of k_part_aggregate where the ids allow; both listed)
-    "groupby": ("groupby", ["k_slot_sample", "k_slot_plan", "k_part_reset_cursors", "k_part_scatter", "k_part_aggregate", "k_dense_sample", "k_dense_plan",
+    # (round 6: the dense-id path's kernels -- k_dense_* -- run INSTEAD of k_part_fold where the ids allow; both listed)
+    "groupby": ("groupby", ["k_slot_sample", "k_slot_plan", "k_part_reset_cursors", "k_part_scatter", "k_part_fold", "k_dense_sample", "k_dense_plan",
                             "k_dense_aggregate", "k_compact", "k_chunk_scan", "k_chunk_reduce"]),
-    "groupby (exact two-pass)": ("groupby", ["k_part_hist", "k_part_offsets", "k_part_scatter", "k_part_aggregate"]),
-    "groupby_minmax": ("groupby_minmax", ["k_slot_sample", "k_slot_plan", "k_part_reset_cursors", "k_part_scatter", "k_part_minmax"]),
+    "groupby (exact two-pass)": ("groupby", ["k_part_hist", "k_part_offsets", "k_part_scatter", "k_part_fold"]),
+    "groupby_minmax": ("groupby_minmax", ["k_slot_sample", "k_slot_plan", "k_part_reset_cursors", "k_part_scatter", "k_part_fold"]),
 }
 
 

@@ -1,4 +1,4 @@
-"""Micro-benchmark (not product code): which ingredient makes k_part_minmax<uint64 key, int32 value> 10x slower than
+"""Micro-benchmark (not product code): which ingredient makes k_part_fold<uint64 key, int32 value, MinMax> 10x slower than
 <uint32 key, float64 value>?  Times gx_groupby_min_max over key width x value type x value pattern x nsplit."""
 import sys, os, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))

@@ -1,6 +1,6 @@
 """GPU: float SUM where a compensated sum can differ from the reference's plain addition, and where it must beat it.
 
-Every float SUM of the package is compensated with two_sum (DDSum in gx_reduce_scan.hip; Acc / LdsAcc / global_merge in
+Every float SUM of the package is compensated with two_sum (DDSum in gx_reduce_scan.hip; comp_add in
 gx_groupby.hip).  The error term of an addition that meets +-inf or overflows is inf - inf = NaN; the first part of this file
 pins that no such NaN reaches a result: a sum or prefix is +-inf / NaN exactly where plain addition gives it
 (oracle exact_sum / exact_prefix_sums), and everything finite stays within 1 ulp of the exact value.  The second part feeds
@@ -284,8 +284,8 @@ def _check_hash(k, s, cv, keys, v, vv, what):
 @pytest.mark.parametrize("dtype", FLOATS)
 @pytest.mark.parametrize("algo", [1, 2], ids=["global_table", "lds_partitioned"])
 def test_hash_groupby_sum_non_finite_pinned_path(gx, algo, dtype, nulls):
-    """gx_groupby_set_algorithm(1 | 2, 1) pins the kernels: 1 never partitions (k_aggregate: Acc), 2 partitions every n > 0
-    (k_part_aggregate: LdsAcc in LDS, Acc for rows that spill, global_merge)"""
+    """gx_groupby_set_algorithm(1 | 2, 1) pins the kernels: 1 never partitions (k_aggregate: comp_add on the global table), 2 partitions every n > 0
+    (k_part_fold: comp_add in LDS, on the global table for rows that spill, and in the merge)"""
     Column, ops = gx
     from cudf_amd import _lib
     keys, v, vv = _hash_inputs(dtype, N, 300, nulls, seed=7 + algo)
@@ -323,7 +323,7 @@ def test_hash_groupby_sum_non_finite_auto_path_600k(gx, path, dtype):
 
 
 def test_hash_groupby_two_key_columns_non_finite(gx):
-    """ops.groupby_sum_count_tables on two int32 key columns at 300 000 rows (>= 2^18: the wide-key LDS kernel, LdsAcc)"""
+    """ops.groupby_sum_count_tables on two int32 key columns at 300 000 rows (>= 2^18: the wide-key LDS kernel, comp_add)"""
     Column, ops = gx
     n = 300_000
     keys, v, _ = _hash_inputs("float64", n, 1000, False, seed=13)

@@ -239,9 +239,11 @@ def test_groupby_sum_count_matches_oracle(gx, kdtype, vdtype, gb_algo):
 @pytest.mark.parametrize("nsplit", [1, 3])
 @pytest.mark.parametrize("nulls", [False, True])
 def test_groupby_partitioned_large(gx, nulls, nsplit):
-    """The auto path at sizes where the LDS-partitioned kernels run (n >= 2^19): few groups (every
-    partition fits its LDS table), ~8k groups per partition (LDS tables fill up: rows spill to the
-    global table and the partial sums merge), the all-ones key (dedicated LDS slot) and a hot key."""
+    """The auto path at sizes where the LDS-partitioned kernels run (n >= 2^19): few groups (~100 per
+    partition), many groups (up to 2e6 keys over 512 partitions: at most ~3900 per partition against LDS
+    tables of 4864-6656 slots -- long probe chains, but below the 7/8 load at which rows spill to the global
+    table; that path is tests/test_gpu_groupby_lds_spill.py's), the all-ones key (dedicated LDS slot) and a
+    hot key."""
     Column, ops = gx
     from cudf_amd import _lib
     _lib.lib.gx_groupby_set_algorithm(0, nsplit)
