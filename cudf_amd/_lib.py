@@ -177,6 +177,11 @@ _PROTOS = {
     "gx_search_bounds": (_i, [_i, ctypes.POINTER(_i), ctypes.POINTER(_p), ctypes.POINTER(_p), ctypes.POINTER(_i64), _i64,
                               ctypes.POINTER(_p), ctypes.POINTER(_p), ctypes.POINTER(_i64), _i64, ctypes.POINTER(_i), ctypes.POINTER(_i),
                               _i, _p, _p]),
+    # rolling windows (gx_rolling.hip): fixed or per-row windows, optional groups, no scratch
+    "gx_rolling_tile_rows": (_i, []),
+    "gx_rolling_max_span": (_i, []),
+    "gx_rolling_window": (_i, [_i, _p, _p, _i64, _i64, _i64, _i64, _p, _p, _p, _p, _i, _i, _p, _p, _p, _p]),
+    "gx_rolling_set_kernel": (None, [_i]),
 }
 
 for _name, (_res, _args) in _PROTOS.items():

@@ -1,5 +1,5 @@
 """Thin pandas-like wrapper over the hot path (the cudf.DataFrame surface of the reference, reduced
-to the methods that land on it): sort_values, merge, groupby(...).agg, df[mask], dropna, drop_duplicates.
+to the methods that land on it): sort_values, merge, groupby(...).agg, rolling(...), df[mask], dropna, drop_duplicates.
 
 reference: python/cudf/cudf/core/dataframe.py (sort_values -> core/_internals/sorting.py ->
 pylibcudf.sorting.sorted_order + gather; merge -> core/join/join.py -> pylibcudf.join.inner_join /
@@ -238,6 +238,10 @@ class DataFrame:
     def groupby(self, by: Union[str, Sequence[str]]) -> "GroupBy":
         return GroupBy(self, by)
 
+    def rolling(self, window: int, min_periods: Optional[int] = None, center: bool = False) -> "Rolling":
+        """pandas' DataFrame.rolling(window, min_periods, center) over the rows: .sum() / .min() / .max() / .mean() of every column"""
+        return Rolling(self, window, min_periods, center)
+
 
 def _head(col: Column, n: int) -> Column:
     return ops._slice_rows(col, 0, n)
@@ -286,6 +290,42 @@ def _lexicographic_order(cols: Sequence[Column]) -> Column:
         else:
             order = ops.gather(order, ops.sorted_order(ops.gather(c, order)))
     return order
+
+
+class Rolling:
+    """A fixed window of `window` rows ending at each row (center=True: centred on it, the extra row of an even window before it).
+    min_periods (default: window) = the valid values a window needs for a result; below it the result is null, where pandas has NaN.
+    There is no count: pandas' count has a min_periods rule of its own."""
+
+    def __init__(self, df: DataFrame, window: int, min_periods: Optional[int] = None, center: bool = False):
+        if not isinstance(window, (int, np.integer)) or window < 0:
+            raise ValueError("window must be an integer 0 or greater")
+        if min_periods is not None and min_periods > window:
+            raise ValueError(f"min_periods {min_periods} must be <= window {window}")
+        if min_periods is not None and min_periods < 0:
+            raise ValueError("min_periods must be >= 0")
+        self._df = df
+        self._following = (int(window) - 1) // 2 if center else 0
+        self._preceding = int(window) - self._following
+        self._min_periods = int(window) if min_periods is None else int(min_periods)
+
+    def _all(self, op: str) -> DataFrame:
+        out = DataFrame()
+        for name, c in self._df._cols.items():
+            out._cols[name] = ops.rolling_window(c, self._preceding, self._following, self._min_periods, op)
+        return out
+
+    def sum(self) -> DataFrame:
+        return self._all("sum")
+
+    def min(self) -> DataFrame:
+        return self._all("min")
+
+    def max(self) -> DataFrame:
+        return self._all("max")
+
+    def mean(self) -> DataFrame:
+        return self._all("mean")
 
 
 class GroupBy:

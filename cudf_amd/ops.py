@@ -1351,6 +1351,84 @@ def upper_bound(haystack_cols: Sequence[Column], needle_cols: Sequence[Column], 
     return _bounds(haystack_cols, needle_cols, ascending, null_before, True)
 
 
+# ------------------------------------------------------------------------------------------------
+# rolling windows  (cudf::rolling_window / grouped_rolling_window: include/cudf/rolling.hpp)
+# ------------------------------------------------------------------------------------------------
+
+_ROLLING_OPS = {"sum": L.OP_SUM, "min": L.OP_MIN, "max": L.OP_MAX, "mean": L.OP_MEAN, "count_valid": L.OP_COUNT_VALID,
+                "count_all": L.OP_COUNT_ALL}
+
+
+def _rolling_out_dtype(dt: np.dtype, op: str) -> np.dtype:
+    if op in ("count_valid", "count_all"):
+        return np.dtype(np.int32)
+    if op == "mean":
+        return np.dtype(np.float64)
+    if op == "sum" and dt.kind != "f":
+        return np.dtype(np.uint64 if dt == np.uint64 else np.int64)
+    return dt
+
+
+def group_runs(key_cols: Sequence[Column]):
+    """(labels, offsets) of the runs of equal key rows, as gx_group_offsets writes them: gx_group_heads per key column (nulls equal
+    to nulls, NaNs to NaNs), ORed together."""
+    n = key_cols[0].size
+    heads = torch.empty(max(n, 1), dtype=torch.uint8, device="cuda")
+    for k, c in enumerate(key_cols):
+        if c.size != n:
+            raise ValueError("group keys of different lengths")
+        L.check(_lib.gx_group_heads(c.gx, c.data_ptr, c.mask_ptr if c.has_nulls() else None, None, n, int(k > 0), ptr(heads), stream_ptr()),
+                "gx_group_heads")
+    labels = torch.empty(max(n, 1), dtype=torch.int32, device="cuda")
+    offsets = torch.empty(n + 1, dtype=torch.int32, device="cuda")
+    _run(_lib.gx_group_offsets, ptr(heads), n, ptr(labels), ptr(offsets), None, ptr(_dev_i64()))
+    return labels, offsets
+
+
+def rolling_window(col: Column, preceding, following, min_periods: int, op: str, group_keys: Optional[Sequence[Column]] = None) -> Column:
+    """cudf::rolling_window / grouped_rolling_window: op ("sum", "min", "max", "mean", "count_valid", "count_all") over the rows
+    [i - preceding + 1, i + following] of every row i (preceding counts the row itself), cut to the column or, with group_keys (a
+    sequence of key Columns: groups are runs of equal key rows), to the row's group.  preceding / following: two ints, or two INT32
+    Columns without nulls (one window per row).  A value is valid iff its window holds max(min_periods, 1) valid values, a count iff
+    its window has min_periods rows (include/cudf_amd/gx.h); the mask is kept only when a row is null."""
+    if op not in _ROLLING_OPS:
+        raise ValueError(f"rolling_window: unsupported aggregation {op!r}")
+    if min_periods < 0:
+        raise ValueError("min_periods must be non-negative")
+    per_row = isinstance(preceding, Column) or isinstance(following, Column)
+    if per_row:
+        if group_keys:
+            raise ValueError("rolling_window: per-row windows and group keys do not combine")
+        for w in (preceding, following):
+            if not isinstance(w, Column) or w.dtype != np.int32 or w.mask is not None or w.size != col.size:
+                raise ValueError("rolling_window: window columns must be INT32 Columns without a mask, one row per input row")
+    if col.dtype not in (np.dtype(t) for t in ("i1", "i2", "i4", "i8", "u1", "u2", "u4", "u8", "f4", "f8", "bool")):
+        raise TypeError(f"unsupported dtype {col.dtype}")
+    n = col.size
+    out = Column.empty(_rolling_out_dtype(col.dtype, op), n, nullable=True)
+    if n == 0:
+        out.mask = None
+        return out
+    labels = offsets = None
+    if group_keys:
+        for c in group_keys:
+            if c.size != n:
+                raise ValueError("rolling_window: the group keys must have one row per input row")
+        labels, offsets = group_runs(list(group_keys))
+    nulls = _dev_i64()
+    L.check(_lib.gx_rolling_window(col.gx, col.data_ptr, col.mask_ptr if col.has_nulls() else None, 0, n,
+                                   0 if per_row else int(preceding), 0 if per_row else int(following),
+                                   preceding.data_ptr if per_row else None, following.data_ptr if per_row else None,
+                                   ptr(labels), ptr(offsets), int(min_periods), _ROLLING_OPS[op], out.data_ptr, out.mask_ptr, ptr(nulls),
+                                   stream_ptr()), "gx_rolling_window")
+    k = int(nulls.item())
+    if k:
+        out.null_count = k
+    else:
+        out.mask = None
+    return out
+
+
 def compare_scalar(col: Column, op: str, value) -> Column:
     """BOOL8 column of col[i] <op> value, op in eq / ne / lt / le / gt / ge (or ==, !=, <, <=, >, >=); it shares the input's validity
     (a null row stays null).  NaN compares false except under ne.  The scalar must be representable in the column's dtype."""

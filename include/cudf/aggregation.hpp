@@ -3,6 +3,8 @@
 // order so integer values stay interchangeable; the hot path implements SUM, PRODUCT, MIN, MAX, COUNT_VALID,
 // COUNT_ALL, MEAN, ANY and ALL (cudf::reduce), SUM_OF_SQUARES, M2, VARIANCE, STD, ARGMIN, ARGMAX and (sort path) NTH_ELEMENT; others throw
 // cudf::logic_error where they are used.
+// cudf::rolling_window / grouped_rolling_window (rolling.hpp) take SUM, MIN, MAX, MEAN, COUNT_VALID and COUNT_ALL through
+// rolling_aggregation; every other kind made for that base throws cudf::logic_error there.
 #pragma once
 #include <cudf/types.hpp>
 #include <cudf/utilities/error.hpp>

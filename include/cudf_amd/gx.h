@@ -322,6 +322,41 @@ int gx_search_bounds(int nkeys, const int* dtypes_host, const void* const* hay_c
                      const int* null_before_host, int upper, int32_t* out, gx_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Rolling windows (cudf_amd/csrc/gx_rolling.hip).  Replace the per-row window loop behind cudf::rolling_window and
+ * cudf::grouped_rolling_window (cpp/include/cudf/rolling.hpp; rolling_detail.cuh, grouped_rolling.cu of the reference).
+ * gx_rolling_window: out[i] = op over the rows [i - preceding + 1, i + following] of `in` (n rows; `preceding` counts row i
+ *   itself), cut to [0, n) -- or, with labels / offsets (both or neither; as gx_group_offsets writes them: labels[i] = group
+ *   of row i, offsets[g] = its first row, offsets[ngroups] = n), to the row's group.  Negative values are legal: such a window
+ *   does not hold row i and may be empty.  Bounds are computed in 64 bits.  preceding_col / following_col (both or neither,
+ *   INT32, n rows) give one window per row; the two scalars are then ignored.
+ *   op: GX_OP_SUM (integers and BOOL8 -> INT64, wrapping mod 2^64, UINT64 -> UINT64 with the same bits; floats keep their
+ *   type, FLOAT32 accumulated in double and rounded once), GX_OP_MIN / GX_OP_MAX (input type), GX_OP_MEAN (FLOAT64; integers
+ *   summed exactly in 64 bits, then divided), GX_OP_COUNT_VALID / GX_OP_COUNT_ALL (INT32).
+ *   Validity: out_valid is REQUIRED, (n + 31) / 32 words, every word written; *out_null_count_dev (optional, device int64) =
+ *   nulls written.  SUM / MIN / MAX / MEAN: row i is valid iff its window holds at least max(min_periods, 1) valid values -- a
+ *   window without a valid value is NULL, never an identity, also at min_periods == 0 (a deliberate choice: the reference's
+ *   handling of min_periods == 0 is not copied).  The two counts: row i is valid iff its cut window has at least min_periods
+ *   ROWS.  in_valid (NULL = no nulls) is read from in_begin_bit on; a null's bytes are never read; a null row of `out` is 0.
+ *   Floats: +-inf, NaN and overflow follow plain addition over the window's values (nothing is subtracted anywhere); MIN / MAX
+ *   in the order of the sorts: NaN greater than every number, -0.0 == +0.0 (which zero comes back is unspecified).
+ *   Cost: fixed windows whose halo max(preceding - 1, 0) + max(following, 0) is at most gx_rolling_max_span() and that hold a
+ *   row (preceding + following >= 1) take the tile kernel: constant work per row whatever the window.  Per-row windows, wider
+ *   halos, preceding + following <= 0 -- and windows of up to 8 rows, where it is the faster of the two -- take one thread per
+ *   row looping over its window: O(window) per row.  No scratch.
+ * gx_rolling_tile_rows: output rows per workgroup of the tile kernel (tests size their cases from it).
+ * gx_rolling_max_span: the largest halo (rows before + rows after) the tile kernel takes.
+ * Errors, before any launch: GX_EINVAL n outside [0, 2^31), min_periods < 0, only one of the two window columns, only one of
+ *   labels / offsets, null in / out / out_valid with n > 0, a negative begin bit; GX_EDTYPE an unknown dtype or op.
+ *   n == 0: nothing is launched.
+ * ------------------------------------------------------------------------------------------ */
+int gx_rolling_tile_rows(void);
+int gx_rolling_max_span(void);
+int gx_rolling_window(int dtype, const void* in, const uint32_t* in_valid, int64_t in_begin_bit, int64_t n, int64_t preceding,
+                      int64_t following, const int32_t* preceding_col, const int32_t* following_col, const int32_t* labels,
+                      const int32_t* offsets, int min_periods, int op, void* out, uint32_t* out_valid,
+                      int64_t* out_null_count_dev, gx_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * Hashing / partitioning.
  * gx_murmur3_32: cudf::hashing::detail::MurmurHash3_x86_32<T>
  * (include/cudf/hashing/detail/murmurhash3_x86_32.cuh:22-67), null -> UINT32_MAX, and the

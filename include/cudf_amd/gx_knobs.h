@@ -217,6 +217,11 @@ void gx_select_set_stages(int mask);
  * aligned output, else the direct one runs), 0 = the default choice (DESIGN.md, row filtering: the measured table). */
 void gx_compact_set_kernel(int kernel);
 
+/* A/B knob (per calling thread) of gx_rolling_window: 0 = the default choice (rolling windows: the measured table -- the row
+ * loop for windows of up to 8 rows, the tile kernel beyond, wherever it applies), 1 = the tile kernel wherever it applies (fixed window, preceding + following >= 1, halo <= gx_rolling_max_span()), 2 = always the row loop.
+ * Tests use it to pin the path. */
+void gx_rolling_set_kernel(int which);
+
 /* TEST HOOK (process-wide) of gx_select_distinct: only the low `bits` bits of a row's hash choose its home slot.  0 (default) = the
  * whole hash; a negative value = none of it, every row starts probing at slot 0 -- so a test can drive long probe chains through the
  * slots of OTHER classes at small sizes. */
