@@ -182,6 +182,12 @@ _PROTOS = {
     "gx_rolling_max_span": (_i, []),
     "gx_rolling_window": (_i, [_i, _p, _p, _i64, _i64, _i64, _i64, _p, _p, _p, _p, _i, _i, _p, _p, _p, _p]),
     "gx_rolling_set_kernel": (None, [_i]),
+    # row movement (gx_copying.hip): fused concatenate (descriptors in scratch), scatter in place, copy_if_else
+    "gx_concat_tile_rows": (_i, []),
+    "gx_concatenate": (_i, [_i, _i, ctypes.POINTER(_p), ctypes.POINTER(_i64), ctypes.POINTER(_p), ctypes.POINTER(_i64), _p, _p, _p,
+                            _p, _sz, _p]),
+    "gx_scatter": (_i, [_i, _p, _p, _i64, _p, _i, _p, _i64, _p, _p, _i64, _p]),
+    "gx_copy_if_else": (_i, [_i, _p, _p, _i64, _p, _i, _p, _p, _i64, _p, _i, _p, _p, _i64, _i64, _p, _p, _p, _p]),
 }
 
 for _name, (_res, _args) in _PROTOS.items():

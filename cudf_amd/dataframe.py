@@ -1,5 +1,6 @@
 """Thin pandas-like wrapper over the hot path (the cudf.DataFrame surface of the reference, reduced
-to the methods that land on it): sort_values, merge, groupby(...).agg, rolling(...), df[mask], dropna, drop_duplicates.
+to the methods that land on it): sort_values, merge, groupby(...).agg, rolling(...), df[mask], dropna, drop_duplicates, where, mask;
+concat(frames) beside it.
 
 reference: python/cudf/cudf/core/dataframe.py (sort_values -> core/_internals/sorting.py ->
 pylibcudf.sorting.sorted_order + gather; merge -> core/join/join.py -> pylibcudf.join.inner_join /
@@ -238,9 +239,62 @@ class DataFrame:
     def groupby(self, by: Union[str, Sequence[str]]) -> "GroupBy":
         return GroupBy(self, by)
 
+    def _select(self, cond: Column, other, keep_where_true: bool) -> "DataFrame":
+        if not isinstance(cond, Column) or cond.dtype != np.bool_:
+            raise TypeError("cond must be a bool Column")
+        if cond.size != len(self):
+            raise ValueError(f"cond has {cond.size} rows instead of {len(self)}")
+        if isinstance(other, DataFrame):
+            if other.columns != self.columns or len(other) != len(self):
+                raise ValueError("other must have the columns and the rows of the frame")
+            for name, c in self._cols.items():
+                if other._cols[name].dtype != c.dtype:
+                    raise TypeError(f"column {name!r}: other has dtype {other._cols[name].dtype}, the frame {c.dtype}")
+        elif isinstance(other, Column) or (other is not None and np.ndim(other) != 0):
+            raise TypeError("other must be a scalar, None or a DataFrame")
+        out = DataFrame()
+        for name, c in self._cols.items():
+            o = other._cols[name] if isinstance(other, DataFrame) else other
+            out._cols[name] = ops.copy_if_else(c, o, cond) if keep_where_true else ops.copy_if_else(o, c, cond)
+        return out
+
+    def where(self, cond: Column, other=None) -> "DataFrame":
+        """pandas' DataFrame.where for a row condition: every column keeps its value where cond (a bool Column of len(df) rows) is
+        true and takes `other` elsewhere -- a scalar representable in every column's dtype (no upcast: TypeError otherwise), None
+        (the row becomes null, where pandas has NaN) or a DataFrame with the same columns, dtypes and rows.  A null cond element
+        counts as false."""
+        return self._select(cond, other, True)
+
+    def mask(self, cond: Column, other=None) -> "DataFrame":
+        """pandas' DataFrame.mask: the complement of where -- `other` where cond is true, the frame's value elsewhere (also where
+        cond is null)"""
+        return self._select(cond, other, False)
+
     def rolling(self, window: int, min_periods: Optional[int] = None, center: bool = False) -> "Rolling":
         """pandas' DataFrame.rolling(window, min_periods, center) over the rows: .sum() / .min() / .max() / .mean() of every column"""
         return Rolling(self, window, min_periods, center)
+
+
+def concat(frames: Sequence[DataFrame]) -> DataFrame:
+    """pandas' concat(frames, ignore_index=True) for frames with the same columns (names, order) and dtypes: the rows of frames[0],
+    then frames[1], ...; every column is one fused launch (ops.concatenate).  ValueError: no frames, differing columns; TypeError:
+    differing dtypes (no upcast)."""
+    frames = list(frames)
+    if not frames:
+        raise ValueError("No objects to concatenate")
+    for f in frames:
+        if not isinstance(f, DataFrame):
+            raise TypeError("concat takes DataFrames")
+        if f.columns != frames[0].columns:
+            raise ValueError("concat: the frames must have the same columns")
+    for name, c in frames[0]._cols.items():
+        for f in frames:
+            if f._cols[name].dtype != c.dtype:
+                raise TypeError(f"concat: column {name!r} has dtypes {c.dtype} and {f._cols[name].dtype}")
+    out = DataFrame()
+    for name in frames[0].columns:
+        out._cols[name] = ops.concatenate([f._cols[name] for f in frames])
+    return out
 
 
 def _head(col: Column, n: int) -> Column:

@@ -1429,6 +1429,178 @@ def rolling_window(col: Column, preceding, following, min_periods: int, op: str,
     return out
 
 
+# ------------------------------------------------------------------------------------------------
+# row movement  (cudf::concatenate: include/cudf/concatenate.hpp; scatter / copy_if_else: include/cudf/copying.hpp)
+# ------------------------------------------------------------------------------------------------
+
+def concatenate(cols: Sequence[Column]) -> Column:
+    """cudf::concatenate: the rows of cols[0], then cols[1], ... in ONE launch (gx_concatenate: data, validity words and any
+    number of inputs).  The result has a mask only if an input has nulls; its null count is the sum of the inputs'."""
+    cols = list(cols)
+    if not cols:
+        raise ValueError("concatenate: no columns")
+    dt = cols[0].dtype
+    gx_dtype(dt)
+    for c in cols:
+        if c.dtype != dt:
+            raise TypeError("Type mismatch in columns to concatenate.")
+    n = sum(c.size for c in cols)
+    if n > 2**31 - 1:
+        raise OverflowError("Total number of concatenated rows exceeds the column size limit")
+    with_mask = any(c.has_nulls() for c in cols)
+    out = Column.empty(dt, n, nullable=with_mask and n > 0)
+    if n == 0:
+        return out
+    k = len(cols)
+    ptrs = (ctypes.c_void_p * k)(*[c.data.data_ptr() for c in cols])
+    rows = (ctypes.c_int64 * k)(*[c.size for c in cols])
+    valid = (ctypes.c_void_p * k)(*[c.mask.data_ptr() if c.has_nulls() else None for c in cols])
+    _run(_lib.gx_concatenate, dt.itemsize, k, ptrs, rows, valid, None, out.data_ptr, out.mask_ptr, None)
+    if with_mask:
+        out.null_count = sum(c.null_count for c in cols)
+    return out
+
+
+def concatenate_tables(tables: Sequence[Sequence[Column]]) -> List[Column]:
+    """cudf::concatenate of tables (each a sequence of Columns): column by column"""
+    tables = [list(t) for t in tables]
+    if not tables:
+        raise ValueError("concatenate: no tables")
+    nc = len(tables[0])
+    for t in tables:
+        if len(t) != nc:
+            raise ValueError("Mismatch in table columns to concatenate.")
+        if len({c.size for c in t}) > 1:
+            raise ValueError("Column size mismatch")
+    for k in range(nc):
+        for t in tables:
+            if t[k].dtype != tables[0][k].dtype:
+                raise TypeError("Type mismatch in columns to concatenate.")
+    return [concatenate([t[k] for t in tables]) for k in range(nc)]
+
+
+def _check_scatter_map(m: Column, what: str):
+    if not isinstance(m, Column) or m.dtype != np.int32:
+        raise TypeError(f"{what} must be an INT32 Column")
+    if m.mask is not None:
+        raise ValueError(f"{what} contains nulls")
+
+
+def _scatter_into(target: Column, src_ptr, src_mask_ptr, scalar_valid, is_scalar: bool, src_may_be_null: bool, smap: Column) -> Column:
+    """a copy of `target` with the rows of smap written in place by gx_scatter; the mask is kept only when a row ends up null"""
+    n = target.size
+    out = Column(target.data.clone(), target.dtype, n)
+    if target.has_nulls() or src_may_be_null:
+        out.mask = target.mask.clone() if target.has_nulls() else torch.full((bitmask_words(n),), -1, dtype=torch.int32, device="cuda")
+    if smap.size:
+        L.check(_lib.gx_scatter(target.dtype.itemsize, src_ptr, src_mask_ptr, 0, ptr(scalar_valid), int(is_scalar), smap.data_ptr, smap.size,
+                                out.data_ptr, out.mask_ptr, n, stream_ptr()), "gx_scatter")
+    if out.mask is not None:
+        out.null_count = n - bitmask_count(out.mask, n)
+        if out.null_count == 0:
+            out.mask = None
+    return out
+
+
+def scatter(source_cols: Sequence[Column], scatter_map: Column, target_cols: Sequence[Column]) -> List[Column]:
+    """cudf::scatter: copies of the target columns with target[scatter_map[i]] = source[i]; a negative index counts from the end,
+    indices outside [-n, n) are undefined behaviour (not checked).  scatter_map: an INT32 Column without a mask, no longer than the
+    source.  A map that repeats a row leaves it with one of its candidates."""
+    source_cols, target_cols = list(source_cols), list(target_cols)
+    if len(source_cols) != len(target_cols):
+        raise ValueError("Number of columns in source and target not equal")
+    _check_scatter_map(scatter_map, "scatter_map")
+    for s, t in zip(source_cols, target_cols):
+        if s.dtype != t.dtype:
+            raise TypeError("Column types do not match between source and target")
+        gx_dtype(t.dtype)
+        if scatter_map.size > s.size:
+            raise ValueError("Size of scatter map must be equal to or less than source rows")
+    if len({t.size for t in target_cols}) > 1 or len({s.size for s in source_cols}) > 1:
+        raise ValueError("Column size mismatch")
+    return [_scatter_into(t, s.data_ptr, s.mask_ptr if s.has_nulls() else None, None, False, s.has_nulls(), scatter_map)
+            for s, t in zip(source_cols, target_cols)]
+
+
+def _device_scalar(value, dt: np.dtype, valid: bool = True):
+    """(one element of dt, its validity byte) in device memory, as cudf::scalar keeps them; None is the invalid scalar (value 0); an
+    invalid scalar with a value keeps it, as the reference's does"""
+    host = np.zeros(1, dtype=dt)
+    if value is not None:
+        host[0] = value                      # numpy raises OverflowError for an integer the dtype cannot hold
+        if dt.kind in "iub" and host[0] != value:
+            raise TypeError(f"{value!r} is not representable as {dt}")
+    ok = int(valid and value is not None)
+    return torch.from_numpy(host.view(np.uint8).copy()).cuda(), torch.full((1,), ok, dtype=torch.uint8, device="cuda")
+
+
+def scatter_scalar(values: Sequence, valids: Optional[Sequence[bool]], indices: Column, target_cols: Sequence[Column]) -> List[Column]:
+    """cudf::scatter with one scalar per column: target[indices[i]] = values[k] in column k; valids[k] false (or values[k] None)
+    writes nulls.  valids None = all valid."""
+    values, target_cols = list(values), list(target_cols)
+    valids = [True] * len(values) if valids is None else list(valids)
+    if len(values) != len(target_cols) or len(valids) != len(values):
+        raise ValueError("Number of scalars and table columns mismatch")
+    _check_scatter_map(indices, "indices")
+    for t in target_cols:
+        gx_dtype(t.dtype)
+    if len({t.size for t in target_cols}) > 1:
+        raise ValueError("Column size mismatch")
+    outs = []
+    for v, ok, t in zip(values, valids, target_cols):
+        val, vb = _device_scalar(v, t.dtype, bool(ok))
+        outs.append(_scatter_into(t, ptr(val), None, vb, True, (v is None or not ok) and indices.size > 0, indices))
+    return outs
+
+
+def copy_if_else(lhs, rhs, mask: Column) -> Column:
+    """cudf::copy_if_else: out[i] = lhs[i] where mask[i] is valid and true, else rhs[i] (a null mask element takes rhs).  lhs / rhs:
+    a Column of mask.size rows, or a Python scalar (None: the invalid scalar) standing for a column of equal rows.  The validity
+    of a row is the chosen side's; the mask is kept only when a row is null."""
+    if not isinstance(mask, Column) or mask.dtype != np.bool_:
+        raise TypeError("Boolean mask column must be of type BOOL8")
+    sides = (lhs, rhs)
+    cols = [s for s in sides if isinstance(s, Column)]
+    if len(cols) == 2 and lhs.dtype != rhs.dtype:
+        raise TypeError("Both inputs must be of the same type")
+    if cols:
+        dt = cols[0].dtype
+    else:
+        known = [s for s in sides if s is not None]
+        if not known:
+            raise TypeError("copy_if_else: two invalid scalars have no type")
+        dt = np.asarray(known[0]).dtype
+    gx_dtype(dt)
+    for c in cols:
+        if c.size != mask.size:
+            raise ValueError("Boolean mask column must be the same size as lhs and rhs columns")
+    n = mask.size
+    keep = []                                # device scalars stay alive until the launch is queued
+    args = []
+    may_be_null = False
+    for s in sides:
+        if isinstance(s, Column):
+            args += [s.data_ptr, s.mask_ptr if s.has_nulls() else None, 0, None, 0]
+            may_be_null |= s.has_nulls()
+        else:
+            if n:
+                val, vb = _device_scalar(s, dt)
+                keep.append((val, vb))
+                args += [ptr(val), None, 0, ptr(vb), 1]
+            may_be_null |= s is None
+    out = Column.empty(dt, n, nullable=may_be_null and n > 0)
+    if n == 0:
+        return out
+    nulls = _dev_i64() if may_be_null else None
+    L.check(_lib.gx_copy_if_else(dt.itemsize, *args, mask.data_ptr, mask.mask_ptr if mask.has_nulls() else None, 0, n, out.data_ptr,
+                                 out.mask_ptr, ptr(nulls), stream_ptr()), "gx_copy_if_else")
+    if may_be_null:
+        out.null_count = int(nulls.item())
+        if out.null_count == 0:
+            out.mask = None
+    return out
+
+
 def compare_scalar(col: Column, op: str, value) -> Column:
     """BOOL8 column of col[i] <op> value, op in eq / ne / lt / le / gt / ge (or ==, !=, <, <=, >, >=); it shares the input's validity
     (a null row stays null).  NaN compares false except under ne.  The scalar must be representable in the column's dtype."""

@@ -357,6 +357,50 @@ int gx_rolling_window(int dtype, const void* in, const uint32_t* in_valid, int64
                       int64_t* out_null_count_dev, gx_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Row movement (cudf_amd/csrc/gx_copying.hip).  Replace fused_concatenate_kernel / concatenate_masks (concatenate.cu), the
+ * thrust::scatter + scatter_bitmask pair (detail/scatter.cuh) and copy_if_else_kernel (detail/copy_if_else.cuh) of the
+ * reference.  elem_size is the element width in bytes, 1 / 2 / 4 / 8 (values move as bits: NaN payloads and -0.0 survive).
+ * Validity bitmaps are Arrow bitmaps read from a begin bit on (a sliced view needs no re-based copy); row counts lie in
+ * [0, 2^31).  Every argument check comes before the first device call; with no rows nothing is launched.
+ * gx_concatenate: out = the rows of input 0, then input 1, ... (ninputs >= 1; cols_host / rows_host / valid_ptrs_host /
+ *   begin_bits_host are HOST arrays of ninputs entries; valid_ptrs_host may be NULL, as may any entry: an input without nulls;
+ *   begin_bits_host NULL = all 0).  One launch: a workgroup takes a tile of gx_concat_tile_rows() output rows, finds the inputs
+ *   that cover it, copies each piece with the widest access that source and destination address share (16 bytes down to 1), and
+ *   -- with out_valid, (rows + 31) / 32 words, every word written, bits behind the last row 0 -- composes the tile's validity
+ *   words from the inputs' bitmaps; a tile owns whole words, so nothing is merged with atomics.  *out_null_count_dev
+ *   (optional, device int64) = nulls written (0 without out_valid).  A tile fed by more than 16 inputs copies row by row.
+ *   out == NULL with out_valid: the validity alone (cudf::concatenate_masks); cols_host is then not read.
+ *   Scratch (cub-style query: tmp == NULL -> *tmp_bytes) holds the input descriptors; they reach it as kernel arguments, 64
+ *   per small launch, so the host arrays are not read after the call returns and the stream is not waited for.
+ *   GX_EINVAL: ninputs < 1, a NULL host array (cols, rows), a negative row count or begin bit, a row total of 2^31 or more,
+ *   a NULL input with rows, NULL out and out_valid with rows; GX_ETMP: scratch too small.
+ * gx_scatter: in place on a target the caller has filled: target[wrap(map[i])] = src[i] for i in [0, n), src[0] with
+ *   src_is_scalar; wrap(m) = m < 0 ? m + target_rows : m.  Entries outside [-target_rows, target_rows) are undefined behaviour
+ *   (the reference's DONT_CHECK).  With target_valid the bit of every written row is set or cleared atomically on its word
+ *   (src_valid read from src_begin_bit on, NULL = no nulls; a scalar's validity is the device byte *src_scalar_valid_dev, NULL =
+ *   valid); bits of other rows stay.  A map that repeats a target row leaves it with the value AND validity of one of its
+ *   candidates, which one is unspecified: where the source has nulls the bits are written by a second pass, by the rows whose
+ *   value the target holds.  GX_EINVAL: n or target_rows outside [0, 2^31), a negative begin bit, NULL src / map / target or
+ *   target_rows == 0 with n > 0.
+ * gx_copy_if_else: out[i] = (mask_bool8[i] != 0 and the mask's bit set) ? lhs[i] : rhs[i]; a side with *_is_scalar is one
+ *   element in device memory with its validity byte (NULL = valid).  With out_valid ((n + 31) / 32 words, every word written)
+ *   the validity is the chosen side's, and *out_null_count_dev (optional) the nulls written.  One streaming pass, no scratch.
+ *   GX_EINVAL: n outside [0, 2^31), a negative begin bit, NULL lhs / rhs / mask / out with n > 0.
+ * ------------------------------------------------------------------------------------------ */
+int gx_concat_tile_rows(void);
+int gx_concatenate(int elem_size, int ninputs, const void* const* cols_host, const int64_t* rows_host,
+                   const uint32_t* const* valid_ptrs_host, const int64_t* begin_bits_host, void* out, uint32_t* out_valid,
+                   int64_t* out_null_count_dev, void* tmp, size_t* tmp_bytes, gx_stream_t stream);
+int gx_scatter(int elem_size, const void* src, const uint32_t* src_valid, int64_t src_begin_bit,
+               const uint8_t* src_scalar_valid_dev, int src_is_scalar, const int32_t* map, int64_t n, void* target,
+               uint32_t* target_valid, int64_t target_rows, gx_stream_t stream);
+int gx_copy_if_else(int elem_size, const void* lhs, const uint32_t* lhs_valid, int64_t lhs_begin_bit,
+                    const uint8_t* lhs_scalar_valid_dev, int lhs_is_scalar, const void* rhs, const uint32_t* rhs_valid,
+                    int64_t rhs_begin_bit, const uint8_t* rhs_scalar_valid_dev, int rhs_is_scalar, const uint8_t* mask_bool8,
+                    const uint32_t* mask_valid, int64_t mask_begin_bit, int64_t n, void* out, uint32_t* out_valid,
+                    int64_t* out_null_count_dev, gx_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * Hashing / partitioning.
  * gx_murmur3_32: cudf::hashing::detail::MurmurHash3_x86_32<T>
  * (include/cudf/hashing/detail/murmurhash3_x86_32.cuh:22-67), null -> UINT32_MAX, and the
