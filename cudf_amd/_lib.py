@@ -33,6 +33,16 @@ OP_SUM, OP_PRODUCT, OP_MIN, OP_MAX, OP_COUNT_VALID, OP_COUNT_ALL = 0, 1, 2, 3, 4
 OP_MEAN = 10
 CMP_EQ, CMP_NE, CMP_LT, CMP_LE, CMP_GT, CMP_GE = range(6)
 KEEP_ANY, KEEP_FIRST, KEEP_LAST, KEEP_NONE = range(4)
+# gx_binop (== cudf::binary_operator) and gx_unop (== cudf::unary_operator, IS_NAN / IS_NOT_NAN beside it)
+BINOPS = ("ADD", "SUB", "MUL", "DIV", "TRUE_DIV", "FLOOR_DIV", "MOD", "PMOD", "PYMOD", "POW", "INT_POW", "LOG_BASE", "ATAN2",
+          "SHIFT_LEFT", "SHIFT_RIGHT", "SHIFT_RIGHT_UNSIGNED", "BITWISE_AND", "BITWISE_OR", "BITWISE_XOR", "LOGICAL_AND", "LOGICAL_OR",
+          "EQUAL", "NOT_EQUAL", "LESS", "GREATER", "LESS_EQUAL", "GREATER_EQUAL", "NULL_EQUALS", "NULL_NOT_EQUALS", "NULL_MAX",
+          "NULL_MIN", "GENERIC_BINARY", "NULL_LOGICAL_AND", "NULL_LOGICAL_OR")
+BINOP = {name: code for code, name in enumerate(BINOPS)}
+UNOPS = ("SIN", "COS", "TAN", "ARCSIN", "ARCCOS", "ARCTAN", "SINH", "COSH", "TANH", "ARCSINH", "ARCCOSH", "ARCTANH", "EXP", "LOG",
+         "SQRT", "CBRT", "CEIL", "FLOOR", "ABS", "RINT", "BIT_COUNT", "BIT_INVERT", "NOT", "NEGATE")
+UNOP = {name: code for code, name in enumerate(UNOPS)}
+UNOP.update(IS_NAN=100, IS_NOT_NAN=101)
 
 _PROTOS = {
     "gx_version": (ctypes.c_char_p, []),
@@ -188,6 +198,15 @@ _PROTOS = {
                             _p, _sz, _p]),
     "gx_scatter": (_i, [_i, _p, _p, _i64, _p, _i, _p, _i64, _p, _p, _i64, _p]),
     "gx_copy_if_else": (_i, [_i, _p, _p, _i64, _p, _i, _p, _p, _i64, _p, _i, _p, _p, _i64, _i64, _p, _p, _p, _p]),
+    # element-wise operations (gx_elementwise.hip): binary, unary, cast, bitmap -> BOOL8; the _supported tables are host code
+    "gx_binary_op": (_i, [_i, _i, _p, _p, _i64, _p, _i, _i, _p, _p, _i64, _p, _i, _i64, _i, _p, _p, _p, _p]),
+    "gx_unary_op": (_i, [_i, _i, _p, _i64, _i, _p, _p]),
+    "gx_cast": (_i, [_i, _p, _i64, _i, _p, _p]),
+    "gx_bitmask_to_bool8": (_i, [_p, _i64, _i64, _i, _p, _p]),
+    "gx_binary_op_supported": (_i, [_i, _i, _i, _i]),
+    "gx_unary_op_supported": (_i, [_i, _i, _i]),
+    "gx_elementwise_tile_rows": (_i, []),
+    "gx_elementwise_grid_cap": (_i, []),
 }
 
 for _name, (_res, _args) in _PROTOS.items():

@@ -125,3 +125,105 @@ class Column:
 
     def __len__(self):
         return self.size
+
+    # -------- element-wise operators (ops.binary_operation / unary_operation / cast).  The result dtype is NumPy's:
+    # np.result_type of the operands (a Python scalar is weak), float64 for / on integers, bool for comparisons.  Where NumPy
+    # promotes further than the common type of C++ the operands are cast first (int32 o uint32 -> int64, int64 o uint64 -> float64).
+    # __eq__ / __ne__ are NOT defined: columns are compared and hashed by identity; use .eq() / .ne().
+    def _binop(self, other, kind: str, reflected: bool = False) -> "Column":
+        from . import ops
+        if isinstance(other, Column):
+            odt = other.dtype
+            rt = np.result_type(self.dtype, odt)
+        elif isinstance(other, (bool, int, float, np.generic)):
+            rt = np.result_type(self.dtype, other)
+            odt = other.dtype if isinstance(other, np.generic) else rt
+        else:
+            return NotImplemented
+        integral = rt.kind in "iub"
+        if kind in ("and", "or", "xor", "lshift", "rshift") and not integral:
+            raise TypeError(f"operator {kind!r} is not supported for {rt}")
+        if kind in ("lshift", "rshift") and rt.kind == "b":
+            rt = np.dtype(np.int8)           # NumPy shifts bools as int8
+        name = {"add": "ADD", "sub": "SUB", "mul": "MUL", "floordiv": "FLOOR_DIV", "mod": "PYMOD", "and": "BITWISE_AND",
+                "or": "BITWISE_OR", "xor": "BITWISE_XOR", "lshift": "SHIFT_LEFT", "rshift": "SHIFT_RIGHT", "lt": "LESS",
+                "le": "LESS_EQUAL", "gt": "GREATER", "ge": "GREATER_EQUAL", "eq": "EQUAL", "ne": "NOT_EQUAL",
+                "truediv": "TRUE_DIV" if integral else "DIV", "pow": "INT_POW" if integral else "POW"}[kind]
+        if kind in ("lt", "le", "gt", "ge", "eq", "ne"):
+            out = np.dtype(np.bool_)
+        elif kind == "truediv" and integral:
+            out = np.dtype(np.float64)
+        else:
+            out = rt
+        # the compute class of the kernel (everything below 32 bits computes in int32) against the class of NumPy's type
+        cls = lambda dt: {"u4": 1, "i8": 2, "u8": 3, "f4": 4, "f8": 5}.get(np.dtype(dt).str[1:], 0)  # noqa: E731
+        lhs = self
+        if max(cls(self.dtype), cls(odt)) != cls(rt):
+            lhs = ops.cast(self, rt) if self.dtype != rt else self
+            if isinstance(other, Column):
+                other = ops.cast(other, rt) if other.dtype != rt else other
+            odt = rt
+        sdt = None if isinstance(other, Column) else odt
+        if reflected:
+            return ops.binary_operation(other, lhs, name, out, scalar_dtype=sdt)
+        return ops.binary_operation(lhs, other, name, out, scalar_dtype=sdt)
+
+    def __add__(self, o): return self._binop(o, "add")
+    def __radd__(self, o): return self._binop(o, "add", True)
+    def __sub__(self, o): return self._binop(o, "sub")
+    def __rsub__(self, o): return self._binop(o, "sub", True)
+    def __mul__(self, o): return self._binop(o, "mul")
+    def __rmul__(self, o): return self._binop(o, "mul", True)
+    def __truediv__(self, o): return self._binop(o, "truediv")
+    def __rtruediv__(self, o): return self._binop(o, "truediv", True)
+    def __floordiv__(self, o): return self._binop(o, "floordiv")
+    def __rfloordiv__(self, o): return self._binop(o, "floordiv", True)
+    def __mod__(self, o): return self._binop(o, "mod")
+    def __rmod__(self, o): return self._binop(o, "mod", True)
+    def __pow__(self, o): return self._binop(o, "pow")
+    def __rpow__(self, o): return self._binop(o, "pow", True)
+    def __and__(self, o): return self._binop(o, "and")
+    def __rand__(self, o): return self._binop(o, "and", True)
+    def __or__(self, o): return self._binop(o, "or")
+    def __ror__(self, o): return self._binop(o, "or", True)
+    def __xor__(self, o): return self._binop(o, "xor")
+    def __rxor__(self, o): return self._binop(o, "xor", True)
+    def __lshift__(self, o): return self._binop(o, "lshift")
+    def __rlshift__(self, o): return self._binop(o, "lshift", True)
+    def __rshift__(self, o): return self._binop(o, "rshift")
+    def __rrshift__(self, o): return self._binop(o, "rshift", True)
+    def __lt__(self, o): return self._binop(o, "lt")
+    def __le__(self, o): return self._binop(o, "le")
+    def __gt__(self, o): return self._binop(o, "gt")
+    def __ge__(self, o): return self._binop(o, "ge")
+
+    def eq(self, o) -> "Column":
+        """element-wise ==, a bool column (== itself compares columns by identity)"""
+        return self._binop(o, "eq")
+
+    def ne(self, o) -> "Column":
+        return self._binop(o, "ne")
+
+    def __neg__(self):
+        from . import ops
+        return ops.unary_operation(self, "NEGATE")
+
+    def __abs__(self):
+        from . import ops
+        return ops.unary_operation(self, "ABS")
+
+    def __invert__(self):
+        from . import ops
+        return ops.unary_operation(self, "NOT" if self.dtype == np.bool_ else "BIT_INVERT")
+
+    def astype(self, dtype) -> "Column":
+        from . import ops
+        return ops.cast(self, dtype)
+
+    def isnull(self) -> "Column":
+        from . import ops
+        return ops.is_null(self)
+
+    def notnull(self) -> "Column":
+        from . import ops
+        return ops.is_valid(self)

@@ -1626,6 +1626,119 @@ def compare_scalar(col: Column, op: str, value) -> Column:
 
 
 # ------------------------------------------------------------------------------------------------
+# element-wise operations  (cudf::binary_operation / unary_operation / cast: binaryop.hpp, unary.hpp; gx_elementwise.hip)
+# ------------------------------------------------------------------------------------------------
+
+def _op_code(op, table, what: str) -> int:
+    if isinstance(op, str):
+        if op.upper() not in table:
+            raise ValueError(f"unknown {what} {op!r}")
+        return table[op.upper()]
+    return int(op)
+
+
+def binary_operation(lhs, rhs, op, out_dtype, scalar_dtype=None) -> Column:
+    """cudf::binary_operation: out[i] = cast<out_dtype>(lhs[i] op rhs[i]), op a name of cudf::binary_operator ("ADD", "LESS", ...).
+    One side may be a Python / NumPy scalar, or None for the invalid scalar; it is held in scalar_dtype, or else in the dtype NumPy's
+    promotion gives it beside the column (np.result_type(column dtype, scalar): a Python scalar is weak; None: the column's dtype).
+    The operands are converted to the common type of C++ (int32 o uint32 -> uint32, ...: include/cudf_amd/gx.h), not to NumPy's.
+    A row is null where a side is (the NULL_* operators have their own rules); the mask is kept only when a row is null."""
+    code = _op_code(op, L.BINOP, "binary operator")
+    sides = (lhs, rhs)
+    cols = [s for s in sides if isinstance(s, Column)]
+    if not cols:
+        raise TypeError("binary_operation: one side must be a Column")
+    if len(cols) == 2 and lhs.size != rhs.size:
+        raise ValueError("Column sizes don't match")
+    out_dt = np.dtype(out_dtype)
+    n = cols[0].size
+    dts = []
+    for s in sides:
+        if isinstance(s, Column):
+            dts.append(s.dtype)
+        elif scalar_dtype is not None:
+            dts.append(np.dtype(scalar_dtype))
+        elif s is None:
+            dts.append(cols[0].dtype)
+        else:
+            dts.append(np.result_type(cols[0].dtype, s))
+    if not _lib.gx_binary_op_supported(code, gx_dtype(dts[0]), gx_dtype(dts[1]), gx_dtype(out_dt)):
+        raise TypeError(f"binary operator {op!r} is not supported for {dts[0]} and {dts[1]}")
+    keep, args = [], []                      # device scalars stay alive until the launch is queued
+    may_be_null = False
+    for s, dt in zip(sides, dts):
+        if isinstance(s, Column):
+            args += [s.gx, s.data_ptr, s.mask_ptr if s.has_nulls() else None, 0, None, 0]
+            may_be_null |= s.has_nulls()
+        else:
+            val, vb = _device_scalar(s, dt) if n else (None, None)
+            keep.append((val, vb))
+            args += [gx_dtype(dt), ptr(val), None, 0, ptr(vb), 1]
+            may_be_null |= s is None
+    out = Column.empty(out_dt, n, nullable=may_be_null and n > 0)
+    if n == 0:
+        return out
+    nulls = _dev_i64() if may_be_null else None
+    L.check(_lib.gx_binary_op(code, *args, n, out.gx, out.data_ptr, out.mask_ptr, ptr(nulls), stream_ptr()), "gx_binary_op")
+    if may_be_null:
+        out.null_count = int(nulls.item())
+        if out.null_count == 0:
+            out.mask = None
+    return out
+
+
+def _share_validity(out: Column, col: Column) -> Column:
+    if col.mask is not None:
+        out.mask, out.null_count = col.mask, col.null_count
+    return out
+
+
+def unary_operation(col: Column, op) -> Column:
+    """cudf::unary_operation (SQRT, CEIL, FLOOR, ABS, RINT, BIT_INVERT, NOT, NEGATE) and IS_NAN / IS_NOT_NAN: the result has the
+    input's dtype (NOT and the NaN predicates: bool) and shares its validity."""
+    code = _op_code(op, L.UNOP, "unary operator")
+    out_dt = np.dtype(np.bool_) if code in (L.UNOP["NOT"], L.UNOP["IS_NAN"], L.UNOP["IS_NOT_NAN"]) else col.dtype
+    if not _lib.gx_unary_op_supported(code, col.gx, gx_dtype(out_dt)):
+        raise TypeError(f"unary operator {op!r} is not supported for {col.dtype}")
+    out = Column.empty(out_dt, col.size)
+    L.check(_lib.gx_unary_op(code, col.gx, col.data_ptr, col.size, out.gx, out.data_ptr, stream_ptr()), "gx_unary_op")
+    return _share_validity(out, col)
+
+
+def cast(col: Column, dtype) -> Column:
+    """cudf::cast: static_cast of every element (to bool: x != 0; float -> integer truncates toward zero); shares the validity"""
+    gx_dtype(dtype), gx_dtype(col.dtype)     # TypeError before anything is allocated
+    out = Column.empty(np.dtype(dtype), col.size)
+    L.check(_lib.gx_cast(col.gx, col.data_ptr, col.size, out.gx, out.data_ptr, stream_ptr()), "gx_cast")
+    return _share_validity(out, col)
+
+
+def _validity_as_bool(col: Column, invert: bool) -> Column:
+    out = Column.empty(np.bool_, col.size)
+    L.check(_lib.gx_bitmask_to_bool8(col.mask_ptr if col.has_nulls() else None, 0, col.size, int(invert), out.data_ptr, stream_ptr()),
+            "gx_bitmask_to_bool8")
+    return out
+
+
+def is_null(col: Column) -> Column:
+    """cudf::is_null: a bool column without nulls, true where the row is null"""
+    return _validity_as_bool(col, True)
+
+
+def is_valid(col: Column) -> Column:
+    return _validity_as_bool(col, False)
+
+
+def is_nan(col: Column) -> Column:
+    """cudf::is_nan: a float column -> bool, true where the value is a NaN; a null row stays null"""
+    return unary_operation(col, "IS_NAN")
+
+
+def is_not_nan(col: Column) -> Column:
+    return unary_operation(col, "IS_NOT_NAN")
+
+
+# ------------------------------------------------------------------------------------------------
 # synthetic data / checks (bench + tests)
 # ------------------------------------------------------------------------------------------------
 

@@ -401,6 +401,78 @@ int gx_copy_if_else(int elem_size, const void* lhs, const uint32_t* lhs_valid, i
                     int64_t* out_null_count_dev, gx_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Element-wise operations (cudf_amd/csrc/gx_elementwise.hip).  Replace the type-dispatched functors and the JIT of the
+ * reference's cpp/src/binaryop and the kernels of cpp/src/unary.  All eleven gx_dtype are taken on every operand and on the
+ * output; no scratch, no host synchronisation, everything is stream-ordered; row counts lie in [0, 2^31).
+ * gx_binary_op: out[i] = cast<Out>( f( cast<C>(lhs[i]), cast<C>(rhs[i]) ) ).  C is the type the usual arithmetic conversions of
+ *   C++ give for L op R: anything narrower than 32 bits, and BOOL8, computes in int32; else C is uint32, int64, uint64, float or
+ *   double (int32 o uint32 -> uint32, int64 o uint64 -> uint64, integer o float -> float, anything o double -> double).  Integer
+ *   results wrap modulo 2^width of C.  A BOOL8 load takes any nonzero byte as 1, a BOOL8 store writes 0 or 1 (x != 0).
+ *   Operators (gx_binop, the values of cudf::binary_operator):
+ *     ADD SUB MUL in C; DIV '/' in C (integers truncate); TRUE_DIV double(x) / double(y);
+ *     FLOOR_DIV integers: exact floor division; floats: NumPy's floor_divide -- floor of (x - fmod(x, y)) / y, corrected as
+ *       npy_divmod does, which is floor(x / y) wherever that quotient is exact, NaN for an infinite x, -1 for finite x / -inf of
+ *       opposite signs, and a zero that carries the sign of x / y;
+ *     MOD '%' (sign of the dividend) / fmod; PMOD and PYMOD on signed integers ((x % y) + y) % y computed without the overflow of
+ *       the inner sum, on unsigned x % y; PMOD on floats r = fmod(x, y), r < 0: r = fmod(r + y, y); PYMOD on floats NumPy's
+ *       remainder (r = fmod(x, y); r != 0: r += y when the signs of r and y differ; else r = copysign(0, y));
+ *     POW pow(double(x), double(y)), powf when C is float; INT_POW (integer C) by squaring, wrapping, 0 for a negative exponent;
+ *     BITWISE_AND / OR / XOR, SHIFT_LEFT, SHIFT_RIGHT (integer C; arithmetic for signed C), SHIFT_RIGHT_UNSIGNED a logical shift
+ *       of the left operand as the unsigned type of ITS OWN width (an int8 -1 by 1 is 127);
+ *     LOGICAL_AND / OR on x != 0, y != 0; EQUAL ... GREATER_EQUAL in C (NaN compares false except under NOT_EQUAL);
+ *     NULL_EQUALS / NULL_NOT_EQUALS, NULL_MAX / NULL_MIN ((x < y) ? y : x, (y < x) ? y : x), NULL_LOGICAL_AND / OR: below.
+ *     LOG_BASE, ATAN2 and GENERIC_BINARY are not built (gx_binary_op_supported = 0).
+ *   Unspecified, as where the reference has C++ undefined behaviour -- integer division or modulo by zero, INT_MIN / -1, shift
+ *   counts outside [0, width), a float -> integer cast out of range, the data of a null output row -- but none of them faults,
+ *   traps or hangs the kernel.
+ *   A side with *_is_scalar is one element in device memory with its validity byte (NULL = valid), as in gx_copy_if_else; the
+ *   bitmaps are read from their own begin bits.  out_valid == NULL: no bitmap is read or written (neither side can be null).
+ *   Else every one of the (n + 31) / 32 words is written, bits behind the last row 0: ordinary operators lhs bit AND rhs bit (an
+ *   invalid scalar makes every row null); NULL_EQUALS / NULL_NOT_EQUALS always valid (both null: true / false, one null: false /
+ *   true); NULL_MAX / NULL_MIN valid when either side is, the value that side's when only one is; NULL_LOGICAL_AND / OR Kleene
+ *   logic (a valid false / true on either side decides the row, otherwise it is null if either side is).
+ *   *out_null_count_dev (optional) = null rows (0 without out_valid).  A workgroup owns gx_elementwise_tile_rows() consecutive
+ *   rows per trip (a multiple of 32: one writer per word, no atomics) and at most gx_elementwise_grid_cap() workgroups are
+ *   launched; a thread moves 16 bytes per access on the widest of lhs, rhs and out.
+ *   GX_EINVAL: n outside [0, 2^31), a negative begin bit, NULL lhs / rhs / out with n > 0, an op outside gx_binop;
+ *   GX_EDTYPE: an unknown dtype or a combination gx_binary_op_supported rejects.  n == 0 returns 0 and reads no pointer.
+ * gx_unary_op (gx_unop, the values of cudf::unary_operator; IS_NAN / IS_NOT_NAN beside them): ABS (identity on unsigned), NEGATE
+ *   (numeric dtypes), SQRT CEIL FLOOR RINT (floats; RINT rounds half to even), BIT_INVERT (integers, not BOOL8): out_dtype ==
+ *   in_dtype; NOT: x == 0 into BOOL8 from any dtype; IS_NAN / IS_NOT_NAN: a float into BOOL8.  The transcendental operators,
+ *   CBRT and BIT_COUNT are not built.  gx_cast: static_cast between any two dtypes (to BOOL8: x != 0).  Neither touches a
+ *   bitmap: the caller copies or shares the input's.  Errors as gx_binary_op.
+ * gx_bitmask_to_bool8: out[i] = bit begin_bit + i of valid (NULL: every bit set), inverted with invert != 0.
+ * ------------------------------------------------------------------------------------------ */
+enum gx_binop {
+  GX_BINOP_ADD = 0, GX_BINOP_SUB = 1, GX_BINOP_MUL = 2, GX_BINOP_DIV = 3, GX_BINOP_TRUE_DIV = 4, GX_BINOP_FLOOR_DIV = 5,
+  GX_BINOP_MOD = 6, GX_BINOP_PMOD = 7, GX_BINOP_PYMOD = 8, GX_BINOP_POW = 9, GX_BINOP_INT_POW = 10, GX_BINOP_LOG_BASE = 11,
+  GX_BINOP_ATAN2 = 12, GX_BINOP_SHIFT_LEFT = 13, GX_BINOP_SHIFT_RIGHT = 14, GX_BINOP_SHIFT_RIGHT_UNSIGNED = 15,
+  GX_BINOP_BITWISE_AND = 16, GX_BINOP_BITWISE_OR = 17, GX_BINOP_BITWISE_XOR = 18, GX_BINOP_LOGICAL_AND = 19,
+  GX_BINOP_LOGICAL_OR = 20, GX_BINOP_EQUAL = 21, GX_BINOP_NOT_EQUAL = 22, GX_BINOP_LESS = 23, GX_BINOP_GREATER = 24,
+  GX_BINOP_LESS_EQUAL = 25, GX_BINOP_GREATER_EQUAL = 26, GX_BINOP_NULL_EQUALS = 27, GX_BINOP_NULL_NOT_EQUALS = 28,
+  GX_BINOP_NULL_MAX = 29, GX_BINOP_NULL_MIN = 30, GX_BINOP_GENERIC_BINARY = 31, GX_BINOP_NULL_LOGICAL_AND = 32,
+  GX_BINOP_NULL_LOGICAL_OR = 33
+};
+enum gx_unop {
+  GX_UNOP_SIN = 0, GX_UNOP_COS = 1, GX_UNOP_TAN = 2, GX_UNOP_ARCSIN = 3, GX_UNOP_ARCCOS = 4, GX_UNOP_ARCTAN = 5, GX_UNOP_SINH = 6,
+  GX_UNOP_COSH = 7, GX_UNOP_TANH = 8, GX_UNOP_ARCSINH = 9, GX_UNOP_ARCCOSH = 10, GX_UNOP_ARCTANH = 11, GX_UNOP_EXP = 12,
+  GX_UNOP_LOG = 13, GX_UNOP_SQRT = 14, GX_UNOP_CBRT = 15, GX_UNOP_CEIL = 16, GX_UNOP_FLOOR = 17, GX_UNOP_ABS = 18,
+  GX_UNOP_RINT = 19, GX_UNOP_BIT_COUNT = 20, GX_UNOP_BIT_INVERT = 21, GX_UNOP_NOT = 22, GX_UNOP_NEGATE = 23,
+  GX_UNOP_IS_NAN = 100, GX_UNOP_IS_NOT_NAN = 101
+};
+int gx_binary_op(int op, int lhs_dtype, const void* lhs, const uint32_t* lhs_valid, int64_t lhs_begin_bit,
+                 const uint8_t* lhs_scalar_valid_dev, int lhs_is_scalar, int rhs_dtype, const void* rhs, const uint32_t* rhs_valid,
+                 int64_t rhs_begin_bit, const uint8_t* rhs_scalar_valid_dev, int rhs_is_scalar, int64_t n, int out_dtype, void* out,
+                 uint32_t* out_valid, int64_t* out_null_count_dev, gx_stream_t stream);
+int gx_unary_op(int op, int in_dtype, const void* in, int64_t n, int out_dtype, void* out, gx_stream_t stream);
+int gx_cast(int in_dtype, const void* in, int64_t n, int out_dtype, void* out, gx_stream_t stream);
+int gx_bitmask_to_bool8(const uint32_t* valid, int64_t begin_bit, int64_t n, int invert, uint8_t* out, gx_stream_t stream);
+int gx_binary_op_supported(int op, int lhs_dtype, int rhs_dtype, int out_dtype); /* host only: 1 / 0 */
+int gx_unary_op_supported(int op, int in_dtype, int out_dtype);                  /* host only: 1 / 0 */
+int gx_elementwise_tile_rows(void);                                              /* rows one workgroup owns per trip */
+int gx_elementwise_grid_cap(void);                                               /* most workgroups of one launch */
+
+/* ------------------------------------------------------------------------------------------
  * Hashing / partitioning.
  * gx_murmur3_32: cudf::hashing::detail::MurmurHash3_x86_32<T>
  * (include/cudf/hashing/detail/murmurhash3_x86_32.cuh:22-67), null -> UINT32_MAX, and the
