@@ -30,6 +30,26 @@ namespace gx {
 __host__ __device__ static inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 __host__ __device__ static inline int64_t div_up(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
+// blocks of a 1-D grid that covers n rows at rows_per_block each: at least 1, at most cap (grid-stride kernels take the rest)
+static inline unsigned capped_grid(int64_t n, int64_t rows_per_block, int64_t cap)
+{
+  const int64_t b = div_up(n, rows_per_block);
+  return (unsigned)(b > cap ? cap : (b < 1 ? 1 : b));
+}
+
+// f(T{}) with T the unsigned type of elem_size bytes (the host twin of rolling's with_type); GX_EDTYPE for any other size
+template <typename F>
+inline int with_width(int elem_size, F&& f)
+{
+  switch (elem_size) {
+    case 1: return f(uint8_t{});
+    case 2: return f(uint16_t{});
+    case 4: return f(uint32_t{});
+    case 8: return f(uint64_t{});
+    default: return GX_EDTYPE;
+  }
+}
+
 // carve helper for caller-provided scratch
 struct Carver {
   char* base;
@@ -598,15 +618,9 @@ __host__ __device__ __forceinline__ uint64_t splitmix64(uint64_t x)
   return x ^ (x >> 31);
 }
 
-// validity bitmap: LSB-first bits in uint32 words, 1 = valid (cudf/utilities/bit.hpp:47-61)
-__device__ __forceinline__ bool bit_is_set(const uint32_t* mask, int64_t i)
-{
-  return (mask[i >> 5] >> (i & 31)) & 1u;
-}
-__device__ __forceinline__ bool row_valid(const uint32_t* mask, int64_t i)
-{
-  return mask == nullptr || bit_is_set(mask, i);
-}
+}  // namespace gx
+#include "gx_validity.hpp"  // validity bitmaps: bit_is_set, row_valid, the word readers and writers of the value kernels
+namespace gx {
 
 // MurmurHash3_x86_32 finaliser / block (published algorithm; the reference delegates to
 // cuco::murmurhash3_32: include/cudf/hashing/detail/murmurhash3_x86_32.cuh:16,45)

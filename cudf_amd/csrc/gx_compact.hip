@@ -48,7 +48,7 @@ __global__ void __launch_bounds__(256) k_select_mask16(const uint8_t* __restrict
   } else if (r < n) {
     for (int j = 0; j < (int)(n - r); ++j) m16 |= (mask[r + j] != 0 ? 1u : 0u) << j;
   }
-  if (valid && r < n) m16 &= load_bits(valid, vbit0 + r, (n - r) < 16 ? (int)(n - r) : 16);
+  if (valid && r < n) m16 &= bits_from(valid, vbit0 + r, (n - r) < 16 ? (int)(n - r) : 16);
   uint64_t x = (uint64_t)m16 << (16 * (lane & 3u));
   x |= shfl_xor(x, 1);
   x |= shfl_xor(x, 2);
@@ -118,8 +118,7 @@ __global__ void __launch_bounds__(256) k_compact(const T* __restrict__ in, const
     const unsigned int s = wave_inclusive_scan(c, SumOp());
     s_row[threadIdx.x]   = s - c;
   }
-  if (threadIdx.x == 0) s_nulls = 0;
-  __syncthreads();
+  tally_begin(&s_nulls);  // (its barrier publishes s_row as well)
   const unsigned lane   = lane_id();
   const unsigned w      = threadIdx.x / GX_WAVE;
   const long long start = chunk_start[blockIdx.x];
@@ -148,11 +147,7 @@ __global__ void __launch_bounds__(256) k_compact(const T* __restrict__ in, const
       if (lane < 3 && part) atomicOr(&out_valid[(pos0 >> 5) + lane], part);  // set bits lie below the output's row count
     }
   }
-  if (HAS_VALID) {
-    if (lane == 0 && nulls) atomicAdd(&s_nulls, nulls);
-    __syncthreads();
-    if (threadIdx.x == 0 && s_nulls && out_nulls) atomicAdd(out_nulls, (unsigned long long)s_nulls);
-  }
+  if (HAS_VALID) tally_end(&s_nulls, nulls, out_nulls);
 }
 
 // The same scatter with the chunk's selected elements STAGED in LDS and written as whole 16-byte lanes (columns without a bitmap,
@@ -289,9 +284,7 @@ int compare_launch(const void* in, const uint32_t* valid, int64_t n, int cmp, ui
 {
   T sc;
   __builtin_memcpy(&sc, &scalar_bits, sizeof(T));  // the low bytes hold the scalar in the column's type
-  int64_t blocks = div_up(n, 256 * 8);
-  if (blocks > 8192) blocks = 8192;
-  hipLaunchKernelGGL((k_compare_scalar<T>), dim3((unsigned)blocks), dim3(256), 0, s, static_cast<const T*>(in), valid, n, cmp, sc, out);
+  hipLaunchKernelGGL((k_compare_scalar<T>), dim3(capped_grid(n, 256 * 8, 8192)), dim3(256), 0, s, static_cast<const T*>(in), valid, n, cmp, sc, out);
   GX_LAUNCH_CHECK();
   return 0;
 }
@@ -414,12 +407,9 @@ int gx_compact_column(int elem_size, const void* in, const uint32_t* in_valid, i
   if (out_null_count_dev) GX_HIP_TRY(hipMemsetAsync(out_null_count_dev, 0, sizeof(int64_t), s));
   if (n == 0) return 0;
   const Plan p = carve(sel_tmp, n);
-  switch (elem_size) {
-    case 1: return compact_launch<uint8_t>(in, in_valid, in_valid_begin_bit, n, p, out, out_valid, out_null_count_dev, s);
-    case 2: return compact_launch<uint16_t>(in, in_valid, in_valid_begin_bit, n, p, out, out_valid, out_null_count_dev, s);
-    case 4: return compact_launch<uint32_t>(in, in_valid, in_valid_begin_bit, n, p, out, out_valid, out_null_count_dev, s);
-    default: return compact_launch<uint64_t>(in, in_valid, in_valid_begin_bit, n, p, out, out_valid, out_null_count_dev, s);
-  }
+  return with_width(elem_size, [&](auto tag) {
+    return compact_launch<decltype(tag)>(in, in_valid, in_valid_begin_bit, n, p, out, out_valid, out_null_count_dev, s);
+  });
 }
 
 int gx_compact_indices(int64_t n, const void* sel_tmp, int32_t* out_idx, gx_stream_t stream)

@@ -31,16 +31,6 @@ static inline Plan carve(const void* tmp, int64_t n)
   return p;
 }
 
-// `count` (1..32) bits of an LSB-first bitmap from bit `bit` on; touches only the words that hold them
-__device__ __forceinline__ uint32_t load_bits(const uint32_t* m, int64_t bit, int count)
-{
-  const int64_t w = bit >> 5;
-  const int sh    = (int)(bit & 31);
-  uint32_t v      = m[w] >> sh;
-  if (sh + count > 32) v |= m[w + 1] << (32 - sh);
-  return count >= 32 ? v : (v & ((1u << count) - 1u));
-}
-
 // one row per lane, any predicate: wave w takes wave-rows w, w + 4, ... of the chunk
 template <typename Pred>
 __global__ void __launch_bounds__(256) k_select_pred(Pred pred, int64_t n, uint64_t* __restrict__ bits,

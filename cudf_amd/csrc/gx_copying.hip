@@ -61,17 +61,6 @@ __device__ __forceinline__ int concat_find(const long long* __restrict__ start, 
   return lo;
 }
 
-// cnt (1..32) bits of `m` from bit sb on, in the low bits of the result; no word behind the last needed one is read
-__device__ __forceinline__ uint32_t bits_from(const uint32_t* __restrict__ m, long long sb, int cnt)
-{
-  const long long w = sb >> 5;
-  const int sh      = (int)(sb & 31);
-  uint64_t two      = m[w];
-  if (sh + cnt > 32) two |= (uint64_t)m[w + 1] << 32;
-  const uint32_t v = (uint32_t)(two >> sh);
-  return cnt == 32 ? v : (v & ((1u << cnt) - 1u));
-}
-
 // The validity word of output rows [r0, r1) (r0 a multiple of 32, r1 - r0 <= 32) composed from every input that has rows
 // in it -- up to 32 of them, with any number of inputs without rows in between.  Bits from r1 - r0 on are 0.
 __device__ __forceinline__ uint32_t concat_word(const ConcatDesc& d, long long r0, long long r1)
@@ -84,7 +73,7 @@ __device__ __forceinline__ uint32_t concat_word(const ConcatDesc& d, long long r
     if (e > r) {
       const int cnt       = (int)(e - r);
       const uint32_t* m   = d.valid[k];
-      const uint32_t bits = m ? bits_from(m, d.bbit[k] + (r - d.start[k]), cnt) : (cnt == 32 ? 0xFFFFFFFFu : ((1u << cnt) - 1u));
+      const uint32_t bits = m ? bits_from(m, d.bbit[k] + (r - d.start[k]), cnt) : low_mask32(cnt);
       word |= bits << (int)(r - r0);
       r = e;
     }
@@ -121,28 +110,19 @@ __global__ void __launch_bounds__(COPY_BT) k_concat(ConcatDesc d, long long n, T
 
   // validity: thread j composes word j of the tile (CONCAT_TILE / 32 = 128 words, the first two waves)
   if (out_valid) {
-    if (null_count) {
-      if (t == 0) s_nulls = 0;
-      __syncthreads();
-    }
-    const long long r0 = t0 + (long long)t * 32;
+    if (null_count) tally_begin(&s_nulls);
+    const long long r0       = t0 + (long long)t * 32;
+    unsigned long long nulls = 0;
     if (t < CONCAT_TILE / 32) {  // whole waves: CONCAT_TILE / 32 is a multiple of 64
-      unsigned long long nulls = 0;
       if (r0 < t1) {
         const long long r1  = r0 + 32 < t1 ? r0 + 32 : t1;
         const uint32_t word = concat_word(d, r0, r1);
         out_valid[r0 >> 5]  = word;
         nulls               = (unsigned long long)((r1 - r0) - __builtin_popcount(word));
       }
-      if (null_count) {
-        nulls = wave_reduce(nulls, SumOp());
-        if (lane_id() == 0 && nulls) atomicAdd(&s_nulls, nulls);
-      }
+      if (null_count) nulls = wave_reduce(nulls, SumOp());
     }
-    if (null_count) {
-      __syncthreads();
-      if (t == 0 && s_nulls) atomicAdd(null_count, s_nulls);
-    }
+    if (null_count) tally_end(&s_nulls, nulls, null_count);
   }
 
   // data (out == NULL: the validity alone, concatenate_masks)
@@ -201,15 +181,15 @@ __device__ __forceinline__ void put_bit(uint32_t* mask, int64_t row, bool ok)
 // target[wrap(map[i])] = src[i] (scalar: src[0]).  BITS: the validity bit of every written row follows in the same pass -- right
 // when every candidate of a row carries the same validity (a scalar, or a source without nulls).
 template <typename T, bool BITS>
-__global__ void __launch_bounds__(COPY_BT) k_scatter(const T* __restrict__ src, const uint8_t* __restrict__ scalar_valid, int is_scalar,
-                                                     const int32_t* __restrict__ map, int64_t n, T* __restrict__ target,
+__global__ void __launch_bounds__(COPY_BT) k_scatter(ValueSrc from, const int32_t* __restrict__ map, int64_t n, T* __restrict__ target,
                                                      uint32_t* __restrict__ target_valid, int64_t target_rows)
 {
-  const int64_t stride = (int64_t)gridDim.x * COPY_BT;
-  const bool ok        = !(is_scalar && scalar_valid) || *scalar_valid != 0;
+  const T* __restrict__ src = static_cast<const T*>(from.data);
+  const int64_t stride      = (int64_t)gridDim.x * COPY_BT;
+  const bool ok             = from.scalar_ok();
   for (int64_t i = (int64_t)blockIdx.x * COPY_BT + threadIdx.x; i < n; i += stride) {
     const int64_t m = wrap_row(map[i], target_rows);
-    target[m]       = is_scalar ? src[0] : src[i];
+    target[m]       = from.is_scalar ? src[0] : src[i];
     if (BITS) put_bit(target_valid, m, ok);
   }
 }
@@ -230,26 +210,19 @@ __global__ void __launch_bounds__(COPY_BT) k_scatter_bits(const T* __restrict__ 
   }
 }
 
-static inline unsigned row_grid(int64_t n)
-{
-  int64_t b = div_up(n, COPY_BT * 4);
-  if (b > 8192) b = 8192;
-  if (b < 1) b = 1;
-  return (unsigned)b;
-}
+static inline unsigned copy_grid(int64_t n) { return capped_grid(n, COPY_BT * 4, 8192); }
 
 template <typename T>
 int scatter_launch(const void* src, const uint32_t* src_valid, int64_t src_begin_bit, const uint8_t* scalar_valid, int is_scalar,
                    const int32_t* map, int64_t n, void* target, uint32_t* target_valid, int64_t target_rows, hipStream_t s)
 {
-  const dim3 grid(row_grid(n)), block(COPY_BT);
+  const dim3 grid(copy_grid(n)), block(COPY_BT);
   const bool two_passes = target_valid && src_valid && !is_scalar;
+  const ValueSrc from{src, src_valid, src_begin_bit, scalar_valid, is_scalar};
   if (target_valid && !two_passes)
-    hipLaunchKernelGGL((k_scatter<T, true>), grid, block, 0, s, static_cast<const T*>(src), scalar_valid, is_scalar, map, n,
-                       static_cast<T*>(target), target_valid, target_rows);
+    hipLaunchKernelGGL((k_scatter<T, true>), grid, block, 0, s, from, map, n, static_cast<T*>(target), target_valid, target_rows);
   else
-    hipLaunchKernelGGL((k_scatter<T, false>), grid, block, 0, s, static_cast<const T*>(src), scalar_valid, is_scalar, map, n,
-                       static_cast<T*>(target), target_valid, target_rows);
+    hipLaunchKernelGGL((k_scatter<T, false>), grid, block, 0, s, from, map, n, static_cast<T*>(target), target_valid, target_rows);
   GX_LAUNCH_CHECK();
   if (two_passes) {
     hipLaunchKernelGGL((k_scatter_bits<T>), grid, block, 0, s, static_cast<const T*>(src), src_valid, src_begin_bit, map, n,
@@ -260,33 +233,10 @@ int scatter_launch(const void* src, const uint32_t* src_valid, int64_t src_begin
 }
 
 // ---------------------------------------------------------------- copy_if_else
-// 64 bits of `m` from bit b0 on for the wave whose rows start there; b0 is wave-uniform, so these are scalar loads.  Only words
-// that hold a bit below `end_bit` are read.
-__device__ __forceinline__ uint64_t wave_bits(const uint32_t* __restrict__ m, int64_t b0, int64_t end_bit)
-{
-  const int64_t w    = b0 >> 5;
-  const int sh       = (int)(b0 & 31);
-  const int64_t last = (end_bit - 1) >> 5;  // end_bit > b0
-  uint64_t lo        = m[w];
-  if (w + 1 <= last) lo |= (uint64_t)m[w + 1] << 32;
-  if (sh == 0) return lo;
-  uint64_t hi = 0;
-  if (w + 2 <= last) hi = m[w + 2];
-  return (lo >> sh) | (hi << (64 - sh));
-}
-
-struct Side {
-  const void* data;
-  const uint32_t* valid;
-  int64_t begin_bit;
-  const uint8_t* scalar_valid;
-  int is_scalar;
-};
-
 // out[i] = pick ? lhs[i] : rhs[i], pick = mask[i] != 0 and the mask's bit set.  One row per lane; a wave covers an aligned span of
-// 64 rows, reads its 64 bits of each bitmap once and writes two validity words.
+// 64 rows, reads its 64 bits of each bitmap once (bits_from64: scalar loads) and writes two validity words.
 template <typename T, bool HAS_VALID>
-__global__ void __launch_bounds__(COPY_BT) k_copy_if_else(Side lhs, Side rhs, const uint8_t* __restrict__ mask,
+__global__ void __launch_bounds__(COPY_BT) k_copy_if_else(ValueSrc lhs, ValueSrc rhs, const uint8_t* __restrict__ mask,
                                                           const uint32_t* __restrict__ mask_valid, int64_t mask_begin_bit, int64_t n,
                                                           T* __restrict__ out, uint32_t* __restrict__ out_valid,
                                                           unsigned long long* __restrict__ null_count)
@@ -294,12 +244,8 @@ __global__ void __launch_bounds__(COPY_BT) k_copy_if_else(Side lhs, Side rhs, co
   __shared__ unsigned long long s_nulls;
   const T* __restrict__ lp = static_cast<const T*>(lhs.data);
   const T* __restrict__ rp = static_cast<const T*>(rhs.data);
-  const bool l_ok = !(lhs.is_scalar && lhs.scalar_valid) || *lhs.scalar_valid != 0;
-  const bool r_ok = !(rhs.is_scalar && rhs.scalar_valid) || *rhs.scalar_valid != 0;
-  if (HAS_VALID && null_count) {
-    if (threadIdx.x == 0) s_nulls = 0;
-    __syncthreads();
-  }
+  const bool l_ok = lhs.scalar_ok(), r_ok = rhs.scalar_ok();
+  if (HAS_VALID && null_count) tally_begin(&s_nulls);
   const int64_t n64    = (n + 63) & ~int64_t(63);
   const int64_t stride = (int64_t)gridDim.x * COPY_BT;
   const unsigned lane  = lane_id();
@@ -312,7 +258,7 @@ __global__ void __launch_bounds__(COPY_BT) k_copy_if_else(Side lhs, Side rhs, co
     const bool live   = i < n;
     bool pick         = live && mask[i] != 0;
     uint64_t pickbits = ballot(pick);
-    if (mask_valid) pickbits &= wave_bits(mask_valid, mask_begin_bit + w0, mask_begin_bit + end);
+    if (mask_valid) pickbits &= bits_from64(mask_valid, mask_begin_bit + w0, mask_begin_bit + end);
     pick = (pickbits >> lane) & 1u;
     if (live) {
       const T l = lp[lhs.is_scalar ? 0 : i];
@@ -320,30 +266,21 @@ __global__ void __launch_bounds__(COPY_BT) k_copy_if_else(Side lhs, Side rhs, co
       out[i]    = pick ? l : r;
     }
     if (HAS_VALID) {
-      const uint64_t lbits = lhs.valid ? wave_bits(lhs.valid, lhs.begin_bit + w0, lhs.begin_bit + end) : (l_ok ? ~0ull : 0ull);
-      const uint64_t rbits = rhs.valid ? wave_bits(rhs.valid, rhs.begin_bit + w0, rhs.begin_bit + end) : (r_ok ? ~0ull : 0ull);
-      const uint64_t span  = end - w0 == 64 ? ~0ull : ((1ull << (end - w0)) - 1ull);
-      const uint64_t b     = ((pickbits & lbits) | (~pickbits & rbits)) & span;
-      if (lane == 0) {
-        const int64_t w = w0 >> 5;
-        out_valid[w]    = (uint32_t)b;
-        if (w + 1 < ((n + 31) >> 5)) out_valid[w + 1] = (uint32_t)(b >> 32);
-        nulls += (unsigned long long)__builtin_popcountll(~b & span);
-      }
+      // the bits of the span's rows; both are 0 from row `end` on, so the row's own bit decides alone
+      const uint64_t lbits = lhs.bits64(w0, end, l_ok), rbits = rhs.bits64(w0, end, r_ok);
+      const uint64_t b     = (pickbits & lbits) | (~pickbits & rbits);
+      store_wave_words(out_valid, w0, n, b);
+      nulls += (unsigned long long)((end - w0) - __builtin_popcountll(b));  // (wave-uniform: lane 0's count is the wave's)
     }
   }
-  if (HAS_VALID && null_count) {
-    if (lane == 0 && nulls) atomicAdd(&s_nulls, nulls);
-    __syncthreads();
-    if (threadIdx.x == 0 && s_nulls) atomicAdd(null_count, s_nulls);
-  }
+  if (HAS_VALID && null_count) tally_end(&s_nulls, nulls, null_count);
 }
 
 template <typename T>
-int copy_if_else_launch(const Side& lhs, const Side& rhs, const uint8_t* mask, const uint32_t* mask_valid, int64_t mask_begin_bit,
+int copy_if_else_launch(const ValueSrc& lhs, const ValueSrc& rhs, const uint8_t* mask, const uint32_t* mask_valid, int64_t mask_begin_bit,
                         int64_t n, void* out, uint32_t* out_valid, int64_t* nulls, hipStream_t s)
 {
-  const dim3 grid(row_grid(n)), block(COPY_BT);
+  const dim3 grid(copy_grid(n)), block(COPY_BT);
   if (out_valid)
     hipLaunchKernelGGL((k_copy_if_else<T, true>), grid, block, 0, s, lhs, rhs, mask, mask_valid, mask_begin_bit, n, static_cast<T*>(out),
                        out_valid, reinterpret_cast<unsigned long long*>(nulls));
@@ -409,12 +346,7 @@ int gx_concatenate(int elem_size, int ninputs, const void* const* cols_host, con
     GX_LAUNCH_CHECK();
   }
   const gx::ConcatDesc d{start, src, valid, bbit, ninputs};
-  switch (elem_size) {
-    case 1: return gx::concat_launch<uint8_t>(d, n, out, out_valid, out_null_count_dev, s);
-    case 2: return gx::concat_launch<uint16_t>(d, n, out, out_valid, out_null_count_dev, s);
-    case 4: return gx::concat_launch<uint32_t>(d, n, out, out_valid, out_null_count_dev, s);
-    default: return gx::concat_launch<uint64_t>(d, n, out, out_valid, out_null_count_dev, s);
-  }
+  return gx::with_width(elem_size, [&](auto tag) { return gx::concat_launch<decltype(tag)>(d, n, out, out_valid, out_null_count_dev, s); });
 }
 
 int gx_scatter(int elem_size, const void* src, const uint32_t* src_valid, int64_t src_begin_bit, const uint8_t* src_scalar_valid_dev,
@@ -426,12 +358,10 @@ int gx_scatter(int elem_size, const void* src, const uint32_t* src_valid, int64_
   if (n == 0) return 0;
   if (!src || !map || !target || target_rows == 0) return GX_EINVAL;
   if (src_is_scalar) src_valid = nullptr;
-  switch (elem_size) {
-    case 1: return gx::scatter_launch<uint8_t>(src, src_valid, src_begin_bit, src_scalar_valid_dev, src_is_scalar, map, n, target, target_valid, target_rows, s);
-    case 2: return gx::scatter_launch<uint16_t>(src, src_valid, src_begin_bit, src_scalar_valid_dev, src_is_scalar, map, n, target, target_valid, target_rows, s);
-    case 4: return gx::scatter_launch<uint32_t>(src, src_valid, src_begin_bit, src_scalar_valid_dev, src_is_scalar, map, n, target, target_valid, target_rows, s);
-    default: return gx::scatter_launch<uint64_t>(src, src_valid, src_begin_bit, src_scalar_valid_dev, src_is_scalar, map, n, target, target_valid, target_rows, s);
-  }
+  return gx::with_width(elem_size, [&](auto tag) {
+    return gx::scatter_launch<decltype(tag)>(src, src_valid, src_begin_bit, src_scalar_valid_dev, src_is_scalar, map, n, target, target_valid,
+                                             target_rows, s);
+  });
 }
 
 int gx_copy_if_else(int elem_size, const void* lhs, const uint32_t* lhs_valid, int64_t lhs_begin_bit, const uint8_t* lhs_scalar_valid_dev,
@@ -444,14 +374,11 @@ int gx_copy_if_else(int elem_size, const void* lhs, const uint32_t* lhs_valid, i
   if (n == 0) return 0;
   if (!lhs || !rhs || !mask_bool8 || !out) return GX_EINVAL;
   if (out_null_count_dev) GX_HIP_TRY(hipMemsetAsync(out_null_count_dev, 0, sizeof(int64_t), s));
-  const gx::Side l{lhs, lhs_is_scalar ? nullptr : lhs_valid, lhs_begin_bit, lhs_scalar_valid_dev, lhs_is_scalar};
-  const gx::Side r{rhs, rhs_is_scalar ? nullptr : rhs_valid, rhs_begin_bit, rhs_scalar_valid_dev, rhs_is_scalar};
-  switch (elem_size) {
-    case 1: return gx::copy_if_else_launch<uint8_t>(l, r, mask_bool8, mask_valid, mask_begin_bit, n, out, out_valid, out_null_count_dev, s);
-    case 2: return gx::copy_if_else_launch<uint16_t>(l, r, mask_bool8, mask_valid, mask_begin_bit, n, out, out_valid, out_null_count_dev, s);
-    case 4: return gx::copy_if_else_launch<uint32_t>(l, r, mask_bool8, mask_valid, mask_begin_bit, n, out, out_valid, out_null_count_dev, s);
-    default: return gx::copy_if_else_launch<uint64_t>(l, r, mask_bool8, mask_valid, mask_begin_bit, n, out, out_valid, out_null_count_dev, s);
-  }
+  const gx::ValueSrc l{lhs, lhs_is_scalar ? nullptr : lhs_valid, lhs_begin_bit, lhs_scalar_valid_dev, lhs_is_scalar};
+  const gx::ValueSrc r{rhs, rhs_is_scalar ? nullptr : rhs_valid, rhs_begin_bit, rhs_scalar_valid_dev, rhs_is_scalar};
+  return gx::with_width(elem_size, [&](auto tag) {
+    return gx::copy_if_else_launch<decltype(tag)>(l, r, mask_bool8, mask_valid, mask_begin_bit, n, out, out_valid, out_null_count_dev, s);
+  });
 }
 
 }  // extern "C"

@@ -152,18 +152,6 @@ __device__ __forceinline__ void store_rows(int dtype, void* p, int64_t row0, int
   }
 }
 
-// cnt (1..32) bits of `m` from bit sb on, in the low bits of the result; no word behind the last needed one is read
-// (bits_from of gx_copying.hip)
-__device__ __forceinline__ uint32_t ew_bits_from(const uint32_t* __restrict__ m, int64_t sb, int cnt)
-{
-  const int64_t w = sb >> 5;
-  const int sh    = (int)(sb & 31);
-  uint64_t two    = m[w];
-  if (sh + cnt > 32) two |= (uint64_t)m[w + 1] << 32;
-  const uint32_t v = (uint32_t)(two >> sh);
-  return cnt == 32 ? v : (v & ((1u << cnt) - 1u));
-}
-
 // ---------------------------------------------------------------- the operators on one pair of values of class C
 template <typename C>
 struct cls {
@@ -403,12 +391,7 @@ __device__ __forceinline__ uint32_t out_bits(int op, const C (&x)[R], const C (&
   }
 }
 
-struct Operand {
-  const void* data;
-  const uint32_t* valid;
-  int64_t begin_bit;
-  const uint8_t* scalar_valid;
-  int is_scalar;
+struct Operand : ValueSrc {
   int dtype;
 };
 
@@ -427,12 +410,8 @@ __global__ void __launch_bounds__(EW_BT) k_elementwise(int op, Operand lhs, Oper
   __shared__ unsigned long long s_nulls;
   const unsigned t    = threadIdx.x;
   const unsigned lane = lane_id();
-  const bool l_ok     = !(lhs.is_scalar && lhs.scalar_valid) || *lhs.scalar_valid != 0;
-  const bool r_ok     = !(rhs.is_scalar && rhs.scalar_valid) || *rhs.scalar_valid != 0;
-  if (null_count) {
-    if (t == 0) s_nulls = 0;
-    __syncthreads();
-  }
+  const bool l_ok     = lhs.scalar_ok(), r_ok = rhs.scalar_ok();
+  if (null_count) tally_begin(&s_nulls);
   unsigned long long nulls = 0;
   const int64_t tiles = div_up(n, EW_TILE);
   for (int64_t tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
@@ -445,8 +424,9 @@ __global__ void __launch_bounds__(EW_BT) k_elementwise(int op, Operand lhs, Oper
       const uint32_t lm = (1u << cnt) - 1u;      // cnt <= 16
       uint32_t lb = lm, rb = lm;
       if (out_valid && cnt > 0) {
-        lb = lhs.valid ? ew_bits_from(lhs.valid, lhs.begin_bit + row0, cnt) : (l_ok ? lm : 0u);
-        if (KIND != KIND_UNARY) rb = rhs.valid ? ew_bits_from(rhs.valid, rhs.begin_bit + row0, cnt) : (r_ok ? lm : 0u);
+        // (spelled out, not a member of ValueSrc: behind any wrapper k_elementwise<float, 2, REAL> takes a 101st SGPR and loses its 8th wave)
+        lb = lhs.valid ? bits_from(lhs.valid, lhs.begin_bit + row0, cnt) : (l_ok ? lm : 0u);
+        if (KIND != KIND_UNARY) rb = rhs.valid ? bits_from(rhs.valid, rhs.begin_bit + row0, cnt) : (r_ok ? lm : 0u);
       }
       uint32_t ob = 0;
       if (cnt > 0) {
@@ -473,12 +453,7 @@ __global__ void __launch_bounds__(EW_BT) k_elementwise(int op, Operand lhs, Oper
       }
     }
   }
-  if (null_count) {
-    nulls = wave_reduce(nulls, SumOp());
-    if (lane == 0 && nulls) atomicAdd(&s_nulls, nulls);
-    __syncthreads();
-    if (t == 0 && s_nulls) atomicAdd(null_count, s_nulls);
-  }
+  if (null_count) tally_end(&s_nulls, wave_reduce(nulls, SumOp()), null_count);
 }
 
 // out[i] = bit (begin_bit + i) of valid, inverted on request; 16 rows = one 16-byte store per thread
@@ -488,7 +463,7 @@ __global__ void __launch_bounds__(EW_BT) k_bitmask_to_bool8(const uint32_t* __re
   const int64_t stride = (int64_t)gridDim.x * EW_BT * 16;
   for (int64_t row0 = ((int64_t)blockIdx.x * EW_BT + threadIdx.x) * 16; row0 < n; row0 += stride) {
     const int cnt = n - row0 < 16 ? (int)(n - row0) : 16;
-    uint32_t b    = valid ? ew_bits_from(valid, begin_bit + row0, cnt) : 0xFFFFu;
+    uint32_t b    = valid ? bits_from(valid, begin_bit + row0, cnt) : 0xFFFFu;
     if (invert) b = ~b;
     Pack<uint8_t, 16> pk;
 #pragma unroll
@@ -539,9 +514,7 @@ template <typename C, int R, int KIND>
 int ew_launch(int op, const Operand& l, const Operand& r, int64_t n, int out_dtype, void* out, uint32_t* out_valid, int64_t* nulls,
               int lhs_bits, hipStream_t s)
 {
-  int64_t grid = div_up(n, EW_TILE);
-  if (grid > EW_GRID_CAP) grid = EW_GRID_CAP;
-  hipLaunchKernelGGL((k_elementwise<C, R, KIND>), dim3((unsigned)grid), dim3(EW_BT), 0, s, op, l, r, n, out_dtype, out, out_valid,
+  hipLaunchKernelGGL((k_elementwise<C, R, KIND>), dim3(capped_grid(n, EW_TILE, EW_GRID_CAP)), dim3(EW_BT), 0, s, op, l, r, n, out_dtype, out, out_valid,
                      reinterpret_cast<unsigned long long*>(nulls), lhs_bits);
   GX_LAUNCH_CHECK();
   return 0;
@@ -578,7 +551,7 @@ static inline int max3(int a, int b, int c) { return a > b ? (a > c ? a : c) : (
 
 static int unary_launch(int op, int in_dtype, const void* in, int64_t n, int out_dtype, void* out, hipStream_t s)
 {
-  const Operand l{in, nullptr, 0, nullptr, 0, in_dtype};
+  const Operand l{{in, nullptr, 0, nullptr, 0}, in_dtype};
   const int widest = dtype_bytes(in_dtype) > dtype_bytes(out_dtype) ? dtype_bytes(in_dtype) : dtype_bytes(out_dtype);
   return ew_dispatch<KIND_UNARY>(class_of_dtype(in_dtype), widest, op, l, l, n, out_dtype, out, nullptr, nullptr, 0, s);
 }
@@ -631,8 +604,8 @@ int gx_binary_op(int op, int lhs_dtype, const void* lhs, const uint32_t* lhs_val
   if (n == 0) return 0;
   if (!lhs || !rhs || !out) return GX_EINVAL;
   if (out_null_count_dev) GX_HIP_TRY(hipMemsetAsync(out_null_count_dev, 0, sizeof(int64_t), s));
-  const gx::Operand l{lhs, lhs_is_scalar ? nullptr : lhs_valid, lhs_begin_bit, lhs_scalar_valid_dev, lhs_is_scalar, lhs_dtype};
-  const gx::Operand r{rhs, rhs_is_scalar ? nullptr : rhs_valid, rhs_begin_bit, rhs_scalar_valid_dev, rhs_is_scalar, rhs_dtype};
+  const gx::Operand l{{lhs, lhs_is_scalar ? nullptr : lhs_valid, lhs_begin_bit, lhs_scalar_valid_dev, lhs_is_scalar}, lhs_dtype};
+  const gx::Operand r{{rhs, rhs_is_scalar ? nullptr : rhs_valid, rhs_begin_bit, rhs_scalar_valid_dev, rhs_is_scalar}, rhs_dtype};
   const int cl = gx::class_of_dtype(lhs_dtype), cr = gx::class_of_dtype(rhs_dtype);
   const int c  = cl > cr ? cl : cr;
   const int widest   = gx::max3(gx::dtype_bytes(lhs_dtype), gx::dtype_bytes(rhs_dtype), gx::dtype_bytes(out_dtype));
@@ -669,9 +642,7 @@ int gx_bitmask_to_bool8(const uint32_t* valid, int64_t begin_bit, int64_t n, int
   if (n < 0 || n > gx::EW_MAX_ROWS || begin_bit < 0) return GX_EINVAL;
   if (n == 0) return 0;
   if (!out) return GX_EINVAL;
-  int64_t grid = gx::div_up(n, gx::EW_TILE);
-  if (grid > gx::EW_GRID_CAP) grid = gx::EW_GRID_CAP;
-  hipLaunchKernelGGL(gx::k_bitmask_to_bool8, dim3((unsigned)grid), dim3(gx::EW_BT), 0, s, valid, begin_bit, n, invert, out);
+  hipLaunchKernelGGL(gx::k_bitmask_to_bool8, dim3(gx::capped_grid(n, gx::EW_TILE, gx::EW_GRID_CAP)), dim3(gx::EW_BT), 0, s, valid, begin_bit, n, invert, out);
   GX_LAUNCH_CHECK();
   return 0;
 }

@@ -30,14 +30,7 @@ __global__ void __launch_bounds__(GATHER_BT) k_gather(const T* __restrict__ src,
       }
       out[i] = v;
     }
-    if (HAS_VALID) {
-      const uint64_t b = ballot(ok);
-      if (lane_id() == 0) {
-        const int64_t w = i >> 5;  // i is a multiple of 64 here
-        out_valid[w]     = (uint32_t)b;
-        if (w + 1 < ((n + 31) >> 5)) out_valid[w + 1] = (uint32_t)(b >> 32);
-      }
-    }
+    if (HAS_VALID) store_wave_validity(out_valid, i & ~int64_t(63), n, ok);
   }
 }
 
@@ -45,32 +38,20 @@ template <typename T>
 int gather_launch(const void* src, const uint32_t* src_valid, int64_t src_rows, const int32_t* map, int64_t n,
                   int nullify_oob, void* out, uint32_t* out_valid, hipStream_t s)
 {
-  int64_t blocks = div_up(n, GATHER_BT * 4);
-  if (blocks > 8192) blocks = 8192;
-  if (blocks < 1) blocks = 1;
+  const dim3 grid(capped_grid(n, GATHER_BT * 4, 8192));
   if (out_valid)
-    hipLaunchKernelGGL((k_gather<T, true>), dim3((unsigned)blocks), dim3(GATHER_BT), 0, s,
+    hipLaunchKernelGGL((k_gather<T, true>), grid, dim3(GATHER_BT), 0, s,
                        static_cast<const T*>(src), src_valid, src_rows, map, n, nullify_oob, static_cast<T*>(out),
                        out_valid);
   else
-    hipLaunchKernelGGL((k_gather<T, false>), dim3((unsigned)blocks), dim3(GATHER_BT), 0, s,
+    hipLaunchKernelGGL((k_gather<T, false>), grid, dim3(GATHER_BT), 0, s,
                        static_cast<const T*>(src), src_valid, src_rows, map, n, nullify_oob, static_cast<T*>(out),
                        out_valid);
   GX_LAUNCH_CHECK();
   return 0;
 }
 
-// ---------------------------------------------------------------- bitmask kernels
-__device__ __forceinline__ uint32_t word_range_mask(int64_t w, int64_t begin_bit, int64_t end_bit)
-{
-  const int64_t lo = w * 32, hi = lo + 32;
-  if (hi <= begin_bit || lo >= end_bit) return 0u;
-  uint32_t m = 0xFFFFFFFFu;
-  if (begin_bit > lo) m &= 0xFFFFFFFFu << (begin_bit - lo);
-  if (end_bit < hi) m &= 0xFFFFFFFFu >> (hi - end_bit);
-  return m;
-}
-
+// ---------------------------------------------------------------- bitmask kernels (word_range_mask, bits_from: gx_validity.hpp)
 __global__ void __launch_bounds__(256) k_bitmask_set(uint32_t* mask, int64_t begin_bit, int64_t end_bit, int valid)
 {
   const int64_t w0 = begin_bit >> 5, w1 = (end_bit + 31) >> 5;
@@ -140,17 +121,9 @@ __global__ void __launch_bounds__(256) k_bitmask_copy(uint32_t* __restrict__ dst
   for (int64_t w = w0 + (int64_t)blockIdx.x * 256 + threadIdx.x; w < w1; w += stride) {
     const int64_t lo = (w << 5) > dst_begin ? (w << 5) : dst_begin;                                  // first dst bit of this word
     const int64_t hi = ((w + 1) << 5) < dst_begin + nbits ? ((w + 1) << 5) : dst_begin + nbits;      // one past the last
-    const uint32_t m = (hi - lo == 32) ? 0xFFFFFFFFu : (((1u << (hi - lo)) - 1u) << (lo & 31));
+    const uint32_t m = low_mask32((int)(hi - lo)) << (lo & 31);
     uint32_t v       = 0xFFFFFFFFu;
-    if (src) {
-      const int64_t sb  = src_begin + (lo - dst_begin);  // source bit that lands on dst bit `lo`
-      const int64_t sw  = sb >> 5;
-      const unsigned sh = (unsigned)(sb & 31);
-      const int64_t send = (src_begin + nbits + 31) >> 5;
-      uint64_t two = src[sw];
-      if (sh && sw + 1 < send) two |= (uint64_t)src[sw + 1] << 32;
-      v = (uint32_t)(two >> sh) << (lo & 31);
-    }
+    if (src) v = bits_from(src, src_begin + (lo - dst_begin), (int)(hi - lo)) << (lo & 31);  // the source bit that lands on dst bit `lo`
     if (m == 0xFFFFFFFFu) {
       dst[w] = v;
     } else {
@@ -160,13 +133,7 @@ __global__ void __launch_bounds__(256) k_bitmask_copy(uint32_t* __restrict__ dst
   }
 }
 
-static inline unsigned word_grid(int64_t nwords)
-{
-  int64_t b = div_up(nwords, 256 * 4);
-  if (b > 4096) b = 4096;
-  if (b < 1) b = 1;
-  return (unsigned)b;
-}
+static inline unsigned mask_grid(int64_t nwords) { return capped_grid(nwords, 256 * 4, 4096); }
 
 }  // namespace gx
 
@@ -277,9 +244,8 @@ int gx_gather_global_rows_dev(const int32_t* rows, int64_t nrows, const int32_t*
   if (n < 0 || nrows < 0 || nseg < 1 || !segtab_dev) return GX_EINVAL;
   if (n == 0) return 0;
   if (!rows || !idx || !out) return GX_EINVAL;
-  int64_t blocks = gx::div_up(n, (int64_t)256 * 4);
-  if (blocks > 16384) blocks = 16384;
-  hipLaunchKernelGGL(gx::k_gather_global_rows_dev, dim3((unsigned)blocks), dim3(256), 0, s, rows, idx, n, nseg,
+  const unsigned blocks = gx::capped_grid(n, 256 * 4, 16384);
+  hipLaunchKernelGGL(gx::k_gather_global_rows_dev, dim3(blocks), dim3(256), 0, s, rows, idx, n, nseg,
                      reinterpret_cast<const long long*>(segtab_dev), reinterpret_cast<long long*>(out));
   GX_LAUNCH_CHECK();
   return 0;
@@ -291,9 +257,8 @@ int gx_decode_global_rows(const int32_t* enc, int64_t n, int shift, const int64_
   if (n < 0 || shift < 1 || shift > 31 || !bases_dev || (snap_dev && (!chunk_rows_dev || nchunks < 1 || nchunks > gx::DEC_MAXCH))) return GX_EINVAL;
   if (n == 0) return 0;
   if (!enc || !out) return GX_EINVAL;
-  int64_t blocks = gx::div_up(n, (int64_t)256 * 8);
-  if (blocks > 8192) blocks = 8192;
-  hipLaunchKernelGGL(gx::k_decode_global_rows, dim3((unsigned)blocks), dim3(256), 0, s, enc, n, shift, reinterpret_cast<const long long*>(bases_dev),
+  const unsigned blocks = gx::capped_grid(n, 256 * 8, 8192);
+  hipLaunchKernelGGL(gx::k_decode_global_rows, dim3(blocks), dim3(256), 0, s, enc, n, shift, reinterpret_cast<const long long*>(bases_dev),
                      reinterpret_cast<const long long*>(chunk_rows_dev), reinterpret_cast<const long long*>(snap_dev), nchunks,
                      reinterpret_cast<long long*>(out));
   GX_LAUNCH_CHECK();
@@ -304,9 +269,8 @@ int gx_widen_i32_i64(const int32_t* in, int64_t n, int64_t* out, gx_stream_t s)
 {
   if (n < 0 || (n > 0 && (!in || !out))) return GX_EINVAL;
   if (n == 0) return 0;
-  int64_t blocks = gx::div_up(n, (int64_t)256 * 8);
-  if (blocks > 8192) blocks = 8192;
-  hipLaunchKernelGGL(gx::k_widen_i32_i64, dim3((unsigned)blocks), dim3(256), 0, s, in, n, reinterpret_cast<long long*>(out));
+  const unsigned blocks = gx::capped_grid(n, 256 * 8, 8192);
+  hipLaunchKernelGGL(gx::k_widen_i32_i64, dim3(blocks), dim3(256), 0, s, in, n, reinterpret_cast<long long*>(out));
   GX_LAUNCH_CHECK();
   return 0;
 }
@@ -327,9 +291,8 @@ int gx_gather_global_rows(const int32_t* rows, int64_t nrows, const int32_t* idx
   sb.start[nseg] = run;
   sb.nseg        = nseg;
   if (run != nrows) return GX_EINVAL;
-  int64_t blocks = gx::div_up(n, (int64_t)256 * 4);
-  if (blocks > 16384) blocks = 16384;
-  hipLaunchKernelGGL(gx::k_gather_global_rows, dim3((unsigned)blocks), dim3(256), 0, s, rows, idx, n, sb, reinterpret_cast<long long*>(out));
+  const unsigned blocks = gx::capped_grid(n, 256 * 4, 16384);
+  hipLaunchKernelGGL(gx::k_gather_global_rows, dim3(blocks), dim3(256), 0, s, rows, idx, n, sb, reinterpret_cast<long long*>(out));
   GX_LAUNCH_CHECK();
   return 0;
 }
@@ -340,13 +303,7 @@ int gx_gather(int elem_size, const void* src, const uint32_t* src_valid, int64_t
   if (n < 0 || src_rows < 0) return GX_EINVAL;
   if (n == 0) return 0;
   if (!map || !out || (!src && src_rows > 0)) return GX_EINVAL;
-  switch (elem_size) {
-    case 1: return gx::gather_launch<uint8_t>(src, src_valid, src_rows, map, n, nullify_oob, out, out_valid, s);
-    case 2: return gx::gather_launch<uint16_t>(src, src_valid, src_rows, map, n, nullify_oob, out, out_valid, s);
-    case 4: return gx::gather_launch<uint32_t>(src, src_valid, src_rows, map, n, nullify_oob, out, out_valid, s);
-    case 8: return gx::gather_launch<uint64_t>(src, src_valid, src_rows, map, n, nullify_oob, out, out_valid, s);
-    default: return GX_EDTYPE;
-  }
+  return gx::with_width(elem_size, [&](auto tag) { return gx::gather_launch<decltype(tag)>(src, src_valid, src_rows, map, n, nullify_oob, out, out_valid, s); });
 }
 
 int gx_bitmask_set(uint32_t* mask, int64_t begin_bit, int64_t end_bit, int valid, gx_stream_t s)
@@ -355,7 +312,7 @@ int gx_bitmask_set(uint32_t* mask, int64_t begin_bit, int64_t end_bit, int valid
   if (end_bit == begin_bit) return 0;
   if (!mask) return GX_EINVAL;
   const int64_t nw = ((end_bit + 31) >> 5) - (begin_bit >> 5);
-  hipLaunchKernelGGL(gx::k_bitmask_set, dim3(gx::word_grid(nw)), dim3(256), 0, s, mask, begin_bit, end_bit, valid);
+  hipLaunchKernelGGL(gx::k_bitmask_set, dim3(gx::mask_grid(nw)), dim3(256), 0, s, mask, begin_bit, end_bit, valid);
   GX_LAUNCH_CHECK();
   return 0;
 }
@@ -370,7 +327,7 @@ int gx_bitmask_count(const uint32_t* mask, int64_t begin_bit, int64_t end_bit, i
   ml.m[0]  = mask;
   ml.count = 1;
   const int64_t nw = ((end_bit + 31) >> 5) - (begin_bit >> 5);
-  hipLaunchKernelGGL(gx::k_bitmask_and_count, dim3(gx::word_grid(nw)), dim3(256), 0, s, ml, begin_bit, end_bit,
+  hipLaunchKernelGGL(gx::k_bitmask_and_count, dim3(gx::mask_grid(nw)), dim3(256), 0, s, ml, begin_bit, end_bit,
                      (uint32_t*)nullptr, reinterpret_cast<unsigned long long*>(count_dev));
   GX_LAUNCH_CHECK();
   return 0;
@@ -387,7 +344,7 @@ int gx_bitmask_and(const uint32_t* const* masks_host, int nmasks, int64_t nbits,
   ml.count = nmasks;
   for (int k = 0; k < nmasks; ++k) ml.m[k] = masks_host[k];
   const int64_t nw = (nbits + 31) >> 5;
-  hipLaunchKernelGGL(gx::k_bitmask_and_count, dim3(gx::word_grid(nw)), dim3(256), 0, s, ml, (int64_t)0, nbits, out,
+  hipLaunchKernelGGL(gx::k_bitmask_and_count, dim3(gx::mask_grid(nw)), dim3(256), 0, s, ml, (int64_t)0, nbits, out,
                      reinterpret_cast<unsigned long long*>(count_dev));
   GX_LAUNCH_CHECK();
   return 0;
@@ -399,7 +356,7 @@ int gx_bitmask_copy(uint32_t* dst, int64_t dst_begin_bit, const uint32_t* src, i
   if (nbits < 0 || dst_begin_bit < 0 || src_begin_bit < 0 || (nbits > 0 && !dst)) return GX_EINVAL;
   if (nbits == 0) return 0;
   const int64_t nw = ((dst_begin_bit + nbits + 31) >> 5) - (dst_begin_bit >> 5);
-  hipLaunchKernelGGL(gx::k_bitmask_copy, dim3(gx::word_grid(nw)), dim3(256), 0, s, dst, dst_begin_bit, src, src_begin_bit,
+  hipLaunchKernelGGL(gx::k_bitmask_copy, dim3(gx::mask_grid(nw)), dim3(256), 0, s, dst, dst_begin_bit, src, src_begin_bit,
                      nbits);
   GX_LAUNCH_CHECK();
   return 0;
@@ -412,7 +369,7 @@ int gx_bitmask_first_unset(const uint32_t* mask, int64_t nbits, int64_t* pos_dev
                      (unsigned long long)nbits);
   if (nbits == 0 || !mask) return 0;
   const int64_t nw = (nbits + 31) >> 5;
-  hipLaunchKernelGGL(gx::k_first_unset, dim3(gx::word_grid(nw)), dim3(256), 0, s, mask, nbits,
+  hipLaunchKernelGGL(gx::k_first_unset, dim3(gx::mask_grid(nw)), dim3(256), 0, s, mask, nbits,
                      reinterpret_cast<unsigned long long*>(pos_dev));
   GX_LAUNCH_CHECK();
   return 0;

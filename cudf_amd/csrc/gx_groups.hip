@@ -35,9 +35,7 @@ __global__ void __launch_bounds__(256) k_heads(const U* __restrict__ col, const 
 template <typename U, int KIND>
 int heads_launch(const void* col, const uint32_t* valid, const int32_t* order, int64_t n, int combine, uint8_t* heads, hipStream_t s)
 {
-  int64_t blocks = div_up(n, 256 * 8);
-  if (blocks > 8192) blocks = 8192;
-  hipLaunchKernelGGL((k_heads<U, KIND>), dim3((unsigned)blocks), dim3(256), 0, s, static_cast<const U*>(col), valid, order, n,
+  hipLaunchKernelGGL((k_heads<U, KIND>), dim3(capped_grid(n, 256 * 8, 8192)), dim3(256), 0, s, static_cast<const U*>(col), valid, order, n,
                      combine, heads);
   GX_LAUNCH_CHECK();
   return 0;
@@ -93,11 +91,7 @@ __global__ void __launch_bounds__(256) k_seg_shift(const T* __restrict__ in, con
       }
       out[i] = v;
     }
-    const uint64_t b = ballot(ok);
-    if (out_valid && lane == 0) {
-      out_valid[2 * r] = (uint32_t)b;
-      if ((2 * r + 1) * 32 < n) out_valid[2 * r + 1] = (uint32_t)(b >> 32);
-    }
+    if (out_valid) store_wave_validity(out_valid, r * GX_WAVE, n, ok);
   }
 }
 
@@ -148,11 +142,7 @@ __global__ void __launch_bounds__(256) k_fill_from(const T* __restrict__ in, con
       ok              = j >= 0;
       out[i]          = ok ? in[j] : in[i];
     }
-    const uint64_t b = ballot(ok);
-    if (lane == 0) {
-      out_valid[2 * r] = (uint32_t)b;
-      if ((2 * r + 1) * 32 < n) out_valid[2 * r + 1] = (uint32_t)(b >> 32);
-    }
+    store_wave_validity(out_valid, r * GX_WAVE, n, ok);
   }
 }
 
@@ -202,13 +192,7 @@ __global__ void __launch_bounds__(256) k_segment_ids(const int32_t* __restrict__
   }
 }
 
-static inline unsigned grid_for(int64_t n, int per = 256 * 4)
-{
-  int64_t b = div_up(n, per);
-  if (b > 16384) b = 16384;
-  if (b < 1) b = 1;
-  return (unsigned)b;
-}
+static inline unsigned rows_grid(int64_t n) { return capped_grid(n, 256 * 4, 16384); }
 
 }  // namespace grp
 }  // namespace gx
@@ -260,11 +244,11 @@ int gx_group_offsets(const uint8_t* heads, int64_t n, int32_t* labels, int32_t* 
   if (!heads || !labels || !offsets) return GX_EINVAL;
   int rc = scan::device_scan<int32_t, int32_t>(HeadLoader{heads}, n, 0, SumOp(), true, labels, partials, s);
   if (rc) return rc;
-  hipLaunchKernelGGL(k_offsets, dim3(grid_for(n)), dim3(256), 0, s, heads, labels, n, offsets, reinterpret_cast<long long*>(ngroups_dev));
+  hipLaunchKernelGGL(k_offsets, dim3(rows_grid(n)), dim3(256), 0, s, heads, labels, n, offsets, reinterpret_cast<long long*>(ngroups_dev));
   if (sizes) {
     // the group count is on the device: cover the worst case (n groups), rows beyond it read offsets that k_offsets wrote
     // for smaller indices only -- so bound the launch by reading the count on the device
-    hipLaunchKernelGGL(k_sizes, dim3(grid_for(n)), dim3(256), 0, s, offsets, n, sizes);
+    hipLaunchKernelGGL(k_sizes, dim3(rows_grid(n)), dim3(256), 0, s, offsets, n, sizes);
   }
   GX_LAUNCH_CHECK();
   return 0;
@@ -276,18 +260,14 @@ int gx_segmented_shift(int elem_size, const void* in, const uint32_t* in_valid, 
   using namespace gx::grp;
   if (n < 0 || (n > 0 && (!in || !labels || !out))) return GX_EINVAL;
   if (n == 0) return 0;
-  const unsigned grid = grid_for(n, 256 * 4);
-#define GX_SHIFT(T) hipLaunchKernelGGL((k_seg_shift<T>), dim3(grid), dim3(256), 0, s, static_cast<const T*>(in), in_valid, labels, n, offset, (T)fill_bits, fill_valid, static_cast<T*>(out), out_valid); break
-  switch (elem_size) {
-    case 1: GX_SHIFT(uint8_t);
-    case 2: GX_SHIFT(uint16_t);
-    case 4: GX_SHIFT(uint32_t);
-    case 8: GX_SHIFT(uint64_t);
-    default: return GX_EDTYPE;
-  }
-#undef GX_SHIFT
-  GX_LAUNCH_CHECK();
-  return 0;
+  const unsigned grid = rows_grid(n);
+  return gx::with_width(elem_size, [&](auto tag) {
+    using T = decltype(tag);
+    hipLaunchKernelGGL((k_seg_shift<T>), dim3(grid), dim3(256), 0, s, static_cast<const T*>(in), in_valid, labels, n, offset, (T)fill_bits,
+                       fill_valid, static_cast<T*>(out), out_valid);
+    GX_LAUNCH_CHECK();
+    return 0;
+  });
 }
 
 int gx_segmented_fill_nulls(int elem_size, const void* in, const uint32_t* in_valid, const uint8_t* heads, int64_t n, int backward,
@@ -308,18 +288,13 @@ int gx_segmented_fill_nulls(int elem_size, const void* in, const uint32_t* in_va
   if (!in || !heads || !out || !out_valid) return GX_EINVAL;
   int rc = scan::device_scan<SrcSeg, SrcOut>(SrcLoader{in_valid, heads, n, backward}, n, SrcSeg{-1, 0u}, SrcOp(), true, src, partials, s);
   if (rc) return rc;
-  const unsigned grid = grid_for(n, 256 * 4);
-#define GX_FILL(T) hipLaunchKernelGGL((k_fill_from<T>), dim3(grid), dim3(256), 0, s, static_cast<const T*>(in), src, n, backward, static_cast<T*>(out), out_valid); break
-  switch (elem_size) {
-    case 1: GX_FILL(uint8_t);
-    case 2: GX_FILL(uint16_t);
-    case 4: GX_FILL(uint32_t);
-    case 8: GX_FILL(uint64_t);
-    default: return GX_EDTYPE;
-  }
-#undef GX_FILL
-  GX_LAUNCH_CHECK();
-  return 0;
+  const unsigned grid = rows_grid(n);
+  return with_width(elem_size, [&](auto tag) {
+    using T = decltype(tag);
+    hipLaunchKernelGGL((k_fill_from<T>), dim3(grid), dim3(256), 0, s, static_cast<const T*>(in), src, n, backward, static_cast<T*>(out), out_valid);
+    GX_LAUNCH_CHECK();
+    return 0;
+  });
 }
 
 int gx_rank_from_groups(const int32_t* order, const int32_t* labels, const int32_t* offsets, int64_t n, int method, double scale,
@@ -328,7 +303,7 @@ int gx_rank_from_groups(const int32_t* order, const int32_t* labels, const int32
   using namespace gx::grp;
   if (n < 0 || method < 0 || method > 4 || (n > 0 && ((method != 0 && (!labels || !offsets)) || (!out_i32 && !out_f64)))) return GX_EINVAL;
   if (n == 0) return 0;
-  hipLaunchKernelGGL(k_rank, dim3(grid_for(n)), dim3(256), 0, s, order, labels, offsets, n, method, scale, one_normalized, out_i32,
+  hipLaunchKernelGGL(k_rank, dim3(rows_grid(n)), dim3(256), 0, s, order, labels, offsets, n, method, scale, one_normalized, out_i32,
                      out_f64);
   GX_LAUNCH_CHECK();
   return 0;
@@ -339,7 +314,7 @@ int gx_segment_ids(const int32_t* offsets, int64_t num_offsets, int64_t num_rows
   using namespace gx::grp;
   if (num_offsets < 0 || num_rows < 0 || (num_rows > 0 && !ids) || (num_offsets > 0 && !offsets)) return GX_EINVAL;
   if (num_rows == 0) return 0;
-  hipLaunchKernelGGL(k_segment_ids, dim3(grid_for(num_rows)), dim3(256), 0, s, offsets, num_offsets, num_rows, ids);
+  hipLaunchKernelGGL(k_segment_ids, dim3(rows_grid(num_rows)), dim3(256), 0, s, offsets, num_offsets, num_rows, ids);
   GX_LAUNCH_CHECK();
   return 0;
 }

@@ -234,7 +234,6 @@ __global__ void __launch_bounds__(256) k_gather2(const T* __restrict__ a, const 
 {
   constexpr int ROUNDS = 4;  // 1024 rows per workgroup, a wave owns whole 64-row groups (two validity words)
   const int64_t base   = (int64_t)blockIdx.x * (256 * ROUNDS);
-  const int64_t nwords = (n + 31) >> 5;
   uint32_t nulls       = 0;
 #pragma unroll
   for (int r = 0; r < ROUNDS; ++r) {
@@ -254,12 +253,8 @@ __global__ void __launch_bounds__(256) k_gather2(const T* __restrict__ a, const 
       out[row] = v;
     }
     if (out_valid) {  // (wave-uniform)
-      const uint64_t bal = ballot(ok);
-      const int64_t w    = (row & ~(int64_t)63) >> 5;
-      const unsigned l   = lane_id();
-      if (l == 0 && w < nwords) out_valid[w] = (uint32_t)bal;
-      if (l == 32 && w + 1 < nwords) out_valid[w + 1] = (uint32_t)(bal >> 32);
-      if (l == 0) {
+      const uint64_t bal = store_wave_validity(out_valid, row & ~(int64_t)63, n, ok);
+      if (lane_id() == 0) {
         const int64_t first = row, left = n - first;  // lane 0's row is the group's first
         const int live      = left >= 64 ? 64 : (left > 0 ? (int)left : 0);
         nulls += (uint32_t)(live - __builtin_popcountll(bal));
@@ -386,14 +381,11 @@ int gx_gather2(int elem_size, const void* a, const uint32_t* a_valid, int64_t a_
   hipStream_t s = (hipStream_t)stream;
   if (out_null_count_dev) GX_HIP_TRY(hipMemsetAsync(out_null_count_dev, 0, sizeof(int64_t), s));
   if (n == 0) return 0;
-  switch (elem_size) {
-    case 1: launch_gather2<uint8_t>(a, a_valid, a_begin_bit, na, b, b_valid, b_begin_bit, nb, map, n, out, out_valid, out_null_count_dev, s); break;
-    case 2: launch_gather2<uint16_t>(a, a_valid, a_begin_bit, na, b, b_valid, b_begin_bit, nb, map, n, out, out_valid, out_null_count_dev, s); break;
-    case 4: launch_gather2<uint32_t>(a, a_valid, a_begin_bit, na, b, b_valid, b_begin_bit, nb, map, n, out, out_valid, out_null_count_dev, s); break;
-    default: launch_gather2<uint64_t>(a, a_valid, a_begin_bit, na, b, b_valid, b_begin_bit, nb, map, n, out, out_valid, out_null_count_dev, s); break;
-  }
-  GX_LAUNCH_CHECK();
-  return 0;
+  return with_width(elem_size, [&](auto tag) {
+    launch_gather2<decltype(tag)>(a, a_valid, a_begin_bit, na, b, b_valid, b_begin_bit, nb, map, n, out, out_valid, out_null_count_dev, s);
+    GX_LAUNCH_CHECK();
+    return 0;
+  });
 }
 
 }  // extern "C"

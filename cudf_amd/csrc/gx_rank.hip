@@ -86,14 +86,7 @@ __global__ void __launch_bounds__(256) k_fill_nulls(T* __restrict__ data, const 
     if (!bit_is_set(valid, i)) data[i] = value;
 }
 
-static inline unsigned grid_for(int64_t n)
-{
-  int64_t b = div_up(n, (int64_t)256 * 4);
-  if (b > 16384) b = 16384;
-  if (b < 1) b = 1;
-  return (unsigned)b;
-}
-
+static inline unsigned rows_grid(int64_t n) { return capped_grid(n, 256 * 4, 16384); }
 
 // inverse of k_pack: column k of row i = bits [shift_k, shift_k + 8 width_k) of packed[i]; c.col are the OUTPUT columns
 __global__ void __launch_bounds__(256) k_unpack(Cols c, Shifts sh, int64_t n, const uint64_t* __restrict__ packed)
@@ -172,7 +165,7 @@ int gx_pack_keys(int ncols, const void* const* cols, const int* dtypes, int64_t 
   if (int rc = gx::rank::fill_cols(c, ncols, cols, dtypes, n)) return rc;
   if (int rc = gx::rank::fill_shifts(c, sh)) return rc;
   if (n == 0) return 0;
-  hipLaunchKernelGGL(gx::rank::k_pack, dim3(gx::rank::grid_for(n)), dim3(256), 0, s, c, sh, n, out);
+  hipLaunchKernelGGL(gx::rank::k_pack, dim3(gx::rank::rows_grid(n)), dim3(256), 0, s, c, sh, n, out);
   GX_LAUNCH_CHECK();
   return 0;
 }
@@ -185,7 +178,7 @@ int gx_unpack_keys(int ncols, void* const* out_cols, const int* dtypes, int64_t 
   if (int rc = gx::rank::fill_cols(c, ncols, out_cols, dtypes, n)) return rc;
   if (int rc = gx::rank::fill_shifts(c, sh)) return rc;
   if (n == 0) return 0;
-  hipLaunchKernelGGL(gx::rank::k_unpack, dim3(gx::rank::grid_for(n)), dim3(256), 0, s, c, sh, n, packed);
+  hipLaunchKernelGGL(gx::rank::k_unpack, dim3(gx::rank::rows_grid(n)), dim3(256), 0, s, c, sh, n, packed);
   GX_LAUNCH_CHECK();
   return 0;
 }
@@ -196,7 +189,7 @@ int gx_hash_rows64(int ncols, const void* const* cols, const int* dtypes, int64_
   gx::rank::Cols c;
   if (int rc = gx::rank::fill_cols(c, ncols, cols, dtypes, n)) return rc;
   if (n == 0) return 0;
-  hipLaunchKernelGGL(gx::rank::k_hash_rows, dim3(gx::rank::grid_for(n)), dim3(256), 0, s, c, n, seed, out);
+  hipLaunchKernelGGL(gx::rank::k_hash_rows, dim3(gx::rank::rows_grid(n)), dim3(256), 0, s, c, n, seed, out);
   GX_LAUNCH_CHECK();
   return 0;
 }
@@ -210,7 +203,7 @@ int gx_rows_mismatch_count(int ncols, const void* const* lcols, const void* cons
   if (int rc = gx::rank::fill_cols(r, ncols, rcols, dtypes, npairs)) return rc;
   GX_HIP_TRY(hipMemsetAsync(mismatch_dev, 0, sizeof(int64_t), s));
   if (npairs == 0) return 0;
-  hipLaunchKernelGGL(gx::rank::k_rows_mismatch, dim3(gx::rank::grid_for(npairs)), dim3(256), 0, s, l, r, lidx, ridx, npairs,
+  hipLaunchKernelGGL(gx::rank::k_rows_mismatch, dim3(gx::rank::rows_grid(npairs)), dim3(256), 0, s, l, r, lidx, ridx, npairs,
                      reinterpret_cast<unsigned long long*>(mismatch_dev));
   GX_LAUNCH_CHECK();
   return 0;
@@ -220,7 +213,7 @@ int gx_fill_nulls(int elem_size, void* data, const uint32_t* valid, int64_t n, u
 {
   if (n < 0 || (n > 0 && !data)) return GX_EINVAL;
   if (n == 0 || !valid) return 0;
-  const unsigned g = gx::rank::grid_for(n);
+  const unsigned g = gx::rank::rows_grid(n);
   switch (elem_size) {
     case 1: hipLaunchKernelGGL((gx::rank::k_fill_nulls<uint8_t>), dim3(g), dim3(256), 0, s, static_cast<uint8_t*>(data), valid, n, (uint8_t)value_bits); break;
     case 2: hipLaunchKernelGGL((gx::rank::k_fill_nulls<uint16_t>), dim3(g), dim3(256), 0, s, static_cast<uint16_t*>(data), valid, n, (uint16_t)value_bits); break;
@@ -268,7 +261,7 @@ int gx_dense_rank(int dtype, const void* keys, const uint32_t* valid, int64_t n,
   rc = gx_sorted_order(dtype, keys, v, n, v ? null_count : 0, 0, /*nulls_before=*/0, order, sub, &sort_bytes, s);
   if (rc) return rc;
   const int is_float = dtype == GX_FLOAT32 || dtype == GX_FLOAT64;
-  const unsigned g   = gx::rank::grid_for(n);
+  const unsigned g   = gx::rank::rows_grid(n);
   switch (sz) {
     case 1: hipLaunchKernelGGL((gx::rank::k_differ<uint8_t>), dim3(g), dim3(256), 0, s, static_cast<const uint8_t*>(keys), v, order, n, 0, flags); break;
     case 2: hipLaunchKernelGGL((gx::rank::k_differ<uint16_t>), dim3(g), dim3(256), 0, s, static_cast<const uint16_t*>(keys), v, order, n, 0, flags); break;

@@ -186,17 +186,9 @@ __device__ __forceinline__ bool store_row(const Args& a, int64_t i, typename Acc
   return ok;
 }
 
-// validity word(s) of the 64 consecutive rows a wave has just written; `first` = the row of lane 0 (a multiple of 64).  The null count
-// is NOT kept here: one atomic per wave on one address cost 27 ms per 2^28 rows where many rows are null (xp_rolling, a bitmap at
-// L = 2); it is counted from the finished bitmap instead (gx_bitmask_count: n / 8 bytes read).
-__device__ __forceinline__ void store_validity(const Args& a, int64_t first, bool ok)
-{
-  const uint64_t bal   = ballot(ok);
-  const int64_t nwords = (a.n + 31) >> 5, w = first >> 5;
-  const unsigned l     = lane_id();
-  if (l == 0 && w < nwords) a.out_valid[w] = (uint32_t)bal;
-  if (l == 32 && w + 1 < nwords) a.out_valid[w + 1] = (uint32_t)(bal >> 32);
-}
+// The validity of the 64 consecutive rows a wave has just written goes out through store_wave_validity (gx_validity.hpp).  The null
+// count is NOT kept there: one atomic per wave on one address cost 27 ms per 2^28 rows where many rows are null (xp_rolling, a bitmap
+// at L = 2); it is counted from the finished bitmap instead (gx_bitmask_count: n / 8 bytes read).
 __global__ void k_nulls_from_valid(int64_t* count, int64_t n) { *count = n - *count; }
 
 // ---------------------------------------------------------------------------------------------- the row loop
@@ -232,7 +224,7 @@ __global__ void __launch_bounds__(BT) k_roll_rows(Args a)
     }
     ok = store_row<MODE>(a, i, acc, cnt, size);
   }
-  store_validity(a, i & ~(int64_t)63, ok);
+  store_wave_validity(a.out_valid, i & ~(int64_t)63, a.n, ok);
 }
 
 // ---------------------------------------------------------------------------------------------- the tile kernel
@@ -408,7 +400,7 @@ __global__ void __launch_bounds__(BT) k_roll_tile(Args a, int left, int right)
       }
       ok = store_row<MODE>(a, i, val, cnt, size);
     }
-    store_validity(a, i & ~(int64_t)63, ok);
+    store_wave_validity(a.out_valid, i & ~(int64_t)63, a.n, ok);
   }
 }
 

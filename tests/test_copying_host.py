@@ -1,6 +1,6 @@
 """CPU: cudf::concatenate / scatter / copy_if_else / slice / split as far as they can be checked without a device -- exported
 symbols, the argument checks of gx_concatenate / gx_scatter / gx_copy_if_else, the --host cases of the C++ surface, the argument
-checks of the Python surface, and a NumPy model of how one tile of k_concat (cudf_amd/csrc/gx_copying.hip: concat_word, bits_from)
+checks of the Python surface, and a NumPy model of how one tile of k_concat (cudf_amd/csrc/gx_copying.hip: concat_word; gx_validity.hpp: bits_from)
 composes an output validity word from up to 32 inputs with arbitrary begin bits, checked exhaustively against np.concatenate of the
 unpacked bits."""
 import ctypes
@@ -221,8 +221,8 @@ def test_python_surface_rejects_bad_arguments_without_a_device():
 
 # ------------------------------------------------------------------------------------------------ the model of one validity word
 # inputs: (words, begin_bit, rows) with words = None for an input without nulls.  The model mirrors the device code line by line:
-# concat_find (the LAST input that starts at or before the row), the walk over start[k + 1], bits_from (two words only when the run
-# crosses a word), the shift into place.
+# concat_find (the LAST input that starts at or before the row), the walk over start[k + 1], bits_from of gx_validity.hpp (two words only
+# when the run crosses a word), the shift into place.
 
 def _find(start, lo, hi, r):
     while hi - lo > 1:

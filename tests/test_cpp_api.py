@@ -47,6 +47,17 @@ def test_host_side_validation():
     assert "0 failed" in r.stdout
 
 
+def test_validity_word_arithmetic():
+    """tests/cpp/gx_validity_tests: bits_from, bits_from64, the low masks and word_range_mask of cudf_amd/csrc/gx_validity.hpp --
+    the code the value kernels read validity words with -- against bit-by-bit loops, on arrays that end at the last word a call
+    may read.  The program links no library, so it is a make target of its own and not part of the library build."""
+    subprocess.check_call(["make", "-s", "-C", os.path.join(ROOT, "cudf_amd", "cpp"), "validity_tests"])
+    r = subprocess.run([os.path.join(ROOT, "tests", "cpp", "gx_validity_tests")], capture_output=True, text=True, timeout=120)
+    print(r.stdout[-3000:])
+    assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-2000:]
+    assert "0 failed" in r.stdout
+
+
 @pytest.mark.gpu
 def test_cpp_api_against_reference_vectors():
     _build()

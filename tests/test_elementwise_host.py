@@ -217,7 +217,7 @@ def test_python_surface_rejects_bad_arguments_without_a_device():
 
 # ------------------------------------------------------------------------------------------------ the model of the validity rules
 # One output word of 32 rows from two bitmaps read at independent begin bits, as the kernel composes it: every thread takes the
-# R bits of its rows from each operand (ew_bits_from: two words only when the run crosses a word), out_bits applies the operator's
+# R bits of its rows from each operand (bits_from of gx_validity.hpp: two words only when the run crosses a word), out_bits applies the operator's
 # rule, the lanes that share the word OR their pieces together.
 
 def bits_from(words, sb, cnt, reads=None):

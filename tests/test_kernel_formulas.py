@@ -4,7 +4,8 @@ were derived from, so a future edit of a constant or a shift can be checked with
 
   * scan_tags8 (cudf_amd/csrc/gx_join.hip): the 4-bit slot tags of the partitioned hash-join probe --
     carry-free zero-nibble detection, "tag matches before the first empty slot";
-  * k_bitmask_copy (cudf_amd/csrc/gx_gather.hip): funnel shift + edge-word masks of the offset bitmap copy;
+  * k_bitmask_copy (cudf_amd/csrc/gx_gather.hip): funnel shift + edge-word masks of the offset bitmap copy (the kernel takes the funnel
+    from bits_from of gx_validity.hpp, which reads the second word only when the run crosses into it: never more than this model reads);
   * normalise_float / gx_pack_keys (cudf_amd/csrc/gx_rank.hip): float equality classes and key packing;
   * mm_encode order (cudf_amd/csrc/gx_groupby.hip) == oracle.sortable_bits order for floats.
 """
