@@ -17,6 +17,7 @@
 //   * algorithm 1 (A/B knob, no inter-workgroup communication): per pass a tile-histogram
 //     kernel + device scan + the same scatter kernel reading precomputed offsets.
 #include "gx_common.hpp"
+#include <cstddef>
 #include <cstdlib>
 #include <type_traits>
 #include <vector>
@@ -30,6 +31,18 @@ constexpr int MAX_PASSES = 8;
 constexpr int BT         = 512;  // threads per workgroup (8 waves)
 constexpr int NW         = BT / GX_WAVE;
 constexpr int NRANGE     = 8;    // input ranges == XCDs: each gets its own look-back chain (hybrid level 0)
+
+// How the key stream of a partition level is loaded: level 1 and the rescue pass read the level-0 slots, a use-once stream, with
+// NON-TEMPORAL loads, 16 bytes wide where a whole tile starts on a 16-byte boundary (3.64 -> 3.31 ms per 1e9 keys); level 0 reads the
+// caller's column with plain 8-byte loads (non-temporal loads cost it 0.5 ms, 16-byte loads gained nothing).  The other variants of
+// the three streaming kernels, measured per kernel in builds of their own and not kept: profiles/sort_load_policy_ab.txt.
+typedef unsigned long long u64x2 __attribute__((ext_vector_type(2)));  // a 16-byte access of two 64-bit keys
+template <bool NT, typename T>
+__device__ __forceinline__ T stream_load(const T* p)
+{
+  if constexpr (NT) return __builtin_nontemporal_load(p);
+  else return *p;
+}
 
 // Hybrid MSD sort (64-bit keys, n >= 2^22): two MSD partition passes bring every cell (= keys sharing
 // all bits above shift2) down to at most one LDS-resident cell, then ONE kernel sorts each cell on all
@@ -317,6 +330,9 @@ struct SortPlan {
   FastPlan hf;
   SplitPlan sp;
 };
+// tests/test_gpu_sort_level0_one_launch.py reads the LUT form the plan picked straight out of the caller's scratch, at this byte
+// (gx_sort_split_info reports splitter mode, not the form): keep the constant there in step with this one
+static_assert(offsetof(SortPlan, sp) + offsetof(SplitPlan, lut_log) == 166812, "SplitPlan::lut_log moved: update SP_LUT_FORM_BYTE in the test");
 
 // level-0 digit of a sortable key: ((k >> shift0) & dm) | ((k >> fsh) & fhi), where (dm, fsh, fhi) = (0xFF, 0, 0), or
 // (0x7F, width - 8, 0x80) under the sign fold (HybridPlan::fold)
@@ -2092,10 +2108,14 @@ __global__ void __launch_bounds__((1 << CL2) / 16, 4) k_local_sort(const IoT* in
 //   k_hf_scatter<1>     level 1: the (bucket, range) regions -> padded cell slots, cursor = the cell's size
 //   k_plan2, k_local_sort as on the look-back path.
 // The sample reads 512 B of every stride * 512 B: at 1e9 rows 250 MB in 147.6 us (1.7 TB/s).  The access pattern is not why: a bare
-// kernel that reads the same chunks and nothing else takes 41 us (scripts/xp/xp_strided_read.hip, 6.1 TB/s).  Nor is it the 64-bit
+// kernel that reads the same chunks and nothing else takes 48 us COLD (2 GiB of another buffer read between two launches, as in the
+// sort, where 48 GB move between two samples), 46 us with the chunks 16.5 KiB apart instead of a power-of-two 16 KiB and 45 us with
+// them back to back -- differences inside the 5 - 6 us spread of each (scripts/xp/xp_strided_read.hip,
+// profiles/xp_strided_read_cold.txt; the 41 us / 6.1 TB/s quoted here before was the WARM figure: the same 250 MB read again out of
+// the 256 MiB Infinity Cache).  Chunks spread over their windows (64 * (c mod 32) rows in) left the planning span where it was (same file, last table).  Nor is it the 64-bit
 // division per key (the range of a row), the returning LDS atomic per key or the 4.2 M flush atomics of the round-robin chunk
 // order: without them (lds_count, contiguous runs per workgroup, 16 chunks in flight per wave instead of 8) the kernel takes
-// 137.2 us on the same box (profiles/sort_launch_chain_vs_parent.txt).  Where the remaining ~95 us go is open.
+// 137.2 us on the same box (profiles/sort_launch_chain_vs_parent.txt).  Where the remaining ~90 us go is open.
 // ------------------------------------------------------------------------------------------------------------------
 constexpr int HF_CHUNK = GX_WAVE;  // keys per sample chunk: one 512-byte wave load
 
@@ -3317,15 +3337,29 @@ __device__ __forceinline__ void hf_scatter_tile(const KeyT* __restrict__ in, Key
     return;
   }
 
+  constexpr bool NTB = LVL >= 1;                       // non-temporal loads: level 1 and the rescue pass (see stream_load)
+  constexpr bool W16 = LVL >= 1 && sizeof(KeyT) == 8;  // ... and 16 bytes wide where the tile allows
   KeyT key[KPT];
-  if (nvalid == TILE) {
+  // 16-byte loads: which lane holds which key does not matter before the ranking (no level is stable here, the cell sort ranks by
+  // value).  Only a whole tile on a 16-byte boundary (block-uniform): a column pointer of the C ABI, a region start of level 1 need not be
+  if (W16 && nvalid == TILE && (reinterpret_cast<uintptr_t>(in + base) & 15u) == 0u) {
+    if constexpr (W16) {
+      const u64x2* in2 = reinterpret_cast<const u64x2*>(in + base);
 #pragma unroll
-    for (int j = 0; j < KPT; ++j) key[j] = in[base + j * BT + (int)tid];
+      for (int j = 0; j < KPT / 2; ++j) {
+        const u64x2 q  = stream_load<NTB>(&in2[j * BT + (int)tid]);
+        key[2 * j]     = (KeyT)q.x;
+        key[2 * j + 1] = (KeyT)q.y;
+      }
+    }
+  } else if (nvalid == TILE) {
+#pragma unroll
+    for (int j = 0; j < KPT; ++j) key[j] = stream_load<NTB>(&in[base + j * BT + (int)tid]);
   } else {
 #pragma unroll
     for (int j = 0; j < KPT; ++j) {
       const int idx = j * BT + (int)tid;
-      key[j]        = in[base + (idx < nvalid ? idx : 0)];  // padding repeats the tile's first key: neutral for the masks below
+      key[j]        = stream_load<NTB>(&in[base + (idx < nvalid ? idx : 0)]);  // padding repeats the tile's first key: neutral for the masks below
     }
   }
   for (int b = tid; b < NB; b += BT) s_cnt[b] = 0;
@@ -3507,12 +3541,17 @@ constexpr int SP_KPT  = 14;
 // (13 keys per thread -- 39.3 KiB of LDS, four workgroups per CU instead of three -- measured in run 15: 5.44 against 5.36 ms, no gain)
 constexpr int SP_TILE = BT * SP_KPT;
 constexpr size_t sp_level0_lds() { return (size_t)SP_TILE * 8 + (size_t)(3 * BINS + 16 + 4) * 4 + (size_t)2 * NW * 8 + (size_t)BINS * 8 + (size_t)SP_NLUT * 2 + (size_t)SP_TILE; }
-// F2: the LUT form this instantiation searches with (1: form 2, SpLutF; 0: forms 0 / 1).  Both are launched, the one the plan did not
-// pick returns at once (~0.05 ms): with the form tested per key the unrolled ranking loop of EVERY split-mode column slowed by 0.15 ms
-// (run 14), and with two copies of the loop inside one kernel the compiler stopped interleaving the fourteen searches (70 instead
-// of 84 registers, level 0 4.9 -> 5.4 ms, run 15).
+// F2: the LUT form this instantiation searches with (1: form 2, SpLutF; 0: forms 0 / 1).  With the form tested per key the unrolled
+// ranking loop of EVERY split-mode column slowed by 0.15 ms (run 14), and with two copies of the loop INLINED into one kernel the
+// compiler stopped interleaving the fourteen searches (70 instead of 84 registers, level 0 4.9 -> 5.4 ms, run 15).  k_level0 holds
+// both forms and the bit-digit form behind block-uniform branches: with this compiler 96 registers, no scratch, and splitter-mode
+// level 0 is no slower than as a kernel of its own -- 4.51 -> 4.47 ms, float64 5.15 -> 5.06 (profiles/sort_one_launch_vs_parent.txt,
+// section 5; pinning the wave budget with amdgpu_waves_per_eu(4, 4) changed neither figure and is not done).  Check the register
+// count and the splitter-mode time again when either LUT form or the compiler changes.
+// One tile of it: tile `vblock` of `ntiles` (k_level0 hands both in: its grid is sized for whichever form has more tiles).
 template <int KIND, int F2>
-__global__ void __launch_bounds__(BT, 4) k_sp_level0(const uint64_t* __restrict__ in, uint64_t* __restrict__ out, uint64_t desc_mask, SortPlan* plan, int64_t n)
+__device__ __forceinline__ void sp_level0_tile(const uint64_t* __restrict__ in, uint64_t* __restrict__ out, uint64_t desc_mask, SortPlan* plan, int64_t n,
+                                               int64_t vblock, int64_t ntiles)
 {
   constexpr int KPT = SP_KPT, TILE = SP_TILE;
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -3529,11 +3568,9 @@ __global__ void __launch_bounds__(BT, 4) k_sp_level0(const uint64_t* __restrict_
   HybridPlan& hy      = plan->hy;
   FastPlan& hf        = plan->hf;
   const SplitPlan& sp = plan->sp;
-  if (hf.state != 1 || !sp.on || !hf.slots_ready) return;
-  if ((sp.lut_log == 2u) != (F2 == 1)) return;
   const unsigned tid = threadIdx.x;
-  const int64_t v    = xcd_swizzle((int64_t)blockIdx.x, (int64_t)gridDim.x);
-  const int64_t per  = (int64_t)gridDim.x / NRANGE;  // whole tiles per range (the last range takes the rest)
+  const int64_t v    = xcd_swizzle(vblock, ntiles);
+  const int64_t per  = ntiles / NRANGE;  // whole tiles per range (the last range takes the rest)
   const uint32_t seg = (per > 0 && v / per < NRANGE - 1) ? (uint32_t)(v / per) : (uint32_t)(NRANGE - 1);
   const int64_t base = v * TILE;
   const int nvalid   = (int)(n - base < (int64_t)TILE ? n - base : (int64_t)TILE);
@@ -3667,6 +3704,37 @@ __global__ void __launch_bounds__(BT, 4) k_sp_level0(const uint64_t* __restrict_
   }
 }
 
+// ---- level 0 of the cursor path behind ONE launch.  Its three forms -- the bit digit (hf_scatter_tile<.., 0, 8>) and the two LUT
+// forms of splitter mode (sp_level0_tile<.., 0 / 1>) -- are alternatives: the plan on the device picks one.  As three kernels, each
+// with a workgroup per tile, the two that returned at once cost 60 us each at 1e9 rows (139 509 workgroups dispatched for nothing):
+// 0.12 ms of the level-0 span between HIP events.  Splitter mode keeps 0.05 of it (4.49 -> 4.45 ms, float64 5.17 -> 5.11); the
+// bit-digit form inside this kernel runs 0.15 - 0.2 ms longer than as a kernel of its own -- same grid, same LDS, with or without
+// a pinned wave budget -- so the headline column's level 0 is where it was (profiles/sort_one_launch_vs_parent.txt, section 4).
+// Here the branch is taken once per workgroup, on the same plan words the three kernels tested (block-uniform: scalar branches).
+// Each form as a __noinline__ function instead (its own schedule by construction) saves and restores its callee-saved registers
+// around a call that never returns to anything: 140 - 172 B of scratch per lane, level 0 3.70 -> 4.50 ms, splitter mode 4.49 -> 6.95.
+// The forms cut the column into different tiles (8192 against SP_TILE = 7168 keys): the grid is the larger tile count, and each
+// form is told ITS tile count (nt_bit, nt_sp: swizzle, range seams, last tile) -- the workgroups past it return.
+// Dynamic LDS: the larger request, sp_level0_lds() = 57344 + 3152 + 128 + 2048 + 8192 + 7168 = 78032 B, when splitter mode may run
+// (the bit-digit form alone asks for 68816 B); 2 x 78032 = 156064 B <= 160 KiB = 163840 B: two workgroups per CU either way.
+template <typename KeyT, int KIND>
+__global__ void __launch_bounds__(BT, 4)
+k_level0(const KeyT* __restrict__ in, KeyT* __restrict__ out, KeyT desc_mask, SortPlan* plan, uint32_t* __restrict__ cellcur, int64_t n, int64_t nt_bit, int64_t nt_sp)
+{
+  const FastPlan& hf = plan->hf;
+  if (hf.state != 1) return;
+  const int64_t b = (int64_t)blockIdx.x;
+  if (!plan->sp.on) {
+    if (b < nt_bit) hf_scatter_tile<KeyT, KIND, 0, 8>(in, out, desc_mask, plan, cellcur, n, (KeyT*)nullptr, b, nt_bit);
+    return;
+  }
+  if constexpr (sizeof(KeyT) == 8) {
+    if (!hf.slots_ready || b >= nt_sp) return;
+    if (plan->sp.lut_log == 2u) sp_level0_tile<KIND, 1>(in, out, desc_mask, plan, n, b, nt_sp);
+    else sp_level0_tile<KIND, 0>(in, out, desc_mask, plan, n, b, nt_sp);
+  }
+}
+
 static thread_local int g_algorithm = 0;
 static thread_local int g_order_mode = 0;
 
@@ -3736,8 +3804,9 @@ static inline unsigned local_place_grid(int cells) { return (unsigned)((g_place_
 // ticket when a tile is done.
 // float64 keys: a column with a NaN or a -0.0 is declined by the cursor path on the device and the look-back chain is the
 // ONLY path that sorts it, so for float keys the chain stays in the primary role, launched as without the cursor path.
-// k_sp_level0's two forms are ALTERNATIVES of level 0, not fallbacks, and keep one tile per workgroup: eight tiles per
+// The two splitter forms of level 0 are ALTERNATIVES of it, not fallbacks, and keep one tile per workgroup: eight tiles per
 // workgroup compile to 128 registers + 64 - 116 B of scratch where one tile takes 96, in the hot kernel of every uneven column.
+// They share ONE launch with the bit-digit form (k_level0): a workgroup branches to the form the plan picked.
 // Measured at 1e9 int64 keys, builds alternating (profiles/sort_launch_chain_vs_parent.txt): headline 11.18 -> 10.96 ms; the
 // forced fallback 17.65 -> 18.33 ms, 0.59 ms of it in the two MULTI partition passes (4.26 -> 4.35, 4.56 -> 5.00 ms).
 enum class Role { primary, fallback };
@@ -3908,7 +3977,6 @@ int sort_impl(const void* keys_in, void* keys_out, const int32_t* vals_in, int32
       const int64_t frange  = (ftiles / NRANGE) * FT;  // rows per input range (whole tiles; the last range takes the rest)
       auto lds_hf = [&](int nb) { return (size_t)FT * sizeof(KeyT) + (size_t)(3 * nb + 16 + 4) * 4 + (size_t)2 * NW * 8; };
       typedef void (*HfK)(const KeyT*, KeyT*, KeyT, SortPlan*, uint32_t*, uint32_t, int64_t, KeyT*, uint32_t);
-      HfK kf0 = k_hf_scatter<KeyT, CK, 0, 8>;
       // (the level-1 kernel and the cell grids are sized for bits2_max: the device may take the extra bit)
       HfK kf1 = fc.bits2_max <= 8 ? (HfK)k_hf_scatter<KeyT, CK, 1, 8> : (fc.bits2_max == 9 ? (HfK)k_hf_scatter<KeyT, CK, 1, 9> : (HfK)k_hf_scatter<KeyT, CK, 1, 10>);
       HfK kf2 = fc.bits2_max <= 8 ? (HfK)k_hf_scatter<KeyT, CK, 2, 8> : (fc.bits2_max == 9 ? (HfK)k_hf_scatter<KeyT, CK, 2, 9> : (HfK)k_hf_scatter<KeyT, CK, 2, 10>);
@@ -3950,13 +4018,11 @@ int sort_impl(const void* keys_in, void* keys_out, const int32_t* vals_in, int32
       }
       prof_mark(1, stream);
       prof_mark_h(0, stream);
-      GX_HIP_TRY(launch_lds(dev, kf0, dim3((unsigned)ftiles), dim3(BT), lds_hf(256), stream, kin, slot0_buf, desc_mask, plan, hist2, 1u << 13, n, (KeyT*)nullptr, 0u));
-      if constexpr (sizeof(KeyT) == 8) {
-        if (allow_split)
-        {
-          GX_HIP_TRY(launch_lds(dev, (k_sp_level0<CK, 0>), dim3((unsigned)ftiles_s), dim3(BT), sp_level0_lds(), stream, kin, slot0_buf, (uint64_t)desc_mask, plan, n));
-          GX_HIP_TRY(launch_lds(dev, (k_sp_level0<CK, 1>), dim3((unsigned)ftiles_s), dim3(BT), sp_level0_lds(), stream, kin, slot0_buf, (uint64_t)desc_mask, plan, n));
-        }
+      {
+        // level 0, whichever form the plan picked: one workgroup per tile of the form with more tiles (SP_TILE < FT), its LDS request
+        const int64_t tiles0 = ftiles_s > ftiles ? ftiles_s : ftiles;
+        const size_t lds0    = ftiles_s > 0 && sp_level0_lds() > lds_hf(256) ? sp_level0_lds() : lds_hf(256);
+        GX_HIP_TRY(launch_lds(dev, (k_level0<KeyT, CK>), dim3((unsigned)tiles0), dim3(BT), lds0, stream, kin, slot0_buf, desc_mask, plan, hist2, n, ftiles, ftiles_s));
       }
       hipLaunchKernelGGL(k_hf_plan, dim3(1), dim3(BINS), 0, stream, plan, 2, (int)(8 * sizeof(KeyT)), n, fc.bits2, 1 << 13, fc.stride, frange, FT,
                          (unsigned long long)fc.slot_rows, g_cursor_margin, MIN_SHIFT2, fc.bits2_max, (unsigned long long)nb_buf);
