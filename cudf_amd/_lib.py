@@ -207,6 +207,15 @@ _PROTOS = {
     "gx_unary_op_supported": (_i, [_i, _i, _i]),
     "gx_elementwise_tile_rows": (_i, []),
     "gx_elementwise_grid_cap": (_i, []),
+    # null and value replacement (gx_replace.hip): streaming passes; only the policy fill has scratch (its carry table)
+    "gx_replace_tile_rows": (_i, []),
+    "gx_find_and_replace_chunk": (_i, []),
+    "gx_replace_nulls": (_i, [_i, _p, _p, _i64, _p, _p, _i64, _p, _i, _i64, _p, _p, _p, _p]),
+    "gx_replace_nulls_policy": (_i, [_i, _p, _p, _i64, _i64, _i, _p, _p, _p, _p, _sz, _p]),
+    "gx_replace_nans": (_i, [_i, _p, _p, _i64, _p, _p, _i64, _p, _i, _i64, _p, _p, _p, _p]),
+    "gx_clamp": (_i, [_i, _p, _i64, _p, _p, _p, _p, _p, _p, _p, _p]),
+    "gx_find_and_replace": (_i, [_i, _p, _p, _i64, _i64, _p, _p, _p, _i64, _i64, _p, _p, _p, _p]),
+    "gx_normalize_nans_and_zeros": (_i, [_i, _p, _i64, _p, _p]),
 }
 
 for _name, (_res, _args) in _PROTOS.items():

@@ -227,3 +227,45 @@ class Column:
     def notnull(self) -> "Column":
         from . import ops
         return ops.is_valid(self)
+
+    # -------- null and value replacement (ops.replace_nulls / clamp / find_and_replace_all).  Scalars are cast to the column's dtype:
+    # there is no promotion, a value the dtype cannot hold is a TypeError.
+    def fillna(self, value=None, method: Optional[str] = None) -> "Column":
+        """pandas' Series.fillna: nulls take `value` (a scalar, or a Column of equal rows and dtype), or with method "ffill" / "bfill"
+        the nearest valid value before / after them (rows without one stay null)"""
+        from . import ops
+        if (value is None) == (method is None):
+            raise ValueError("Must specify a fill 'value' or 'method'" if value is None else "Cannot specify both 'value' and 'method'")
+        if method is not None:
+            if method not in ("ffill", "bfill"):
+                raise ValueError(f"invalid fill method {method!r}: expected 'ffill' or 'bfill'")
+            return ops.replace_nulls(self, "preceding" if method == "ffill" else "following")
+        if isinstance(value, str):
+            raise TypeError(f"{value!r} is not representable as {self.dtype}")
+        return ops.replace_nulls(self, value)
+
+    def ffill(self) -> "Column":
+        return self.fillna(method="ffill")
+
+    def bfill(self) -> "Column":
+        return self.fillna(method="bfill")
+
+    def clip(self, lower=None, upper=None) -> "Column":
+        """pandas' Series.clip: values below `lower` become lower, values above `upper` become upper; None does not bound"""
+        from . import ops
+        return ops.clamp(self, lower, upper)
+
+    def replace(self, to_replace, value) -> "Column":
+        """pandas' Series.replace for a scalar pair or two lists of equal length: a row equal to to_replace[j] becomes value[j] (the
+        first j that matches; None in `value` makes the row null).  Null rows stay null; NaN matches nothing."""
+        from . import ops
+        olds = list(to_replace) if np.ndim(to_replace) else [to_replace]
+        news = list(value) if np.ndim(value) else [value] * len(olds)      # one value for a whole list, as in pandas
+        if len(olds) != len(news):
+            raise ValueError(f"Replacement lists must match in length. Expecting {len(olds)} got {len(news)}")
+        for v in olds + [w for w in news if w is not None]:
+            ops._check_scalar(v, self.dtype)
+        valid = np.array([w is not None for w in news], dtype=bool)
+        new_np = np.array([0 if w is None else w for w in news]).astype(self.dtype) if news else np.zeros(0, self.dtype)
+        old_np = np.array(olds).astype(self.dtype) if olds else np.zeros(0, self.dtype)
+        return ops.find_and_replace_all(self, Column.from_numpy(old_np), Column.from_numpy(new_np, None if valid.all() else valid))

@@ -270,6 +270,39 @@ class DataFrame:
         cond is null)"""
         return self._select(cond, other, False)
 
+    def _each(self, f) -> "DataFrame":
+        out = DataFrame()
+        for name, c in self._cols.items():
+            out._cols[name] = f(name, c)
+        return out
+
+    def fillna(self, value=None, method: Optional[str] = None) -> "DataFrame":
+        """pandas' DataFrame.fillna: the nulls of every column take `value` -- a scalar cast to each column's dtype (no upcast:
+        TypeError where it does not fit) or a dict per column name (columns it does not name are kept) -- or, with method "ffill" /
+        "bfill", the nearest valid value before / after them; rows without one stay null."""
+        if isinstance(value, dict):
+            if method is not None:
+                raise ValueError("Cannot specify both 'value' and 'method'")
+            for k in value:
+                if k not in self._cols:
+                    raise KeyError(k)
+            return self._each(lambda name, c: c.fillna(value[name]) if name in value else c)
+        return self._each(lambda name, c: c.fillna(value, method))
+
+    def ffill(self) -> "DataFrame":
+        return self.fillna(method="ffill")
+
+    def bfill(self) -> "DataFrame":
+        return self.fillna(method="bfill")
+
+    def clip(self, lower=None, upper=None) -> "DataFrame":
+        """pandas' DataFrame.clip with scalar bounds, each cast to every column's dtype; None does not bound"""
+        return self._each(lambda name, c: c.clip(lower, upper))
+
+    def replace(self, to_replace, value) -> "DataFrame":
+        """pandas' DataFrame.replace for a scalar pair or two lists of equal length, in every column"""
+        return self._each(lambda name, c: c.replace(to_replace, value))
+
     def rolling(self, window: int, min_periods: Optional[int] = None, center: bool = False) -> "Rolling":
         """pandas' DataFrame.rolling(window, min_periods, center) over the rows: .sum() / .min() / .max() / .mean() of every column"""
         return Rolling(self, window, min_periods, center)

@@ -1739,6 +1739,155 @@ def is_not_nan(col: Column) -> Column:
 
 
 # ------------------------------------------------------------------------------------------------
+# null and value replacement  (cudf::replace_nulls / replace_nans / clamp / find_and_replace_all: replace.hpp; gx_replace.hip)
+# ------------------------------------------------------------------------------------------------
+
+def _check_scalar(value, dt: np.dtype):
+    """host check of a scalar against the column's dtype: no promotion; a value the dtype cannot hold is a TypeError"""
+    host = np.zeros(1, dtype=dt)
+    try:
+        host[0] = value
+    except OverflowError:
+        raise TypeError(f"{value!r} is not representable as {dt}") from None
+    if dt.kind in "iub" and host[0] != value:
+        raise TypeError(f"{value!r} is not representable as {dt}")
+
+
+def _typed_scalar(value, dt: np.dtype):
+    """(value, validity byte) in device memory of a valid scalar cast to the column's dtype"""
+    _check_scalar(value, dt)
+    return _device_scalar(value, dt)
+
+
+def _counted(out: Column, nulls) -> Column:
+    """the null count of a launch that wrote out.mask; a mask that nulls nothing is dropped"""
+    if nulls is not None:
+        out.null_count = int(nulls.item())
+        if out.null_count == 0:
+            out.mask = None
+    return out
+
+
+def _replace_from(fn, what: str, first, col: Column, replacement, nulls_in_both: bool) -> Column:
+    """shared by replace_nulls and replace_nans: the replacement is a Column of equal rows and dtype, or a valid scalar"""
+    n = col.size
+    if isinstance(replacement, Column):
+        if replacement.dtype != col.dtype:
+            raise TypeError("Data type mismatch")
+        if replacement.size != n:
+            raise ValueError("Column size mismatch")
+        r_null = replacement.has_nulls()
+        keep = None
+        rargs = [replacement.data_ptr, replacement.mask_ptr if r_null else None, 0, None, 0]
+    else:
+        r_null = False
+        keep = _typed_scalar(replacement, col.dtype)
+        rargs = [ptr(keep[0]), None, 0, None, 1]
+    may_be_null = (col.has_nulls() and r_null) if nulls_in_both else (col.has_nulls() or r_null)
+    out = Column.empty(col.dtype, n, nullable=may_be_null and n > 0)
+    if n == 0:
+        return out
+    nulls = _dev_i64() if may_be_null else None
+    L.check(fn(first, col.data_ptr, col.mask_ptr if col.has_nulls() else None, 0, *rargs, n, out.data_ptr, out.mask_ptr, ptr(nulls),
+               stream_ptr()), what)
+    return _counted(out, nulls)
+
+
+def replace_nulls(col: Column, replacement) -> Column:
+    """cudf::replace_nulls.  replacement: a Column of equal rows and dtype (a row stays null where both are), a Python / NumPy scalar
+    (cast to the column's dtype), None (the invalid scalar: nothing is replaced), or "preceding" / "following": a null takes the
+    nearest valid value before / after it, rows without one stay null.  A column without nulls comes back as a copy."""
+    gx_dtype(col.dtype)
+    if isinstance(replacement, str):
+        if replacement not in ("preceding", "following"):
+            raise ValueError(f"unknown replace policy {replacement!r}")
+        if not col.has_nulls():
+            return _copy_column(col)
+        n = col.size
+        out = Column.empty(col.dtype, n, nullable=True)
+        nulls = _dev_i64()
+        args = (col.dtype.itemsize, col.data_ptr, col.mask_ptr, 0, n, int(replacement == "following"), out.data_ptr, out.mask_ptr, ptr(nulls))
+        nb = ctypes.c_size_t(0)
+        L.check(_lib.gx_replace_nulls_policy(*args, None, ctypes.byref(nb), None), "gx_replace_nulls_policy")
+        tmp = device_bytes(nb.value)
+        L.check(_lib.gx_replace_nulls_policy(*args, ptr(tmp), ctypes.byref(nb), stream_ptr()), "gx_replace_nulls_policy")
+        return _counted(out, nulls)
+    if isinstance(replacement, Column) and replacement.dtype != col.dtype:
+        raise TypeError("Data type mismatch")
+    if isinstance(replacement, Column) and replacement.size != col.size:
+        raise ValueError("Column size mismatch")
+    if not isinstance(replacement, Column) and replacement is not None:
+        _check_scalar(replacement, col.dtype)    # the value is checked even where nothing is replaced
+    if replacement is None or not col.has_nulls():
+        return _copy_column(col)
+    return _replace_from(_lib.gx_replace_nulls, "gx_replace_nulls", col.dtype.itemsize, col, replacement, True)
+
+
+def replace_nans(col: Column, replacement) -> Column:
+    """cudf::replace_nans: a valid NaN row of a float column takes the replacement's value and validity (a Column of equal rows and
+    dtype, a scalar, or None: nothing is replaced); every other row, a null row with NaN bits included, is kept."""
+    if col.dtype.kind != "f":
+        raise TypeError("replace_nans takes a floating-point column")
+    if replacement is None:
+        return _copy_column(col)
+    return _replace_from(_lib.gx_replace_nans, "gx_replace_nans", col.gx, col, replacement, False)
+
+
+def clamp(col: Column, lo, hi, lo_replace=None, hi_replace=None) -> Column:
+    """cudf::clamp: out[i] = x < lo ? lo_replace : (x > hi ? hi_replace : x) in the column's own dtype; lo / hi None does not bound;
+    lo_replace / hi_replace None is the bound itself.  NaN passes through; the result shares the input's validity."""
+    gx_dtype(col.dtype)
+    if lo is None and hi is None:
+        return _copy_column(col)
+    dt = col.dtype
+    for v in (lo, hi, lo_replace, hi_replace):
+        if v is not None:
+            _check_scalar(v, dt)             # every value before the first allocation
+    lo_v = _typed_scalar(lo, dt)[0] if lo is not None else None
+    hi_v = _typed_scalar(hi, dt)[0] if hi is not None else None
+    lo_r = _typed_scalar(lo_replace, dt)[0] if lo is not None and lo_replace is not None else None
+    hi_r = _typed_scalar(hi_replace, dt)[0] if hi is not None and hi_replace is not None else None
+    out = Column.empty(dt, col.size)
+    L.check(_lib.gx_clamp(col.gx, col.data_ptr, col.size, ptr(lo_v), None, ptr(lo_r), ptr(hi_v), None, ptr(hi_r), out.data_ptr, stream_ptr()),
+            "gx_clamp")
+    return _share_validity(out, col)
+
+
+def find_and_replace_all(col: Column, values_to_replace: Column, replacement_values: Column) -> Column:
+    """cudf::find_and_replace_all: out[i] = replacement_values[j] for the first j with col[i] == values_to_replace[j], else col[i]
+    (NaN matches nothing, -0.0 matches +0.0).  A null row stays null; a replaced row takes its replacement's validity.  The cost is
+    rows x list length comparisons: meant for short lists."""
+    gx_dtype(col.dtype)
+    if values_to_replace.dtype != col.dtype or replacement_values.dtype != col.dtype:
+        raise TypeError("Columns type mismatch")
+    if values_to_replace.size != replacement_values.size:
+        raise ValueError("values_to_replace and replacement_values size mismatch")
+    if values_to_replace.has_nulls():
+        raise ValueError("values_to_replace must not have nulls")
+    n, m = col.size, values_to_replace.size
+    if m == 0:
+        return _copy_column(col)
+    may_be_null = col.has_nulls() or replacement_values.has_nulls()
+    out = Column.empty(col.dtype, n, nullable=may_be_null and n > 0)
+    if n == 0:
+        return out
+    nulls = _dev_i64() if may_be_null else None
+    L.check(_lib.gx_find_and_replace(col.gx, col.data_ptr, col.mask_ptr if col.has_nulls() else None, 0, n, values_to_replace.data_ptr,
+                                     replacement_values.data_ptr, replacement_values.mask_ptr if replacement_values.has_nulls() else None,
+                                     0, m, out.data_ptr, out.mask_ptr, ptr(nulls), stream_ptr()), "gx_find_and_replace")
+    return _counted(out, nulls)
+
+
+def normalize_nans_and_zeros(col: Column) -> Column:
+    """cudf::normalize_nans_and_zeros: every NaN becomes the positive quiet NaN, -0.0 becomes +0.0; shares the input's validity"""
+    if col.dtype.kind != "f":
+        raise TypeError("normalize_nans_and_zeros takes a floating-point column")
+    out = Column.empty(col.dtype, col.size)
+    L.check(_lib.gx_normalize_nans_and_zeros(col.gx, col.data_ptr, col.size, out.data_ptr, stream_ptr()), "gx_normalize_nans_and_zeros")
+    return _share_validity(out, col)
+
+
+# ------------------------------------------------------------------------------------------------
 # synthetic data / checks (bench + tests)
 # ------------------------------------------------------------------------------------------------
 

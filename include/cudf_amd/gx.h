@@ -473,6 +473,65 @@ int gx_elementwise_tile_rows(void);                                             
 int gx_elementwise_grid_cap(void);                                               /* most workgroups of one launch */
 
 /* ------------------------------------------------------------------------------------------
+ * Null and value replacement (cudf_amd/csrc/gx_replace.hip).  Replace the kernels of the reference's cpp/src/replace (nulls.cu,
+ * nans.cu, clamp.cu, replace.cu).  All eleven gx_dtype (the functions that compare nothing take the element width in bytes, 1 / 2 /
+ * 4 / 8); row counts lie in [0, 2^31).  Bitmaps are Arrow bitmaps read from their own begin bit on (a sliced view needs no
+ * re-based copy); every one of the (n + 31) / 32 words of out_valid is written, bits behind the last row 0; *out_null_count_dev
+ * (optional, device int64) = nulls written (0 without out_valid).  Values move as bits wherever no comparison is needed: NaN
+ * payloads and -0.0 survive.  Every argument check comes before the first device call; n == 0 launches nothing and reads no
+ * pointer.  A workgroup owns gx_replace_tile_rows() consecutive rows per trip (a multiple of 64: whole validity words, no atomics
+ * on words) and a thread moves 16 bytes per access on the value streams (the policy fill: one row).  Except where noted `out` must
+ * not overlap an input.  GX_EINVAL: n outside [0, 2^31), a negative begin bit, a NULL pointer that is needed with n > 0;
+ * GX_EDTYPE: an element width or dtype the function does not take; GX_ETMP: scratch too small.
+ * gx_replace_nulls: out[i] = bit(in, i) ? in[i] : repl[i], repl[0] with repl_is_scalar: one element in device memory with its
+ *   validity byte (NULL = valid), as in gx_copy_if_else.  in_valid NULL = no nulls (a copy).  Output bit = input bit OR
+ *   replacement bit; out_valid may be NULL when the caller knows the result has no nulls.  One streaming pass, no scratch; the
+ *   replacement is read only where a thread's rows hold a null.
+ * gx_replace_nulls_policy: replace_policy PRECEDING (backward == 0) / FOLLOWING: a null row takes the value of the nearest valid
+ *   row before / after it and becomes valid; rows without one stay null, their data is unspecified.  in_valid and out_valid are
+ *   required.  No workgroup waits for another (no look-back, no tickets), because the source row of every null is a function of
+ *   the bitmap: (1) a pass over the bitmap alone writes, per tile of gx_replace_tile_rows() rows, the tile's last (first) valid
+ *   row or -1; (2) an exclusive running max over that table, two small launches of fixed depth, gives every tile the nearest
+ *   valid row strictly before (after) it; (3) one streaming pass per tile reads the tile's 64 validity words into a per-word
+ *   LDS table and resolves each null's source from its own word (clz / ctz), the table, or the carried row, then does one load
+ *   in[source] and one store per row, and writes the validity words.  HBM traffic: the column once in and once out plus the
+ *   bitmap twice.  Scratch (cub-style query: tmp == NULL -> *tmp_bytes) holds the carry table only: 4 bytes per tile.
+ * gx_replace_nans (GX_FLOAT32 / GX_FLOAT64): a valid NaN row takes the replacement's value and validity (column or scalar, as
+ *   above); every other row keeps its own value and validity -- a null row stays null whatever its data bits.  out_valid may be
+ *   NULL only when neither side can be null (no in_valid, no repl_valid / scalar validity byte): otherwise GX_EINVAL.
+ * gx_clamp: out[i] = x < lo ? lo_replace : (x > hi ? hi_replace : x) compared in the column's own dtype (64-bit integers as
+ *   integers; BOOL8 as x != 0, a row inside the bounds keeps its byte); a float NaN compares false both ways and passes.  lo, hi,
+ *   lo_replace, hi_replace are device scalars of the dtype; *lo_valid_dev / *hi_valid_dev (NULL = valid) == 0, or a NULL bound,
+ *   does not bound; a NULL replacement is the bound itself.  Reads and writes no bitmap: the caller copies or shares the
+ *   input's, as for gx_unary_op.
+ * gx_find_and_replace: out[i] = new_vals[j] for the smallest j in [0, m) with in[i] == old_vals[j], else in[i]; == is the
+ *   dtype's (integers and BOOL8: equal bits; floats: NaN matches nothing, -0.0 matches +0.0).  A null input row stays null and
+ *   is not compared; a replaced row takes bit new_begin_bit + j of new_valid (NULL = valid).  old_vals is staged through LDS
+ *   gx_find_and_replace_chunk() values at a time, the earliest match across chunks wins, so any m in [0, 2^31) works; the cost is
+ *   O(n * m) comparisons, like the reference's thrust::find per row: meant for short lists.  m == 0 copies.  out_valid may be
+ *   NULL only without in_valid and new_valid.
+ * gx_normalize_nans_and_zeros (floats): every NaN becomes the positive quiet NaN 0x7FC00000 / 0x7FF8000000000000, -0.0 becomes
+ *   +0.0, everything else is copied bit for bit.  out may equal in.
+ * ------------------------------------------------------------------------------------------ */
+int gx_replace_tile_rows(void);
+int gx_find_and_replace_chunk(void);
+int gx_replace_nulls(int elem_size, const void* in, const uint32_t* in_valid, int64_t in_begin_bit, const void* repl,
+                     const uint32_t* repl_valid, int64_t repl_begin_bit, const uint8_t* repl_scalar_valid_dev, int repl_is_scalar,
+                     int64_t n, void* out, uint32_t* out_valid, int64_t* out_null_count_dev, gx_stream_t stream);
+int gx_replace_nulls_policy(int elem_size, const void* in, const uint32_t* in_valid, int64_t in_begin_bit, int64_t n, int backward,
+                            void* out, uint32_t* out_valid, int64_t* out_null_count_dev, void* tmp, size_t* tmp_bytes,
+                            gx_stream_t stream);
+int gx_replace_nans(int dtype, const void* in, const uint32_t* in_valid, int64_t in_begin_bit, const void* repl,
+                    const uint32_t* repl_valid, int64_t repl_begin_bit, const uint8_t* repl_scalar_valid_dev, int repl_is_scalar,
+                    int64_t n, void* out, uint32_t* out_valid, int64_t* out_null_count_dev, gx_stream_t stream);
+int gx_clamp(int dtype, const void* in, int64_t n, const void* lo, const uint8_t* lo_valid_dev, const void* lo_replace,
+             const void* hi, const uint8_t* hi_valid_dev, const void* hi_replace, void* out, gx_stream_t stream);
+int gx_find_and_replace(int dtype, const void* in, const uint32_t* in_valid, int64_t in_begin_bit, int64_t n, const void* old_vals,
+                        const void* new_vals, const uint32_t* new_valid, int64_t new_begin_bit, int64_t m, void* out,
+                        uint32_t* out_valid, int64_t* out_null_count_dev, gx_stream_t stream);
+int gx_normalize_nans_and_zeros(int dtype, const void* in, int64_t n, void* out, gx_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * Hashing / partitioning.
  * gx_murmur3_32: cudf::hashing::detail::MurmurHash3_x86_32<T>
  * (include/cudf/hashing/detail/murmurhash3_x86_32.cuh:22-67), null -> UINT32_MAX, and the
