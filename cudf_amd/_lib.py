@@ -216,6 +216,15 @@ _PROTOS = {
     "gx_clamp": (_i, [_i, _p, _i64, _p, _p, _p, _p, _p, _p, _p, _p]),
     "gx_find_and_replace": (_i, [_i, _p, _p, _i64, _i64, _p, _p, _p, _i64, _i64, _p, _p, _p, _p]),
     "gx_normalize_nans_and_zeros": (_i, [_i, _p, _i64, _p, _p]),
+    # making and reshaping columns (gx_reshape.hip): interleave (descriptors in scratch), tile, repeat, fill, sequence
+    "gx_reshape_tile_rows": (_i, []),
+    "gx_interleave_tile": (_i, [_i, _i, ctypes.POINTER(_i), ctypes.POINTER(_i)]),
+    "gx_interleave": (_i, [_i, _i, ctypes.POINTER(_p), ctypes.POINTER(_p), ctypes.POINTER(_i64), _i64, _p, _p, _p, _p, _sz, _p]),
+    "gx_tile": (_i, [_i, _p, _p, _i64, _i64, _i64, _p, _p, _p, _p]),
+    "gx_repeat_each": (_i, [_i, _p, _p, _i64, _i64, _i64, _p, _p, _p, _p]),
+    "gx_repeat_map": (_i, [_p, _i64, _i64, _p, _p, _sz, _p]),
+    "gx_fill_range": (_i, [_i, _p, _i64, _i64, _p, _p]),
+    "gx_sequence": (_i, [_i, _p, _i64, _p, _p, _p]),
 }
 
 for _name, (_res, _args) in _PROTOS.items():

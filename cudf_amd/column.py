@@ -98,6 +98,26 @@ class Column:
         mask = torch.zeros(bitmask_words(size), dtype=torch.int32, device="cuda") if nullable else None
         return cls(data, dt, size, mask, 0)
 
+    @classmethod
+    def arange(cls, start, stop=None, step=1, dtype=None) -> "Column":
+        """numpy.arange on the device (ops.sequence): start + i * step for i in [0, ceil((stop - start) / step)); one argument is the
+        stop.  dtype defaults to NumPy's for the arguments (int64 / float64).  Floats round the product, then the sum."""
+        from . import ops
+        if stop is None:
+            start, stop = 0, start
+        if step == 0:
+            raise ValueError("arange: step cannot be zero")
+        dt = np.dtype(dtype) if dtype is not None else np.result_type(start, stop, step)
+        if dt.kind not in "iuf":
+            raise TypeError(f"arange: {dt} is not a numeric type")
+        n = max(0, int(np.ceil((stop - start) / step)))
+        return ops.sequence(n, start, step, dt)
+
+    def repeat(self, repeats) -> "Column":
+        """pandas' Series.repeat: every row `repeats` times -- an int, or an integer Column of per-row counts (ops.repeat)"""
+        from . import ops
+        return ops.repeat(self, repeats)
+
     def to_numpy(self) -> np.ndarray:
         nbytes = self.size * self.dtype.itemsize
         return self.data[:nbytes].cpu().numpy().view(self.dtype).copy()

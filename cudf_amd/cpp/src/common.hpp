@@ -3,6 +3,8 @@
 #pragma once
 #include <cudf/column/column.hpp>
 #include <cudf/column/column_view.hpp>
+#include <cudf/table/table.hpp>
+#include <cudf/table/table_view.hpp>
 #include <cudf/types.hpp>
 #include <cudf/utilities/error.hpp>
 #include <cudf_amd/gx.h>
@@ -81,6 +83,11 @@ inline int64_t read_i64(int64_t const* dev, rmm::cuda_stream_view stream)
 // A validity bitmap usable by the kernels for `c`: the kernels index bit i for row i, so a view
 // with a non-zero offset gets its bits re-based into a fresh bitmap (`holder` keeps it alive).
 bitmask_type const* rebased_mask(column_view const& c, rmm::device_buffer& holder, rmm::cuda_stream_view stream);
+
+// cudf::tile (each == false: gx_tile) and cudf::repeat with a scalar count (each == true: gx_repeat_each) differ in the entry point
+// alone: one launch per column, the null counts of all columns in one read (src/reshape.cpp)
+std::unique_ptr<table> tile_or_repeat_each(bool each, table_view const& input, size_type count, rmm::cuda_stream_view stream,
+                                           rmm::device_async_resource_ref mr);
 
 }  // namespace detail
 }  // namespace cudf

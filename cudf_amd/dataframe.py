@@ -303,6 +303,27 @@ class DataFrame:
         """pandas' DataFrame.replace for a scalar pair or two lists of equal length, in every column"""
         return self._each(lambda name, c: c.replace(to_replace, value))
 
+    # ---- reshaping (ops.repeat / interleave_columns / transpose)
+    def repeat(self, repeats) -> "DataFrame":
+        """cudf's DataFrame.repeat: every row `repeats` times -- an int, or an integer Column of per-row counts"""
+        return self._from_columns(ops.repeat(list(self._cols.values()), repeats))
+
+    def interleave_columns(self) -> Column:
+        """cudf's DataFrame.interleave_columns: one Column, row 0 of every column, then row 1, ...; the columns must share a dtype"""
+        return ops.interleave_columns(list(self._cols.values()))
+
+    def transpose(self) -> "DataFrame":
+        """cudf's DataFrame.transpose: row i becomes the column named str(i).  The columns must share a dtype: TypeError otherwise
+        (no upcast to a common type)"""
+        out = DataFrame()
+        for i, c in enumerate(ops.transpose(list(self._cols.values()))):
+            out._cols[str(i)] = c
+        return out
+
+    @property
+    def T(self) -> "DataFrame":
+        return self.transpose()
+
     def rolling(self, window: int, min_periods: Optional[int] = None, center: bool = False) -> "Rolling":
         """pandas' DataFrame.rolling(window, min_periods, center) over the rows: .sum() / .min() / .max() / .mean() of every column"""
         return Rolling(self, window, min_periods, center)

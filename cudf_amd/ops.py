@@ -1888,6 +1888,203 @@ def normalize_nans_and_zeros(col: Column) -> Column:
 
 
 # ------------------------------------------------------------------------------------------------
+# making and reshaping columns  (cudf::fill / repeat / sequence: filling.hpp; interleave_columns / tile: reshape.hpp; transpose:
+# transpose.hpp; gx_reshape.hip).  Every argument check comes before the first device call.
+# ------------------------------------------------------------------------------------------------
+
+_SIZE_MAX = 2**31 - 1
+
+
+def _same_table(cols: Sequence[Column], what: str, same_type: bool) -> List[Column]:
+    cols = list(cols)
+    for c in cols:
+        if not isinstance(c, Column):
+            raise TypeError(f"{what}: expected Columns")
+        gx_dtype(c.dtype)
+    if len({c.size for c in cols}) > 1:
+        raise ValueError("Column size mismatch")
+    if same_type and len({c.dtype for c in cols}) > 1:
+        raise TypeError(f"{what}: the columns differ in dtype")
+    return cols
+
+
+def interleave_columns(cols: Sequence[Column]) -> Column:
+    """cudf::interleave_columns: out[i * k + j] = cols[j][i] for k columns of one dtype and length (gx_interleave: an LDS-staged
+    transpose).  The result has a mask only if it holds a null."""
+    cols = _same_table(cols, "interleave_columns", True)
+    if not cols:
+        raise ValueError("interleave_columns: the table has no columns")
+    k, n, dt = len(cols), cols[0].size, cols[0].dtype
+    if n * k > _SIZE_MAX:
+        raise OverflowError("interleave_columns: the result exceeds the column size limit")
+    with_mask = any(c.has_nulls() for c in cols) and n > 0
+    out = Column.empty(dt, n * k, nullable=with_mask)
+    if n == 0:
+        return out
+    ptrs = (ctypes.c_void_p * k)(*[c.data.data_ptr() for c in cols])
+    valid = (ctypes.c_void_p * k)(*[c.mask.data_ptr() if c.has_nulls() else None for c in cols])
+    nulls = _dev_i64() if with_mask else None
+    _run(_lib.gx_interleave, dt.itemsize, k, ptrs, valid, None, n, out.data_ptr, out.mask_ptr, ptr(nulls))
+    return _counted(out, nulls)
+
+
+def transpose(cols: Sequence[Column]) -> List[Column]:
+    """cudf::transpose: the table on its side -- len(cols[0]) result columns of len(cols) rows each, result[i][j] = cols[j][i].  One
+    interleave moves the data; the result columns are cut out of it.  A table without columns or rows gives []."""
+    cols = _same_table(cols, "transpose", True)
+    if not cols or cols[0].size == 0:
+        return []
+    k, n, dt = len(cols), cols[0].size, cols[0].dtype
+    whole = interleave_columns(cols)
+    nulls = np.zeros(n, dtype=np.int64)
+    if whole.has_nulls():
+        nulls = (~whole.valid_numpy()).reshape(n, k).sum(axis=1)
+    row_bytes = k * dt.itemsize
+    out = []
+    for i in range(n):
+        c = Column(whole.data[i * row_bytes:(i + 1) * row_bytes].clone(), dt, k)
+        if nulls[i]:
+            c.mask = torch.zeros(bitmask_words(k), dtype=torch.int32, device="cuda")
+            c.null_count = int(nulls[i])
+            L.check(_lib.gx_bitmask_copy(c.mask_ptr, 0, whole.mask_ptr, i * k, k, stream_ptr()), "gx_bitmask_copy")
+        out.append(c)
+    return out
+
+
+def _tile_or_repeat(fn, what: str, cols, count: int):
+    single = isinstance(cols, Column)
+    cols = _same_table([cols] if single else cols, what, False)
+    if isinstance(count, bool) or not isinstance(count, (int, np.integer)):
+        raise TypeError(f"{what}: count must be an integer")
+    if count < 0:
+        raise ValueError(f"{what}: count cannot be negative")
+    n = cols[0].size if cols else 0
+    if n * int(count) > _SIZE_MAX:
+        raise OverflowError(f"{what}: the result exceeds the column size limit")
+    total = n * int(count)
+    outs = []
+    for c in cols:
+        with_mask = c.has_nulls() and total > 0
+        out = Column.empty(c.dtype, total, nullable=with_mask)
+        if total:
+            nulls = _dev_i64() if with_mask else None
+            L.check(fn(c.dtype.itemsize, c.data_ptr, c.mask_ptr if with_mask else None, 0, n, int(count), out.data_ptr, out.mask_ptr,
+                       ptr(nulls), stream_ptr()), what)
+            _counted(out, nulls)
+        outs.append(out)
+    return outs[0] if single else outs
+
+
+def tile(cols, count: int):
+    """cudf::tile: the rows of the table laid down `count` times (one streaming launch per column: gx_tile).  cols: a Column or a
+    list of Columns; the result has the same shape."""
+    return _tile_or_repeat(_lib.gx_tile, "tile", cols, count)
+
+
+def repeat(cols, repeats):
+    """cudf::repeat: every row repeated `repeats` times -- an int (gx_repeat_each), or an integer Column of per-row counts without
+    nulls (cast and scanned in int64; one expansion map from gx_repeat_map, then gx_gather per column).  Negative entries of a count
+    Column are undefined behaviour, as in the reference.  cols: a Column or a list of Columns; the result has the same shape."""
+    if not isinstance(repeats, Column):
+        return _tile_or_repeat(_lib.gx_repeat_each, "repeat", cols, repeats)
+    single = isinstance(cols, Column)
+    cols = _same_table([cols] if single else cols, "repeat", False)
+    if repeats.dtype.kind not in "iu":
+        raise ValueError("repeat: count must be an integral Column")
+    if repeats.has_nulls():
+        raise ValueError("repeat: count cannot have nulls")
+    n = cols[0].size if cols else 0
+    if repeats.size != n:
+        raise ValueError("repeat: count and the table differ in length")
+    if n == 0:
+        outs = [Column.empty(c.dtype, 0) for c in cols]
+        return outs[0] if single else outs
+    # counts as int64 with one 0 behind them: the exclusive scan of n + 1 entries ends in the total
+    counts = Column(torch.zeros((n + 1) * 8, dtype=torch.uint8, device="cuda"), np.int64, n + 1)
+    L.check(_lib.gx_cast(repeats.gx, repeats.data_ptr, n, L.INT64, counts.data_ptr, stream_ptr()), "gx_cast")
+    offsets64 = scan(counts, "sum", inclusive=False)
+    total = int(offsets64.data.view(torch.int64)[n].item())      # the one host read: it sizes the result
+    if total > _SIZE_MAX:
+        raise OverflowError("repeat: the result exceeds the column size limit")
+    offsets = cast(offsets64, np.int32)
+    gmap = Column.empty(np.int32, total)
+    if total:
+        _run(_lib.gx_repeat_map, offsets.data_ptr, n, total, gmap.data_ptr)
+    outs = []
+    for c in cols:
+        out = gather(c, gmap) if total else Column.empty(c.dtype, 0)
+        if out.mask is not None and out.null_count == 0:
+            out.mask = None
+        outs.append(out)
+    return outs[0] if single else outs
+
+
+def _sequence_dtype(dtype) -> np.dtype:
+    dt = np.dtype(dtype)
+    gx_dtype(dt)
+    if dt.kind not in "iuf":
+        raise TypeError(f"sequence: {dt} is not a numeric type")
+    return dt
+
+
+def sequence(size: int, init, step=None, dtype=None) -> Column:
+    """cudf::sequence: out[i] = init + i * step in `dtype` (default: NumPy's type of init), step None = 1.  Integers wrap; floats round
+    the product and then the sum, as NumPy's init + arange(size).astype(dtype) * step does."""
+    if init is None:
+        raise ValueError("sequence: init must be a valid scalar")
+    dt = _sequence_dtype(np.asarray(init).dtype if dtype is None else dtype)
+    if isinstance(size, bool) or not isinstance(size, (int, np.integer)):
+        raise TypeError("sequence: size must be an integer")
+    if size < 0:
+        raise ValueError("sequence: size cannot be negative")
+    if size > _SIZE_MAX:
+        raise OverflowError("sequence: size exceeds the column size limit")
+    _check_scalar(init, dt)
+    if step is not None:
+        _check_scalar(step, dt)
+    out = Column.empty(dt, int(size))
+    if size == 0:
+        return out
+    init_dev = _device_scalar(init, dt)[0]
+    step_dev = _device_scalar(step, dt)[0] if step is not None else None
+    L.check(_lib.gx_sequence(out.gx, out.data_ptr, int(size), ptr(init_dev), ptr(step_dev), stream_ptr()), "gx_sequence")
+    return out
+
+
+def fill(col: Column, begin: int, end: int, value) -> Column:
+    """cudf::fill: a copy of col with rows [begin, end) set to `value` (cast to the column's dtype; None: the invalid scalar, the rows
+    become null).  Outside the range values and validity are the input's; begin == end is a copy."""
+    gx_dtype(col.dtype)
+    if begin < 0 or end > col.size or begin > end:
+        raise IndexError("fill: range out of bounds")
+    if value is not None:
+        _check_scalar(value, col.dtype)
+    out = _copy_column(col)
+    if begin == end:
+        return out
+    n = col.size
+    if value is not None:
+        val = _device_scalar(value, col.dtype)[0]
+        L.check(_lib.gx_fill_range(col.dtype.itemsize, out.data_ptr, begin, end, ptr(val), stream_ptr()), "gx_fill_range")
+    old_nulls = 0
+    if col.has_nulls():
+        cnt = _dev_i64()
+        L.check(_lib.gx_bitmask_count(col.mask_ptr, begin, end, ptr(cnt), stream_ptr()), "gx_bitmask_count")
+        old_nulls = (end - begin) - int(cnt.item())
+    else:
+        out.mask = None
+    if value is None and out.mask is None:
+        out.mask = torch.zeros(bitmask_words(n), dtype=torch.int32, device="cuda")
+        L.check(_lib.gx_bitmask_set(out.mask_ptr, 0, n, 1, stream_ptr()), "gx_bitmask_set")
+    if out.mask is not None:
+        L.check(_lib.gx_bitmask_set(out.mask_ptr, begin, end, int(value is not None), stream_ptr()), "gx_bitmask_set")
+        out.null_count = col.null_count - old_nulls + (0 if value is not None else end - begin)
+        if out.null_count == 0:
+            out.mask = None
+    return out
+
+
+# ------------------------------------------------------------------------------------------------
 # synthetic data / checks (bench + tests)
 # ------------------------------------------------------------------------------------------------
 

@@ -532,6 +532,63 @@ int gx_find_and_replace(int dtype, const void* in, const uint32_t* in_valid, int
 int gx_normalize_nans_and_zeros(int dtype, const void* in, int64_t n, void* out, gx_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Making and reshaping columns (cudf_amd/csrc/gx_reshape.hip).  Replace the kernels of the reference's cpp/src/reshape
+ * (interleave_columns.cu, tile.cu), cpp/src/transpose/transpose.cu and cpp/src/filling (fill.cu, repeat.cu, sequence.cu).  The
+ * conventions of the row-movement section hold: elem_size is the element width in bytes, 1 / 2 / 4 / 8, and values move as bits;
+ * bitmaps are Arrow bitmaps read from a begin bit on; row counts (of inputs AND of the result) lie in [0, 2^31); every argument
+ * check comes before the first device call; with no rows nothing is launched; host pointer arrays are not read after the call
+ * returns and the stream is not waited for.  With out_valid every one of its (result rows + 31) / 32 words is written exactly once,
+ * by one owner and without atomics on words, bits behind the last row 0, nothing behind the last word touched;
+ * *out_null_count_dev (optional, device int64) = nulls written.
+ * gx_interleave: out[i * ncols + j] = col_j[i]: cudf::interleave_columns, and the whole data movement of cudf::transpose.
+ *   cols_host / valid_ptrs_host / begin_bits_host are HOST arrays of ncols entries (valid_ptrs_host NULL or a NULL entry = no
+ *   nulls; begin_bits_host NULL = all 0).  A workgroup owns the tile gx_interleave_tile() reports: rows x cols.  Up to 32 columns
+ *   the tile holds all of them for a band of rows: each column's stretch is read with 16-byte loads where the addresses allow
+ *   (a tile with a column off a 16-byte boundary, and a ragged last band, element by element), laid out in LDS in output order,
+ *   and the band leaves as one contiguous run of 16-byte stores.
+ *   Above 32 columns the tile is two-dimensional (64 rows x 32 columns): column-wise coalesced reads, row-wise runs of 32
+ *   elements on the way out.  The LDS image is padded by one word per 32 and per 1024 words, so the column-strided writes into
+ *   it do not fall on one bank.  ncols == 1 is a plain copy.  The validity is composed in a pass of its own, one thread per output
+ *   word.  Scratch (cub-style query: tmp == NULL -> *tmp_bytes) holds the column descriptors; they reach it as kernel arguments.
+ *   GX_EINVAL: ncols < 1, nrows or nrows * ncols outside [0, 2^31), NULL tmp_bytes / cols_host / out or a NULL column with
+ *   rows, a negative begin bit; GX_ETMP: scratch too small.
+ * gx_interleave_tile (host only): the tile of gx_interleave for this width and column count; GX_EDTYPE / GX_EINVAL as above.
+ * gx_tile: out[r * nrows + i] = in[i] for r in [0, count): the column laid down count times, in one streaming launch whatever
+ *   count is; the validity words of the result wrap around the input bitmap (several times inside a word when nrows < 32).
+ * gx_repeat_each: out[i * count + k] = in[i] for k in [0, count).  Streaming, no scratch, validity composed per output word.
+ *   Both: a workgroup owns gx_reshape_tile_rows() result rows per trip (whole validity words).  GX_EINVAL: nrows, count or
+ *   nrows * count outside [0, 2^31), a negative begin bit, NULL in / out with result rows.
+ * gx_repeat_map: out_map[e] = the source row of result row e of a per-row repeat, from offsets_dev: the exclusive prefix sum of
+ *   the counts as int32, nrows + 1 entries, the last equal to total (the caller has read it to size the result).  A workgroup owns
+ *   gx_reshape_tile_rows() result rows: it finds its first source row by binary search, marks in LDS where each source row
+ *   with a count begins inside the tile (rows of count 0 share a position with the row behind them, which is the one marked:
+ *   the largest row number wins), turns the marks into row numbers with a max-scan and writes them with 16-byte stores.  No
+ *   workgroup waits for another; a source row that spans many tiles costs each one binary search.  The values and bitmaps then
+ *   go through gx_gather with this map.  No scratch is needed (the query answers 0).  GX_EINVAL: nrows or total outside [0, 2^31),
+ *   total > 0 with nrows == 0, NULL tmp_bytes / offsets_dev / out_map with total > 0.
+ * gx_fill_range: data[i] = *value_dev (a device scalar of elem_size bytes) for i in [begin, end): elements up to the first
+ *   16-byte boundary, 16-byte stores, elements behind the last.  The validity side of cudf::fill is gx_bitmask_set / _copy.
+ *   GX_EINVAL: begin < 0, end < begin, end >= 2^31, NULL data / value_dev with begin < end.
+ * gx_sequence: out[i] = init + i * step in the column's own type, every numeric gx_dtype (GX_BOOL8: GX_EDTYPE); init_dev /
+ *   step_dev are device scalars of the dtype, step_dev NULL = 1.  Integers wrap modulo 2^w.  Floats round twice, the product
+ *   T(i) * step and then the sum, as NumPy evaluates init + arange(n).astype(T) * step: no fused multiply-add.
+ *   GX_EINVAL: n outside [0, 2^31), NULL out / init_dev with n > 0.
+ * ------------------------------------------------------------------------------------------ */
+int gx_reshape_tile_rows(void);
+int gx_interleave_tile(int elem_size, int ncols, int* rows, int* cols);
+int gx_interleave(int elem_size, int ncols, const void* const* cols_host, const uint32_t* const* valid_ptrs_host,
+                  const int64_t* begin_bits_host, int64_t nrows, void* out, uint32_t* out_valid, int64_t* out_null_count_dev,
+                  void* tmp, size_t* tmp_bytes, gx_stream_t stream);
+int gx_tile(int elem_size, const void* in, const uint32_t* in_valid, int64_t in_begin_bit, int64_t nrows, int64_t count, void* out,
+            uint32_t* out_valid, int64_t* out_null_count_dev, gx_stream_t stream);
+int gx_repeat_each(int elem_size, const void* in, const uint32_t* in_valid, int64_t in_begin_bit, int64_t nrows, int64_t count,
+                   void* out, uint32_t* out_valid, int64_t* out_null_count_dev, gx_stream_t stream);
+int gx_repeat_map(const int32_t* offsets_dev, int64_t nrows, int64_t total, int32_t* out_map, void* tmp, size_t* tmp_bytes,
+                  gx_stream_t stream);
+int gx_fill_range(int elem_size, void* data, int64_t begin, int64_t end, const void* value_dev, gx_stream_t stream);
+int gx_sequence(int dtype, void* out, int64_t n, const void* init_dev, const void* step_dev, gx_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * Hashing / partitioning.
  * gx_murmur3_32: cudf::hashing::detail::MurmurHash3_x86_32<T>
  * (include/cudf/hashing/detail/murmurhash3_x86_32.cuh:22-67), null -> UINT32_MAX, and the
