@@ -314,6 +314,64 @@ struct ProdOp {
   __device__ __forceinline__ T operator()(T a, T b) const { return a * b; }
 };
 
+// ---- float MIN / MAX in the row comparator's order (to_sortable<K_FLOAT> below: every NaN is one value above +inf,
+// -0.0 == +0.0), as associative operators: the scan trees of gx_scan.hpp put a given row on the left of one combine and on
+// the right of the next, so MinOp / MaxOp (plain <, which keeps a NaN on the left and drops one on the right) gave results
+// that changed with the row's position.  On NaN-free input both operators pick exactly what MinOp / MaxOp pick (ties and
+// the sign of a zero included).
+//
+// MAX is the maximum of {numbers < NaN}: NaN as soon as one operand is NaN.  -inf stays the identity.
+struct FloatMaxOp {
+  __device__ __forceinline__ double operator()(double a, double b) const { return (a < b || b != b) ? b : a; }
+};
+// MIN is the minimum of {numbers < NaN < EMPTY}: a number beats a NaN, and a NaN beats "nothing yet".  +inf cannot be the
+// identity of that order (min(+inf, NaN) must be NaN when the +inf stands for a null row and +inf when it is a value), so the
+// accumulator is a double in which two NaN bit patterns have a meaning: 0x7FF8000000000000, which loads map every NaN to, is
+// NaN, and 0x7FFFFFFFFFFFFFFF is EMPTY.  EMPTY converts back to +inf: what an exclusive scan shows in row 0 and what a run
+// without a valid value holds behind its null.  As SIGNED integers the high words order the three classes: a number's is at
+// most 0x7FF00000 (+inf), NaN's is 0x7FF80000, EMPTY's 0x7FFFFFFF -- the operator below tells them apart with 32-bit compares.
+// The constructor's rewrite of NaNs is what makes this sound: a -NaN has a negative high word and an input NaN may carry
+// EMPTY's very bits (tests/test_gpu_float_extremes_nan.py feeds both).  MIN costs more than MAX (profiles/
+// float_extremes_nan_vs_parent.txt).  Follow-up: loaders that hand the kernels a row's validity beside its value, so that
+// "nothing yet" needs no bit pattern and no NaN is rewritten.
+struct FloatMin {
+  double v;
+  static constexpr unsigned long long NAN_BITS = 0x7FF8000000000000ull, EMPTY_BITS = 0x7FFFFFFFFFFFFFFFull;
+  FloatMin() = default;
+  __host__ __device__ explicit FloatMin(double x) : v(x)
+  {
+    const unsigned long long nan = NAN_BITS;
+    if (x != x) __builtin_memcpy(&v, &nan, 8);
+  }
+  static __host__ __device__ FloatMin empty()
+  {
+    FloatMin e;
+    const unsigned long long bits = EMPTY_BITS;
+    __builtin_memcpy(&e.v, &bits, 8);
+    return e;
+  }
+  __host__ __device__ int32_t high() const
+  {
+    unsigned long long b;
+    __builtin_memcpy(&b, &v, 8);
+    return (int32_t)(uint32_t)(b >> 32);
+  }
+  __host__ __device__ bool is_empty() const { return high() == (int32_t)(EMPTY_BITS >> 32); }
+  __host__ __device__ explicit operator double() const { return is_empty() ? __builtin_huge_val() : v; }
+  __host__ __device__ explicit operator float() const { return is_empty() ? __builtin_huge_valf() : (float)v; }
+};
+struct FloatMinOp {
+  __device__ __forceinline__ FloatMin operator()(FloatMin a, FloatMin b) const
+  {
+    // b replaces a when it is the smaller number (a NaN or EMPTY on either side compares false), or when a is NaN / EMPTY and b
+    // is of a lower class.  One select, no early return, one 64-bit compare: of the forms timed on the look-back scan this is
+    // the fastest (profiles/float_extremes_nan_vs_parent.txt).
+    const int32_t ha = a.high(), hb = b.high();
+    const bool take_b = (b.v < a.v) | ((ha >= (int32_t)(FloatMin::NAN_BITS >> 32)) & (hb < ha));
+    return take_b ? b : a;
+  }
+};
+
 // DPP lane movement (gfx9 family): every 32-bit word of v moved by the DPP pattern CTRL under row mask RM; lanes the
 // pattern leaves without a source keep their own value.
 template <int CTRL, int RM, typename T>

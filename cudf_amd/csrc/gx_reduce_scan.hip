@@ -11,6 +11,11 @@
 // error bound n * 2^-104 * sum|x| is then under one ulp of the result); a sum or prefix that meets
 // +-inf or NaN, or that leaves the double range, is the +-inf / NaN of the reference's plain addition.
 // Integer SUM/PRODUCT wrap mod 2^64 exactly like the reference's integer arithmetic.
+//
+// float MIN / MAX (reduce, scan, groupby::scan, sort-path groupby) use FloatMinOp / FloatMaxOp (gx_common.hpp): the row
+// comparator's order, in which every NaN is one value above +inf -- the order the hash groupby and rolling_window use.  MIN is
+// the smallest non-NaN valid value and NaN only when every valid value is NaN; MAX is NaN once a valid value is NaN; nulls never
+// take part; a running MIN is NaN until the first non-NaN valid value (tests/test_gpu_float_extremes_nan.py).
 #include <limits>
 #include <type_traits>
 
@@ -187,6 +192,11 @@ __global__ void k_store_result<DD>(const DD* res, int out_dtype, void* out)
 {
   store_as<double>(static_cast<double>(*res), out_dtype, out);
 }
+template <>
+__global__ void k_store_result<FloatMin>(const FloatMin* res, int out_dtype, void* out)
+{
+  store_as<double>(static_cast<double>(*res), out_dtype, out);
+}
 
 template <typename InT, typename AccT, typename Op>
 int reduce_typed(const void* in, const uint32_t* valid, int64_t n, AccT identity, Op op, int out_dtype, void* out,
@@ -278,8 +288,8 @@ int reduce_float(const void* in, const uint32_t* valid, int64_t n, int op, int o
   switch (op) {
     case GX_OP_SUM: return reduce_dd<InT>(in, valid, n, out_dtype, out, tmp, tmp_bytes, s);
     case GX_OP_PRODUCT: return reduce_typed<InT, double>(in, valid, n, 1.0, ProdOp(), out_dtype, out, tmp, tmp_bytes, s);
-    case GX_OP_MIN: return reduce_typed<InT, double>(in, valid, n, Limits<double>::highest(), MinOp(), out_dtype, out, tmp, tmp_bytes, s);
-    case GX_OP_MAX: return reduce_typed<InT, double>(in, valid, n, Limits<double>::lowest(), MaxOp(), out_dtype, out, tmp, tmp_bytes, s);
+    case GX_OP_MIN: return reduce_typed<InT, FloatMin>(in, valid, n, FloatMin::empty(), FloatMinOp(), out_dtype, out, tmp, tmp_bytes, s);
+    case GX_OP_MAX: return reduce_typed<InT, double>(in, valid, n, Limits<double>::lowest(), FloatMaxOp(), out_dtype, out, tmp, tmp_bytes, s);
     case GX_OP_COUNT_NONZERO: return reduce_nonzero<InT>(in, valid, n, out_dtype, out, tmp, tmp_bytes, s);
     default: return GX_EINVAL;
   }
@@ -349,8 +359,8 @@ int scan_float(const void* in, const uint32_t* valid, int64_t n, int op, int inc
   switch (op) {
     case GX_OP_SUM: return scan_dd<InT>(in, valid, n, inclusive, out, tmp, tmp_bytes, s);
     case GX_OP_PRODUCT: return scan_typed<InT, double>(in, valid, n, 1.0, ProdOp(), inclusive, out, tmp, tmp_bytes, s);
-    case GX_OP_MIN: return scan_lookback<InT, double>(in, valid, n, Limits<double>::highest(), MinOp(), inclusive, out, tmp, tmp_bytes, s);
-    case GX_OP_MAX: return scan_lookback<InT, double>(in, valid, n, Limits<double>::lowest(), MaxOp(), inclusive, out, tmp, tmp_bytes, s);
+    case GX_OP_MIN: return scan_lookback<InT, FloatMin>(in, valid, n, FloatMin::empty(), FloatMinOp(), inclusive, out, tmp, tmp_bytes, s);
+    case GX_OP_MAX: return scan_lookback<InT, double>(in, valid, n, Limits<double>::lowest(), FloatMaxOp(), inclusive, out, tmp, tmp_bytes, s);
     default: return GX_EINVAL;
   }
 }
@@ -402,8 +412,8 @@ int seg_float(const void* vals, const uint32_t* valid, const uint8_t* heads, int
 {
   switch (op) {
     case GX_OP_SUM: return seg_typed<InT, double, InT>(vals, valid, heads, n, 0.0, SumOp(), out, static_cast<Seg<double>*>(partials), s);
-    case GX_OP_MIN: return seg_typed<InT, double, InT>(vals, valid, heads, n, Limits<double>::highest(), MinOp(), out, static_cast<Seg<double>*>(partials), s);
-    case GX_OP_MAX: return seg_typed<InT, double, InT>(vals, valid, heads, n, Limits<double>::lowest(), MaxOp(), out, static_cast<Seg<double>*>(partials), s);
+    case GX_OP_MIN: return seg_typed<InT, FloatMin, InT>(vals, valid, heads, n, FloatMin::empty(), FloatMinOp(), out, static_cast<Seg<FloatMin>*>(partials), s);
+    case GX_OP_MAX: return seg_typed<InT, double, InT>(vals, valid, heads, n, Limits<double>::lowest(), FloatMaxOp(), out, static_cast<Seg<double>*>(partials), s);
     default: return GX_EINVAL;
   }
 }
@@ -533,8 +543,8 @@ int segreduce_float(const void* vals, const uint32_t* valid, const uint8_t* head
     case GX_OP_COUNT_VALID:
     case GX_OP_SUM: return segreduce_typed<InT, DD, InT>(vals, valid, heads, labels, n, DD{0.0, 0.0}, DDSum(), out, out_cnt, partials, s);
     case GX_OP_PRODUCT: return segreduce_typed<InT, double, InT>(vals, valid, heads, labels, n, 1.0, ProdOp(), out, out_cnt, partials, s);
-    case GX_OP_MIN: return segreduce_typed<InT, double, InT>(vals, valid, heads, labels, n, Limits<double>::highest(), MinOp(), out, out_cnt, partials, s);
-    case GX_OP_MAX: return segreduce_typed<InT, double, InT>(vals, valid, heads, labels, n, Limits<double>::lowest(), MaxOp(), out, out_cnt, partials, s);
+    case GX_OP_MIN: return segreduce_typed<InT, FloatMin, InT>(vals, valid, heads, labels, n, FloatMin::empty(), FloatMinOp(), out, out_cnt, partials, s);
+    case GX_OP_MAX: return segreduce_typed<InT, double, InT>(vals, valid, heads, labels, n, Limits<double>::lowest(), FloatMaxOp(), out, out_cnt, partials, s);
     default: return GX_EINVAL;
   }
 }

@@ -910,6 +910,11 @@ int gx_segmented_scan(int key_dtype, const void* sorted_keys, int val_dtype, con
  * src/reductions/scan/scan_inclusive.cu:76-89 and scan_exclusive.cu; output dtype == input
  * dtype (ints wrap); nulls contribute the identity (null_policy handling of the mask is done by
  * the caller: scan_inclusive.cu:198-216).
+ * Float MIN / MAX -- here, in gx_segmented_scan and in gx_segmented_reduce -- use the order of the sorts and of the hash
+ * groupby: every NaN is one value above +inf (and equal to every other NaN), -0.0 == +0.0 (which zero comes back is
+ * unspecified), nulls never take part.  MIN is the smallest non-NaN valid value and NaN only when every valid value is NaN;
+ * MAX is NaN once a valid value is NaN; a running MIN is NaN until the first non-NaN valid value.  The result does not depend
+ * on where the rows sit.  Row 0 of an exclusive scan (and every row with no valid value before it) holds +inf / -inf.
  * ------------------------------------------------------------------------------------------ */
 int gx_reduce(int in_dtype, const void* in, const uint32_t* valid, int64_t n, int op,
               int out_dtype, void* out_dev, int64_t* valid_count_dev, void* tmp, size_t* tmp_bytes,

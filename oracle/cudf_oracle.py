@@ -907,9 +907,34 @@ def groupby_sort_agg(keys, values, agg: str, keys_valid=None, values_valid=None,
     raise ValueError(agg)
 
 
+def _running_any(flag: np.ndarray, starts=None, labels=None) -> np.ndarray:
+    """inclusive running OR of a boolean vector, restarted at every group start (starts[labels[i]] = first row of row i's group)"""
+    c = np.cumsum(flag.astype(np.int64))
+    if starts is not None and len(c):
+        c = c - np.concatenate([[0], c])[starts][labels]
+    return c > 0
+
+
+def float_running_extreme(run: np.ndarray, values: np.ndarray, valid: np.ndarray, op: str, starts=None, labels=None) -> np.ndarray:
+    """The float rule of the inclusive running MIN / MAX, in the row comparator's order (sortable_bits: every NaN is one value
+    above +inf; nulls never take part).  `run` is the running extreme of the non-NaN valid values alone (NaN and null rows
+    replaced by the identity +-inf).  cummin: NaN until the first non-NaN valid value, then `run`: [NaN, 2, NaN, 1] ->
+    [NaN, 2, 2, 1]; before the first valid value it is the identity +inf.  cummax: NaN from the first valid NaN onward."""
+    nan = valid & np.isnan(values)
+    seen_nan = _running_any(nan, starts, labels)
+    out = run.copy()
+    if op == "min":
+        seen_num = _running_any(valid & ~nan, starts, labels)
+        out[seen_nan & ~seen_num] = np.nan
+    else:
+        out[seen_nan] = np.nan
+    return out
+
+
 def groupby_scan(keys, values, op: str, keys_valid=None, values_valid=None, include_null_keys=False, keys_sorted=False):
     """groupby::scan (cpp/src/groupby/sort/scan.cpp:60-238): rows in sorted-key order, per-group INCLUSIVE scan.
     sum / min / max (group_scan_util.cuh:77-133): null values are skipped and stay null, integer SUM in int64;
+    float MIN / MAX follow float_running_extreme;
     count_valid / count_all (group_count_scan.cu:24-62): INT32, never null, count of valid / all rows so far.
     Returns (sorted_keys, out, out_valid)."""
     keys, values = np.asarray(keys), np.asarray(values)
@@ -941,9 +966,12 @@ def groupby_scan(keys, values, op: str, keys_valid=None, values_valid=None, incl
             ident = np.inf if op == "min" else -np.inf
         else:
             ident = np.iinfo(values.dtype).max if op == "min" else np.iinfo(values.dtype).min
-        x = pd.Series(np.where(svv, sv, ident))
+        take = svv & ~np.isnan(sv) if isf else svv  # pandas sees no NaN: the NaN rule is float_running_extreme's, not pandas'
+        x = pd.Series(np.where(take, sv, ident))
         gb = x.groupby(labels)
         out = (gb.cummin() if op == "min" else gb.cummax()).to_numpy().astype(values.dtype)
+        if isf:
+            out = float_running_extreme(out, sv, svv, op, offsets[:-1], labels)
         return sk, out, svv
     raise ValueError(op)
 
@@ -1196,7 +1224,8 @@ def scan(values: np.ndarray, op: str = "sum", inclusive: bool = True, valid=None
     scan_exclusive.cu): output dtype == input dtype (ints wrap); null_policy EXCLUDE: nulls are
     replaced by the identity and stay null in the output (mask copied); INCLUDE: everything from
     the first null on is null (mask_scan :36-61).  exact=True: a float SUM is the exact prefix rounded once (exact_prefix_sums) instead of
-    the sequential sum in the column type.  Returns (values, valid mask)."""
+    the sequential sum in the column type.  Float MIN / MAX follow float_running_extreme (NaN above +inf, as in reduce and the
+    groupby aggregations); an exclusive scan shows the identity +-inf in row 0.  Returns (values, valid mask)."""
     v = np.asarray(values)
     n = len(v)
     m = np.ones(n, bool) if valid is None else np.asarray(valid, bool)
@@ -1216,11 +1245,16 @@ def scan(values: np.ndarray, op: str = "sum", inclusive: bool = True, valid=None
     else:
         raise ValueError(op)
     x = np.where(m, v, ident).astype(dt)
+    float_extreme = dt.kind == "f" and op in ("min", "max")
+    if float_extreme:  # NaN rows give way to the identity here and come back through float_running_extreme
+        x[np.isnan(x)] = ident
     with np.errstate(over="ignore", invalid="ignore"):
         if exact and op == "sum" and dt.kind == "f":
             inc = exact_prefix_sums(x).astype(dt)
         else:
             inc = f(x, dtype=dt) if op in ("sum", "product") else f(x)
+    if float_extreme:
+        inc = float_running_extreme(inc, v, m, op)
     if inclusive:
         out = inc
     else:

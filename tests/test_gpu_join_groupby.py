@@ -330,6 +330,8 @@ def test_groupby_min_max_partitioned_large(gx, nulls, nsplit):
                 vals[::50] = -0.0
                 vals[1::97] = np.inf
                 vals[3::1013] = -np.inf
+                vals[7::211] = np.nan                      # one value above +inf: MAX of its group, MIN only of an all-NaN group
+                vals[keys == 11] = np.nan                  # a group of NaN alone
             else:
                 info = np.iinfo(vdtype)
                 vals = rng.integers(info.min, info.max, n, dtype=vdtype, endpoint=True)

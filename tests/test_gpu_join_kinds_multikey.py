@@ -415,6 +415,8 @@ def test_groupby_compound_matches_oracle(gx, vdtype, nulls):
     if np.dtype(vdtype).kind == "f":
         vals = (rng.integers(-40, 40, n) / 8).astype(vdtype)
         vals[rng.random(n) < 0.01] = -0.0
+        vals[(keys < 500) & (rng.random(n) < 0.02)] = np.nan  # ties of NaN: ARGMAX is the first NaN row; VAR / STD / M2 are NaN there
+        vals[keys == 777] = np.nan                             # a group of NaN alone: ARGMIN is its first valid row
     else:
         info = np.iinfo(vdtype)
         vals = rng.integers(max(info.min, -100), min(info.max, 100) + 1, n).astype(vdtype)

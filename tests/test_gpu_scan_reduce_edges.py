@@ -69,8 +69,11 @@ def test_lookback_scan_tile_edges(gx, dtype, op):
     rng = np.random.default_rng(31)
     for n in [LB_CHUNK - 1, LB_CHUNK, LB_CHUNK + 1, 2 * LB_CHUNK, 17 * LB_CHUNK + 1, 33 * LB_CHUNK + 5]:
         v = _vals(dtype, n, rng)
-        if dtype == "float64":  # +-inf and +-0.0, no NaN (the reference's NaN result depends on the order of the comparisons)
+        if dtype == "float64":  # +-inf, +-0.0 and NaN: one value above +inf on every path (tests/test_gpu_float_extremes_nan.py)
             v[rng.integers(0, n, 64)] = rng.choice(np.array([np.inf, -np.inf, 0.0, -0.0]), 64)
+            v[rng.integers(0, n, 3)] = np.nan  # anywhere: tile 0 and the rows before a tile edge included
+            if n == 2 * LB_CHUNK:
+                v[0] = np.nan                  # and row 0: the running maximum is NaN throughout
         tile = np.ones(n, bool)
         t0 = LB_CHUNK if n > 2 * LB_CHUNK - 1 else 0  # a whole tile of nulls: its aggregate is the identity
         tile[t0:t0 + LB_CHUNK] = False

@@ -1051,3 +1051,73 @@ def test_gap_splitters_keep_the_table_sorted_and_isolate_the_gap():
     smooth = sorted({1000 + 977 * i * i % 100000 for i in range(68)})
     gs = max(smooth[i + 1] - smooth[i] for i in range(len(smooth) - 1))
     assert gs <= (smooth[-1] - smooth[0]) // 2
+
+
+def test_float_min_max_operators_are_associative_and_give_the_nan_rule():
+    """FloatMinOp / FloatMaxOp of gx_common.hpp restated: MIN over {numbers < NaN < EMPTY} (EMPTY = the identity a null row loads
+    as, shown as +inf), MAX over {numbers < NaN} with -inf as the identity.  Every triple of a value set with both zeros, both
+    infinities, NaN and the identity associates (so the lane tree, the steps, the waves and the chunk partials of gx_scan.hpp may
+    group the rows as they like), the identity is neutral on both sides, and folding any sequence in any grouping gives the oracle's
+    reduce: the smallest non-NaN value, NaN only when all values are NaN; NaN once a value is NaN."""
+    import itertools
+    import math
+    EMPTY = "empty"
+
+    def is_nan(x):
+        return x != EMPTY and x != x
+
+    def high(x):  # the signed high word of the accumulator: EMPTY is 0x7FFFFFFFFFFFFFFF; a NaN is whatever bits it came with
+        bits = 0x7FFFFFFFFFFFFFFF if x == EMPTY else int(np.float64(x).view(np.uint64))
+        return int(np.uint32(bits >> 32).view(np.int32))
+
+    def load(x):  # FloatMin(double): every NaN becomes 0x7FF8000000000000 -- without it the operator below is wrong (end of the test)
+        return float(np.uint64(0x7FF8000000000000).view(np.float64)) if x != x else x
+
+    def fmin(a, b):  # take_b = (b.v < a.v) | ((ha >= 0x7FF80000) & (hb < ha));   (EMPTY is a NaN bit pattern: it compares false)
+        lt = a != EMPTY and b != EMPTY and b < a
+        return b if (lt or (high(a) >= 0x7FF80000 and high(b) < high(a))) else a
+
+    def fmax(a, b):  # (a < b || b != b) ? b : a
+        return b if (a < b or b != b) else a
+
+    def same(x, y):
+        return (x == EMPTY and y == EMPTY) or (x != EMPTY and y != EMPTY and (x == y or (x != x and y != y)))
+
+    nums = [-math.inf, -1.5, -0.0, 0.0, 2.0, math.inf]
+    for op, vals, ident in ((fmin, nums + [math.nan, EMPTY], EMPTY), (fmax, nums + [math.nan], -math.inf)):
+        for a in vals:
+            assert same(op(ident, a), a) and same(op(a, ident), a)
+        for a, b, c in itertools.product(vals, repeat=3):
+            assert same(op(op(a, b), c), op(a, op(b, c))), (op.__name__, a, b, c)
+    # against the oracle, nulls as the identity; NaN-free input: exactly what `b < a ? b : a` / `a < b ? b : a` pick, zero signs included
+    rng = np.random.default_rng(0)
+    odd = np.array([0xFFF8000000000000, 0x7FF0000000000001, 0x7FFFFFFFFFFFFFFF], np.uint64).view(np.float64)  # -NaN, quiet bit clear, EMPTY's bits
+    pool = np.concatenate([np.array(nums + [math.nan]), odd])
+    for _ in range(300):
+        n = int(rng.integers(1, 9))
+        x = rng.choice(pool, n)
+        valid = rng.random(n) > 0.3
+        for name, op, ident in (("min", fmin, EMPTY), ("max", fmax, -math.inf)):
+            seq = [(load(float(v)) if name == "min" else float(v)) if ok else ident for v, ok in zip(x, valid)]
+            left = seq[0]
+            for v in seq[1:]:
+                left = op(left, v)
+            k = n // 2  # one other grouping: two halves
+            halves = [ident, ident]
+            for i, v in enumerate(seq):
+                halves[i >= k] = op(halves[i >= k], v)
+            assert same(op(halves[0], halves[1]), left)
+            want, ok = orc.reduce(x, name, valid)
+            assert (left == EMPTY or (name == "max" and not valid.any())) == (not ok)
+            if ok:
+                assert same(left, float(want)), (name, x, valid, left, want)
+            if not np.isnan(x[valid]).any() and valid.any():
+                plain = None
+                for v in x[valid]:
+                    plain = float(v) if plain is None else ((float(v) if v < plain else plain) if name == "min" else (float(v) if plain < v else plain))
+                assert math.copysign(1, plain) == math.copysign(1, left) and plain == left
+    # what load() is for: the raw bits of a -NaN have a negative high word (as the left operand it would hide the number), and
+    # a NaN of the input may be EMPTY's bits (it would lose to "nothing yet" and come back as +inf)
+    neg_nan, empty_bits = float(odd[0]), float(odd[2])
+    assert fmin(neg_nan, 1.0) != 1.0 and fmin(load(neg_nan), 1.0) == 1.0
+    assert high(empty_bits) == high(EMPTY) and high(load(empty_bits)) == 0x7FF80000

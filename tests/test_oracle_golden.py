@@ -499,3 +499,185 @@ def test_exact_prefix_sums_match_rational_arithmetic():
     for k in range(96, 300_007, 97 * 40):
         assert got[k] == math.fsum(big[: k + 1])
     assert got[-1] == math.fsum(big)
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# float MIN / MAX / ARGMIN / ARGMAX with NaN: one order on every entry point (the row comparator's: every NaN is one value
+# above +inf, NaN == NaN; nulls never take part).  Inputs and expected outputs are typed out by hand.
+#   MIN: the smallest non-NaN valid value, NaN only when every valid value is NaN.   MAX: NaN once a valid value is NaN.
+#   ARGMIN / ARGMAX: the smallest row among those equal to that extreme.
+#   cummin: NaN until the first non-NaN valid value, then the running minimum of the non-NaN values.   cummax: NaN from
+#   the first NaN onward.   Exclusive scans show the identity +-inf in row 0.
+# ----------------------------------------------------------------------------------------------------------------------
+_N = np.nan
+_T, _F = True, False
+
+
+def _odd_nans(dtype):
+    """-NaN and a NaN with a signalling-looking payload (quiet bit clear), made from their bits"""
+    if np.dtype(dtype) == np.float64:
+        return np.array([0xFFF8000000000000, 0x7FF0000000000001], np.uint64).view(np.float64)
+    return np.array([0xFFC00000, 0x7F800001], np.uint32).view(np.float32)
+
+
+# (name, values, valid or None, MIN, MAX, ARGMIN, ARGMAX, result valid, inclusive cummin, inclusive cummax); "-N" / "sN" are
+# replaced by the two NaNs of _odd_nans; values under a null (valid False) are unspecified and written as 0
+NAN_EXTREMES = [
+    ("nan_hides_nothing", [1.0, _N, 0.5], None, 0.5, _N, 2, 1, _T, [1.0, 1.0, 0.5], [1.0, _N, _N]),
+    ("null_then_nan", [7.0, _N], [_F, _T], _N, _N, 1, 1, _T, [0, _N], [0, _N]),
+    ("nan_then_null", [_N, 7.0], [_T, _F], _N, _N, 0, 0, _T, [_N, 0], [_N, 0]),
+    ("null_nan_null", [9.0, _N, 9.0], [_F, _T, _F], _N, _N, 1, 1, _T, [0, _N, 0], [0, _N, 0]),
+    ("one_nan", [_N], None, _N, _N, 0, 0, _T, [_N], [_N]),
+    ("all_nan", [_N, _N, _N], None, _N, _N, 0, 0, _T, [_N, _N, _N], [_N, _N, _N]),
+    ("all_null", [3.0, _N], [_F, _F], 0, 0, 0, 0, _F, [0, 0], [0, 0]),
+    ("leading_nan", [_N, 2.0, _N, 1.0], None, 1.0, _N, 3, 0, _T, [_N, 2.0, 2.0, 1.0], [_N, _N, _N, _N]),
+    ("trailing_nan", [3.0, 1.0, _N], None, 1.0, _N, 1, 2, _T, [3.0, 1.0, 1.0], [3.0, 3.0, _N]),
+    ("interior_nan", [2.0, _N, 5.0, 1.0], None, 1.0, _N, 3, 1, _T, [2.0, 2.0, 2.0, 1.0], [2.0, _N, _N, _N]),
+    ("nan_and_inf", [np.inf, _N, np.inf], None, np.inf, _N, 0, 1, _T, [np.inf, np.inf, np.inf], [np.inf, _N, _N]),
+    ("odd_nans", ["-N", 4.0, "sN", -np.inf, np.inf], None, -np.inf, _N, 3, 0, _T,
+     [_N, 4.0, 4.0, -np.inf, -np.inf], [_N, _N, _N, _N, _N]),
+    ("odd_nans_only", ["sN", "-N"], None, _N, _N, 0, 0, _T, [_N, _N], [_N, _N]),
+    ("null_between", [5.0, 0.0, _N, 6.0], [_T, _F, _T, _T], 5.0, _N, 0, 2, _T, [5.0, 0, 5.0, 5.0], [5.0, 0, _N, _N]),
+]
+
+
+def _nan_case(case, dtype):
+    name, vals, valid, mn, mx, amin, amax, ok, cmin, cmax = case
+    odd = _odd_nans(dtype)
+    v = np.array([_N if isinstance(x, str) else x for x in vals], dtype)
+    u = odd.view(f"u{odd.itemsize}")
+    for i, x in enumerate(vals):  # as bits: a scalar on its way through a Python float may lose its payload
+        if isinstance(x, str):
+            v.view(u.dtype)[i] = u[0 if x == "-N" else 1]
+            assert np.isnan(v[i]) and v.view(u.dtype)[i] == u[0 if x == "-N" else 1]
+    m = None if valid is None else np.array(valid, bool)
+    return v, m, mn, mx, amin, amax, ok, np.array(cmin, dtype), np.array(cmax, dtype)
+
+
+def _same(got, want, where=None):
+    """equal values with NaN == NaN (any payload), and the same dtype"""
+    got, want = np.asarray(got), np.asarray(want)
+    assert got.dtype == want.dtype, (got.dtype, want.dtype)
+    if where is not None:
+        got, want = got[where], want[where]
+    np.testing.assert_array_equal(got, want)
+
+
+@pytest.mark.parametrize("dtype", ["float64", "float32"])
+@pytest.mark.parametrize("case", NAN_EXTREMES, ids=[c[0] for c in NAN_EXTREMES])
+def test_float_extremes_nan_rule_one_column(case, dtype):
+    v, m, mn, mx, amin, amax, ok, cmin, cmax = _nan_case(case, dtype)
+    sel = np.ones(len(v), bool) if m is None else m
+    dt = np.dtype(dtype).type
+    # reduce
+    for op, want in (("min", mn), ("max", mx)):
+        r, rok = orc.reduce(v, op, m)
+        assert rok == ok
+        if ok:
+            _same(r, dt(want))
+    # one group: hash-path and sort-path aggregations
+    keys = np.full(len(v), 4, np.int32)
+    _, res = orc.groupby_agg(keys, v, ["min", "max", "argmin", "argmax"], None, m)
+    for agg, want in (("min", mn), ("max", mx)):
+        assert res[agg][1].tolist() == [ok]
+        _, _, so, sok = orc.groupby_sort_agg(keys, v, agg, None, m)
+        assert sok.tolist() == [ok]
+        if ok:
+            _same(res[agg][0], np.array([want], dtype))
+            _same(so, np.array([want], dtype))
+    for agg, want in (("argmin", amin), ("argmax", amax)):
+        assert res[agg][1].tolist() == [ok]
+        if ok:
+            _same(res[agg][0], np.array([want], np.int32))
+    # scans: inclusive, and the exclusive one is the inclusive one shifted behind the identity
+    for op, want, ident in (("min", cmin, np.inf), ("max", cmax, -np.inf)):
+        out, om = orc.scan(v, op, True, m)
+        np.testing.assert_array_equal(om, sel)
+        _same(out, want, sel)
+        exc, em = orc.scan(v, op, False, m)
+        np.testing.assert_array_equal(em, sel)
+        assert exc[0] == dt(ident) and exc.dtype == v.dtype
+        _, gout, gm = orc.groupby_scan(keys, v, op, None, m)
+        np.testing.assert_array_equal(gm, sel)
+        _same(gout, want, sel)
+
+
+def test_float_extremes_nan_rule_exclusive_scan_and_null_include():
+    v = np.array([_N, 2.0, _N, 1.0])
+    _same(orc.scan(v, "min", False)[0], np.array([np.inf, _N, 2.0, 2.0]))
+    _same(orc.scan(v, "max", False)[0], np.array([-np.inf, _N, _N, _N]))
+    v = np.array([3.0, 1.0, _N, 0.5], np.float32)
+    _same(orc.scan(v, "min", False)[0], np.array([np.inf, 3.0, 1.0, 1.0], np.float32))
+    _same(orc.scan(v, "max", False)[0], np.array([-np.inf, 3.0, 3.0, _N], np.float32))
+    # a null before the NaN: the rows behind it still see the identity, then the NaN, then the number
+    v, m = np.array([5.0, _N, 1.0, 8.0]), np.array([_F, _T, _T, _T])
+    out, om = orc.scan(v, "min", False, m)
+    assert om.tolist() == [_F, _T, _T, _T]
+    _same(out[1:], np.array([np.inf, _N, 1.0]))
+    out, om = orc.scan(v, "max", False, m)
+    _same(out[1:], np.array([-np.inf, _N, _N]))
+    # null_policy::INCLUDE: everything from the first null on is null (one row later in an exclusive scan); the values do not change
+    v, m = np.array([_N, 4.0, 0.0, _N]), np.array([_T, _T, _F, _T])
+    out, om = orc.scan(v, "min", True, m, null_include=True)
+    assert om.tolist() == [_T, _T, _F, _F]
+    _same(out[:2], np.array([_N, 4.0]))
+    out, om = orc.scan(v, "max", False, m, null_include=True)
+    assert om.tolist() == [_T, _T, _T, _F]
+    _same(out[:3], np.array([-np.inf, _N, _N]))
+
+
+@pytest.mark.parametrize("dtype", ["float64", "float32"])
+def test_float_extremes_nan_rule_groups(dtype):
+    """four groups in one table, keys unsorted: {1, NaN, 0.5}, {null, NaN}, {NaN, NaN, NaN}, {null, null}"""
+    keys = np.array([30, 10, 20, 10, 40, 30, 10, 30, 20, 40], np.int32)
+    vals = np.array([_N, 1.0, 0.0, _N, 0.0, _N, 0.5, _N, _N, 0.0], dtype)
+    valid = np.array([_T, _T, _F, _T, _F, _T, _T, _T, _T, _F])
+    want_valid = [_T, _T, _T, _F]
+    uk, res = orc.groupby_agg(keys, vals, ["min", "max", "argmin", "argmax"], None, valid)
+    assert uk.tolist() == [10, 20, 30, 40]
+    for agg, want in (("min", [0.5, _N, _N]), ("max", [_N, _N, _N])):
+        assert res[agg][1].tolist() == want_valid
+        _same(res[agg][0][:3], np.array(want, dtype))
+        for keys_sorted in (False, True):
+            o = np.argsort(keys, kind="stable") if keys_sorted else np.arange(len(keys))
+            sk, _, so, sok = orc.groupby_sort_agg(keys[o], vals[o], agg, None, valid[o], False, keys_sorted)
+            assert sk.tolist() == [10, 20, 30, 40] and sok.tolist() == want_valid
+            _same(so[:3], np.array(want, dtype))
+    assert res["argmin"][1].tolist() == want_valid and res["argmax"][1].tolist() == want_valid
+    _same(res["argmin"][0][:3], np.array([6, 8, 0], np.int32))  # rows of the ORIGINAL table; the first NaN row of a NaN extreme
+    _same(res["argmax"][0][:3], np.array([3, 8, 0], np.int32))
+    # groupby::scan: rows in sorted-key order (stable): 10: [1, NaN, 0.5]  20: [null, NaN]  30: [NaN, NaN, NaN]  40: [null, null]
+    sel = np.array([_T, _T, _T, _F, _T, _T, _T, _T, _F, _F])
+    for op, want in (("min", [1.0, 1.0, 0.5, 0, _N, _N, _N, _N, 0, 0]), ("max", [1.0, _N, _N, 0, _N, _N, _N, _N, 0, 0])):
+        sk, out, om = orc.groupby_scan(keys, vals, op, None, valid)
+        assert sk.tolist() == [10, 10, 10, 20, 20, 30, 30, 30, 40, 40]
+        np.testing.assert_array_equal(om, sel)
+        _same(out, np.array(want, dtype), sel)
+    # a group's running minimum does not leak into the next one
+    sk, out, _ = orc.groupby_scan(np.array([1, 0, 1, 0], np.int32), np.array([_N, _N, 3.0, 2.0], dtype), "min")
+    _same(out, np.array([_N, 2.0, _N, 3.0], dtype))
+    sk, out, _ = orc.groupby_scan(np.array([1, 0, 1, 0], np.int32), np.array([3.0, _N, _N, 2.0], dtype), "max")
+    _same(out, np.array([_N, _N, 3.0, _N], dtype))
+
+
+@pytest.mark.parametrize("dtype", ["float64", "float32"])
+def test_float_scan_oracles_unchanged_on_nan_free_input(dtype):
+    """the scan oracles before the NaN rule: numpy's accumulate over the identity-filled column, pandas' grouped cummin / cummax"""
+    import pandas as pd
+    rng = np.random.default_rng(5)
+    n = 5000
+    v = (rng.standard_normal(n) * 100).astype(dtype)
+    v[rng.integers(0, n, 40)] = rng.choice(np.array([np.inf, -np.inf, 0.0, -0.0], dtype), 40)
+    keys = rng.integers(0, 9, n).astype(np.int32)
+    for m in (None, rng.random(n) > 0.2):
+        for op, f, ident in (("min", np.minimum.accumulate, np.inf), ("max", np.maximum.accumulate, -np.inf)):
+            x = v if m is None else np.where(m, v, np.dtype(dtype).type(ident)).astype(dtype)
+            for inclusive in (True, False):
+                want = f(x) if inclusive else np.concatenate([np.array([ident], dtype), f(x)[:-1]])
+                got, _ = orc.scan(v, op, inclusive, m)
+                assert got.dtype == want.dtype and got.tobytes() == want.tobytes()
+            o = np.argsort(keys, kind="stable")
+            gb = pd.Series(x[o]).groupby(keys[o])
+            want = (gb.cummin() if op == "min" else gb.cummax()).to_numpy().astype(dtype)
+            _, got, _ = orc.groupby_scan(keys, v, op, None, m)
+            assert got.dtype == want.dtype and got.tobytes() == want.tobytes()
