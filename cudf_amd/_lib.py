@@ -138,6 +138,7 @@ _PROTOS = {
     "gx_rows_mismatch_count": (_i, [_i, _p, _p, _p, _p, _p, _i64, _p, _p]),
     "gx_dense_rank": (_i, [_i, _p, _p, _i64, _i64, _p, _p, _p, _p, _sz, _p]),
     "gx_square": (_i, [_i, _p, _i64, _p, _p]),
+    "gx_square_centered": (_i, [_p, _p, _p, _i64, _i64, _p, _p]),
     "gx_var_from_sums": (_i, [_i, _p, _p, _p, _i64, _i, _i, _p, _p, _p, _p]),
     "gx_groupby_arg_select": (_i, [_i, _p, _p, _p, _i64, _p, _i64, _p, _p]),
     "gx_fill_nulls": (_i, [_i, _p, _p, _i64, ctypes.c_uint64, _p]),

@@ -338,24 +338,43 @@ std::pair<std::unique_ptr<table>, std::vector<aggregation_result>> groupby::aggr
 
   for (std::size_t i = 0; i < requests.size(); ++i) {
     auto const& req = requests[i];
-    bool want_sum = false, want_mm = false, want_sq = false, want_arg = false;
+    bool want_sum = false, want_mm = false, want_arg = false, want_ssq = false, want_var = false;
     for (auto const& agg : req.aggregations) {
       CUDF_EXPECTS(needs_sum(agg->kind) || needs_mm(agg->kind) || needs_sq(agg->kind),
                    "groupby aggregation kind not implemented on this path (SUM, COUNT, MEAN, MIN, MAX, ARGMIN, ARGMAX, "
                    "SUM_OF_SQUARES, M2, VARIANCE, STD are)");
       want_sum = want_sum || needs_sum(agg->kind) || needs_sq(agg->kind);
       want_mm  = want_mm || needs_mm(agg->kind);
-      want_sq  = want_sq || needs_sq(agg->kind);
       want_arg = want_arg || agg->kind == aggregation::ARGMIN || agg->kind == aggregation::ARGMAX;
+      want_ssq = want_ssq || agg->kind == aggregation::SUM_OF_SQUARES;
+      want_var = want_var || (needs_sq(agg->kind) && agg->kind != aggregation::SUM_OF_SQUARES);
     }
-    hash_agg_out o, q;
+    // float M2 / VARIANCE / STD: the shifted two-pass in FLOAT64 (the comment above k_square in gx_groupby.hip)
+    bool const centred = want_var && is_floating_point(req.values.type());
+    hash_agg_out o, q, qc;
     hash_minmax_out mm;
-    std::unique_ptr<column> order, mm_order, sq_order, group_of_row;
+    std::unique_ptr<column> order, mm_order, sq_order, c_order, group_of_row;
+    // row -> position of its key among one pass's groups: a lookup table over the distinct keys
+    auto lookup_groups = [&](column_view const& group_keys, char const* what) {
+      auto const ksz    = static_cast<int>(size_of(keys.type()));
+      auto const tbytes = gx_join_table_bytes(ksz, group_keys.size(), 0.5);
+      rmm::device_buffer table{tbytes, stream};
+      detail::gx_check(gx_join_build(ksz, group_keys.head<void>(), nullptr, group_keys.size(), table.data(), tbytes, 0.5,
+                                     detail::gxs(stream)),
+                       what);
+      auto rows = make_fixed_width_column(data_type{type_id::INT32}, keys.size(), mask_state::UNALLOCATED, stream);
+      rmm::device_buffer kh;
+      auto const* kmask = keys.has_nulls() ? detail::rebased_mask(keys, kh, stream) : nullptr;
+      detail::gx_check(gx_join_lookup(ksz, detail::row0(keys), kmask, keys.size(), table.data(), tbytes,
+                                      rows->mutable_view().head<int32_t>(), detail::gxs(stream)),
+                       what);
+      return rows;
+    };
     if (want_sum || !want_mm) {
       o = hash_aggregate(keys, req.values, stream, mr);
       if (canonical) order = cudf::sorted_order(table_view{{o.keys->view()}}, {}, {}, stream);
     }
-    if (want_sq) {  // second SUM pass over the squared values (same validity): SUM_OF_SQUARES
+    if (want_ssq || (want_var && !centred)) {  // second SUM pass over the squared values (same validity): SUM_OF_SQUARES
       auto const& v = req.values;
       auto sq       = make_fixed_width_column(sum_type(v.type()), v.size(), mask_state::UNALLOCATED, stream);
       detail::gx_check(gx_square(detail::gx_type(v.type()), detail::row0(v), v.size(), sq->mutable_view().head<void>(),
@@ -368,6 +387,39 @@ std::pair<std::unique_ptr<table>, std::vector<aggregation_result>> groupby::aggr
       q        = hash_aggregate(keys, sqv, stream, mr);
       sq_order = cudf::sorted_order(table_view{{q.keys->view()}}, {}, {}, stream);  // passes >= 2: canonical is set
     }
+    if (centred) {
+      auto const& v = req.values;
+      auto const n  = v.size();
+      rmm::device_buffer holder;
+      auto const* m = v.has_nulls() ? detail::rebased_mask(v, holder, stream) : nullptr;
+      // FLOAT32 values: cast once, and a SUM pass of their own in FLOAT64 (o keeps the FLOAT32 sum that SUM / MEAN return)
+      std::unique_ptr<column> wide;
+      hash_agg_out w;
+      void const* x = detail::row0(v);
+      if (v.type().id() != type_id::FLOAT64) {
+        wide = make_fixed_width_column(data_type{type_id::FLOAT64}, n, mask_state::UNALLOCATED, stream);
+        detail::gx_check(gx_cast(detail::gx_type(v.type()), x, n, GX_FLOAT64, wide->mutable_view().head<void>(), detail::gxs(stream)),
+                         "groupby variance cast");
+        x = wide->view().head<void>();
+        w = hash_aggregate(keys, column_view{wide->type(), n, x, m, m ? v.null_count() : 0}, stream, mr);
+      }
+      auto const& base = wide ? w : o;
+      auto const gb    = base.keys->size();
+      auto mean        = make_fixed_width_column(data_type{type_id::FLOAT64}, gb, mask_state::UNALLOCATED, stream);
+      auto sq          = make_fixed_width_column(data_type{type_id::FLOAT64}, n, mask_state::UNALLOCATED, stream);
+      if (gb > 0)
+        detail::gx_check(gx_mean_from_sum(GX_FLOAT64, base.sum->view().head<void>(), base.count_valid->view().head<int32_t>(), gb,
+                                          mean->mutable_view().head<double>(), detail::gxs(stream)),
+                         "groupby mean");
+      if (gb > 0) {
+        auto rows = lookup_groups(base.keys->view(), "groupby variance lookup");
+        detail::gx_check(gx_square_centered(static_cast<double const*>(x), rows->view().head<int32_t>(), mean->view().head<double>(), n,
+                                            gb, sq->mutable_view().head<double>(), detail::gxs(stream)),
+                         "groupby centred squares");
+      }  // no group: every key is null and the pass below drops every row
+      qc      = hash_aggregate(keys, column_view{sq->type(), n, sq->view().head<void>(), m, m ? v.null_count() : 0}, stream, mr);
+      c_order = cudf::sorted_order(table_view{{qc.keys->view()}}, {}, {}, stream);
+    }
     if (want_mm) {
       mm = hash_minmax(keys, req.values, stream, mr);
       if (canonical) mm_order = cudf::sorted_order(table_view{{mm.keys->view()}}, {}, {}, stream);
@@ -376,21 +428,7 @@ std::pair<std::unique_ptr<table>, std::vector<aggregation_result>> groupby::aggr
         o.count_valid = std::make_unique<column>(mm.count_valid->view(), stream, mr);
         if (canonical) order = std::make_unique<column>(mm_order->view(), stream, mr);
       }
-      if (want_arg && mm.keys->size() > 0) {
-        // row -> position of its key among this pass's groups: a lookup table over the distinct keys
-        auto const ksz    = static_cast<int>(size_of(keys.type()));
-        auto const tbytes = gx_join_table_bytes(ksz, mm.keys->size(), 0.5);
-        rmm::device_buffer table{tbytes, stream};
-        detail::gx_check(gx_join_build(ksz, mm.keys->view().head<void>(), nullptr, mm.keys->size(), table.data(), tbytes, 0.5,
-                                       detail::gxs(stream)),
-                         "groupby argmin/argmax dictionary");
-        group_of_row = make_fixed_width_column(data_type{type_id::INT32}, keys.size(), mask_state::UNALLOCATED, stream);
-        rmm::device_buffer kh;
-        auto const* kmask = keys.has_nulls() ? detail::rebased_mask(keys, kh, stream) : nullptr;
-        detail::gx_check(gx_join_lookup(ksz, detail::row0(keys), kmask, keys.size(), table.data(), tbytes,
-                                        group_of_row->mutable_view().head<int32_t>(), detail::gxs(stream)),
-                         "groupby argmin/argmax lookup");
-      }
+      if (want_arg && mm.keys->size() > 0) group_of_row = lookup_groups(mm.keys->view(), "groupby argmin/argmax lookup");
     }
     auto fin = [&](std::unique_ptr<column> c) {
       return canonical ? permute(c->view(), order->view(), stream, mr) : std::move(c);
@@ -449,9 +487,11 @@ std::pair<std::unique_ptr<table>, std::vector<aggregation_result>> groupby::aggr
         case aggregation::M2:
         case aggregation::VARIANCE:
         case aggregation::STD: {
-          // both passes brought into key order, then M2 = sum_sqr - sum^2/count etc. (m2_var_std.cu:44-61,153-190)
-          auto ssum = permute(q.sum->view(), sq_order->view(), stream, mr);
-          auto sum  = permute(o.sum->view(), order->view(), stream, mr);
+          // the passes brought into key order; integers: M2 = sum_sqr - sum^2/count etc. (m2_var_std.cu:44-61,153-190),
+          // floats: M2 = the sum of the centred squares
+          auto ssum = centred ? permute(qc.sum->view(), c_order->view(), stream, mr) : permute(q.sum->view(), sq_order->view(), stream, mr);
+          std::unique_ptr<column> sum;
+          if (!centred) sum = permute(o.sum->view(), order->view(), stream, mr);
           auto cv   = permute(o.count_valid->view(), order->view(), stream, mr);
           auto c    = make_fixed_width_column(data_type{type_id::FLOAT64}, g, mask_state::UNALLOCATED, stream, mr);
           rmm::device_buffer mask = create_null_mask(g, mask_state::ALL_VALID, stream, mr);
@@ -459,8 +499,9 @@ std::pair<std::unique_ptr<table>, std::vector<aggregation_result>> groupby::aggr
           int ddof = 1;
           if (auto const* sv = dynamic_cast<detail::std_var_aggregation const*>(agg.get())) ddof = sv->_ddof;
           int const mode = agg->kind == aggregation::M2 ? 0 : (agg->kind == aggregation::VARIANCE ? 1 : 2);
-          detail::gx_check(gx_var_from_sums(detail::gx_type(sum->type()), ssum->view().head<void>(), sum->view().head<void>(),
-                                            cv->view().head<int32_t>(), g, ddof, mode, c->mutable_view().head<double>(),
+          detail::gx_check(gx_var_from_sums(detail::gx_type(ssum->type()), ssum->view().head<void>(),
+                                            centred ? nullptr : sum->view().head<void>(), cv->view().head<int32_t>(), g, ddof,
+                                            mode, c->mutable_view().head<double>(),
                                             static_cast<uint32_t*>(mask.data()), static_cast<int64_t*>(cnt.data()),
                                             detail::gxs(stream)),
                            "groupby variance");

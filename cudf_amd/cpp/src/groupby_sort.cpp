@@ -265,6 +265,51 @@ std::pair<std::unique_ptr<table>, std::vector<aggregation_result>> groupby::sort
         case aggregation::M2:
         case aggregation::VARIANCE:
         case aggregation::STD: {
+          int ddof = 1;
+          if (auto const* sva = dynamic_cast<cudf::detail::std_var_aggregation const*>(agg.get())) ddof = sva->_ddof;
+          int const mode = agg->kind == aggregation::M2 ? 0 : (agg->kind == aggregation::VARIANCE ? 1 : 2);
+          auto finalise  = [&](column const& ssq, void const* sum) {
+            out = make_fixed_width_column(data_type{type_id::FLOAT64}, g, mask_state::UNALLOCATED, stream, mr);
+            if (g == 0) return;
+            rmm::device_buffer mask = create_null_mask(g, mask_state::ALL_VALID, stream, mr);
+            rmm::device_buffer cnt{sizeof(int64_t), stream};
+            detail::gx_check(gx_var_from_sums(detail::gx_type(ssq.type()), ssq.view().head<void>(), sum, counts->view().head<int32_t>(), g,
+                                              ddof, mode, out->mutable_view().head<double>(), static_cast<uint32_t*>(mask.data()),
+                                              static_cast<int64_t*>(cnt.data()), detail::gxs(stream)),
+                             "groupby variance");
+            auto const nulls = static_cast<size_type>(detail::read_i64(static_cast<int64_t const*>(cnt.data()), stream));
+            if (nulls > 0) out->set_null_mask(std::move(mask), nulls);
+          };
+          if (agg->kind != aggregation::SUM_OF_SQUARES && is_floating_point(sv.type())) {
+            // float values: the shifted two-pass in FLOAT64 (the comment above k_square in gx_groupby.hip) -- the group means,
+            // then the group sums of (x - mean)^2; the row -> group map is the labels
+            std::unique_ptr<column> wide;
+            column_view dv = sv;
+            if (sv.type().id() != type_id::FLOAT64) {
+              wide = make_fixed_width_column(data_type{type_id::FLOAT64}, n, mask_state::UNALLOCATED, stream);
+              if (n > 0)
+                detail::gx_check(gx_cast(detail::gx_type(sv.type()), detail::row0(sv), n, GX_FLOAT64, wide->mutable_view().head<void>(),
+                                         detail::gxs(stream)),
+                                 "groupby variance cast");
+              dv = column_view{wide->type(), n, wide->view().head<void>(), vmask, vmask ? sv.null_count() : 0};
+            }
+            auto sum    = seg_reduce(dv, vmask, GX_OP_SUM, dv.type(), true);
+            have_counts = true;
+            auto mean   = make_fixed_width_column(data_type{type_id::FLOAT64}, g, mask_state::UNALLOCATED, stream);
+            auto sq     = make_fixed_width_column(data_type{type_id::FLOAT64}, n, mask_state::UNALLOCATED, stream);
+            if (g > 0)
+              detail::gx_check(gx_mean_from_sum(GX_FLOAT64, sum->view().head<void>(), counts->view().head<int32_t>(), g,
+                                                mean->mutable_view().head<double>(), detail::gxs(stream)),
+                               "groupby mean");
+            if (n > 0)
+              detail::gx_check(gx_square_centered(static_cast<double const*>(detail::row0(dv)), labels, mean->view().head<double>(), n, g,
+                                                  sq->mutable_view().head<double>(), detail::gxs(stream)),
+                               "groupby centred squares");
+            column_view sqv{sq->type(), n, sq->view().head<void>(), vmask, vmask ? sv.null_count() : 0};
+            auto ssq = seg_reduce(sqv, vmask, GX_OP_SUM, sq->type(), false);
+            finalise(*ssq, nullptr);
+            break;
+          }
           auto sq = make_fixed_width_column(sum_type_of(sv.type()), n, mask_state::UNALLOCATED, stream);
           if (n > 0)
             detail::gx_check(gx_square(detail::gx_type(sv.type()), detail::row0(sv), n, sq->mutable_view().head<void>(), detail::gxs(stream)),
@@ -278,21 +323,7 @@ std::pair<std::unique_ptr<table>, std::vector<aggregation_result>> groupby::sort
             break;
           }
           auto sum = seg_reduce(sv, vmask, GX_OP_SUM, sum_type_of(sv.type()), false);
-          out      = make_fixed_width_column(data_type{type_id::FLOAT64}, g, mask_state::UNALLOCATED, stream, mr);
-          if (g > 0) {
-            rmm::device_buffer mask = create_null_mask(g, mask_state::ALL_VALID, stream, mr);
-            rmm::device_buffer cnt{sizeof(int64_t), stream};
-            int ddof = 1;
-            if (auto const* sva = dynamic_cast<cudf::detail::std_var_aggregation const*>(agg.get())) ddof = sva->_ddof;
-            int const mode = agg->kind == aggregation::M2 ? 0 : (agg->kind == aggregation::VARIANCE ? 1 : 2);
-            detail::gx_check(gx_var_from_sums(detail::gx_type(sum->type()), ssq->view().head<void>(), sum->view().head<void>(),
-                                              counts->view().head<int32_t>(), g, ddof, mode, out->mutable_view().head<double>(),
-                                              static_cast<uint32_t*>(mask.data()), static_cast<int64_t*>(cnt.data()),
-                                              detail::gxs(stream)),
-                             "groupby variance");
-            auto const nulls = static_cast<size_type>(detail::read_i64(static_cast<int64_t const*>(cnt.data()), stream));
-            if (nulls > 0) out->set_null_mask(std::move(mask), nulls);
-          }
+          finalise(*ssq, sum->view().head<void>());
           break;
         }
         case aggregation::ARGMIN:

@@ -1547,12 +1547,22 @@ int gx_mean_from_sum(int sum_dtype, const void* sum, const int32_t* count, int64
 
 // ------------------------------------------------------------------------------------------------
 // Compound aggregations on top of the passes above.
-//   SUM_OF_SQUARES / M2 / VARIANCE / STD (hash path of the reference: SUM_OF_SQUARES is a single-pass
-//   aggregation, M2 = sum_sqr - sum * sum / count, VAR = M2 / (count - ddof), STD = sqrt(VAR), null when
-//   count - ddof <= 0: cpp/src/groupby/common/m2_var_std.cu:44-61,153-190,
+//   SUM_OF_SQUARES / M2 / VARIANCE / STD: VAR = M2 / (count - ddof), STD = sqrt(VAR), null when
+//   count - ddof <= 0 (cpp/src/groupby/common/m2_var_std.cu:44-61,153-190,
 //   cpp/src/groupby/hash/hash_compound_agg_finalizer.cu:135-186).  gx_square produces the squared values
 //   in the SUM accumulator type (integers -> int64, wrapping like the reference's int64 accumulator;
-//   floats keep their type); the caller sums them with gx_groupby_sum_count.
+//   floats keep their type); the caller sums them with gx_groupby_sum_count: that is SUM_OF_SQUARES.
+//   Integer values: M2 = sum_sqr - sum * sum / count in double from the two int64 sums, as the reference's
+//   hash path does it -- within 8 * 2^-53 * sum_sqr while sum_sqr < 2^53, and no better than the wrapped
+//   sums beyond.
+//   Float values: that formula cancels (constant groups give M2 < 0 and STD = NaN, a large mean leaves no
+//   digit), so they take a shifted two-pass in FLOAT64 (FLOAT32 values are cast first): mean = sum / count
+//   from the SUM pass, gx_square_centered writes (x - mean[group of the row])^2, a second SUM pass adds
+//   them, and gx_var_from_sums with sum == NULL takes that sum as M2.  With mean = mu + e the sum of the
+//   squares is M2* + count * e^2 exactly; the SUM passes are within 1 ulp (double-double accumulators), so
+//   |e| <= 3u|mu| (u = 2^-53), count * e^2 <= 9 u^2 * sum x^2, and the roundings of d, d^2 and the sum add
+//   at most 6u * M2*.  Contract (tests/test_gpu_groupby_moments.py): |M2 - M2*| <= 16u * M2* + 64u^2 * sum x^2,
+//   M2 >= 0, and a group holding a NaN or an infinity gives NaN (valid, not null).
 //   ARGMIN / ARGMAX: the row of the group's MIN / MAX value.  gx_groupby_arg_select takes the row -> group
 //   map (gx_join_lookup on the output keys) and the per-group target value and keeps the SMALLEST row
 //   whose value equals the target (floats: NaN == NaN, -0.0 == +0.0, the order MIN / MAX used).
@@ -1575,7 +1585,25 @@ __global__ void __launch_bounds__(256) k_square(const V* __restrict__ in, int64_
   }
 }
 
-// mode 0: M2, 1: VARIANCE, 2: STD
+// d = x - mean[group of the row] in double, out = d^2.  A row without a group (negative id: a null key)
+// writes 0; the caller's SUM pass drops it with its key.
+__global__ void __launch_bounds__(256) k_square_centered(const double* __restrict__ in, const int32_t* __restrict__ gid,
+                                                         const double* __restrict__ mean, int64_t n, int64_t groups,
+                                                         double* __restrict__ out)
+{
+  const int64_t stride = (int64_t)gridDim.x * 256;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += stride) {
+    const int32_t g = gid[i];
+    double r        = 0.0;
+    if (g >= 0 && g < groups) {
+      const double d = in[i] - mean[g];
+      r              = d * d;
+    }
+    out[i] = r;
+  }
+}
+
+// mode 0: M2, 1: VARIANCE, 2: STD.  sum == nullptr: sumsq holds the sum of the CENTRED squares, which is M2.
 template <typename S>
 __global__ void __launch_bounds__(256) k_var(const S* __restrict__ sumsq, const S* __restrict__ sum,
                                              const int32_t* __restrict__ cnt, int64_t n, int ddof, int mode,
@@ -1589,8 +1617,14 @@ __global__ void __launch_bounds__(256) k_var(const S* __restrict__ sumsq, const 
     if (i < n) {
       const int32_t c = cnt[i];
       if (c > 0) {
-        const double ss = (double)sumsq[i], sm = (double)sum[i];
-        const double m2 = ss - sm * sm / (double)c;
+        const double ss = (double)sumsq[i];
+        double m2;
+        if (sum) {
+          const double sm = (double)sum[i];
+          m2              = ss - sm * sm / (double)c;
+        } else {
+          m2 = ss < 0.0 ? 0.0 : ss;  // not fmax: a NaN stays a NaN
+        }
         if (mode == 0) {
           r  = m2;
           ok = true;
@@ -1681,22 +1715,34 @@ int gx_square(int dtype, const void* in, int64_t n, void* out, gx_stream_t s)
   return 0;
 }
 
+int gx_square_centered(const double* in, const int32_t* group_of_row, const double* mean, int64_t n, int64_t num_groups,
+                       double* out, gx_stream_t s)
+{
+  if (n < 0 || num_groups < 0 || (n > 0 && (!in || !group_of_row || !out)) || (n > 0 && num_groups > 0 && !mean)) return GX_EINVAL;
+  if (n == 0) return 0;
+  int64_t blocks = gx::div_up(n, (int64_t)256 * 8);
+  if (blocks > 16384) blocks = 16384;
+  hipLaunchKernelGGL(gx::gb::k_square_centered, dim3((unsigned)blocks), dim3(256), 0, s, in, group_of_row, mean, n, num_groups, out);
+  GX_LAUNCH_CHECK();
+  return 0;
+}
+
 int gx_var_from_sums(int sum_dtype, const void* sum_sqr, const void* sum, const int32_t* count, int64_t n, int ddof, int mode,
                      double* out, uint32_t* mask_out, int64_t* null_count_dev, gx_stream_t s)
 {
   if (n < 0 || mode < 0 || mode > 2 || !null_count_dev) return GX_EINVAL;
-  if (n > 0 && (!sum_sqr || !sum || !count || !out || !mask_out)) return GX_EINVAL;
+  if (n > 0 && (!sum_sqr || !count || !out || !mask_out)) return GX_EINVAL;
+  if (n > 0 && !sum && sum_dtype != GX_FLOAT64) return GX_EINVAL;  // centred squares are FLOAT64
+  if (sum_dtype != GX_INT64 && sum_dtype != GX_FLOAT64) return GX_EDTYPE;
   GX_HIP_TRY(hipMemsetAsync(null_count_dev, 0, sizeof(int64_t), s));
   if (n == 0) return 0;
   int64_t blocks = gx::div_up(n, (int64_t)256);
   if (blocks > 4096) blocks = 4096;
   auto* nulls = reinterpret_cast<unsigned long long*>(null_count_dev);
-  switch (sum_dtype) {
-    case GX_INT64: hipLaunchKernelGGL((gx::gb::k_var<int64_t>), dim3((unsigned)blocks), dim3(256), 0, s, static_cast<const int64_t*>(sum_sqr), static_cast<const int64_t*>(sum), count, n, ddof, mode, out, mask_out, nulls); break;
-    case GX_FLOAT64: hipLaunchKernelGGL((gx::gb::k_var<double>), dim3((unsigned)blocks), dim3(256), 0, s, static_cast<const double*>(sum_sqr), static_cast<const double*>(sum), count, n, ddof, mode, out, mask_out, nulls); break;
-    case GX_FLOAT32: hipLaunchKernelGGL((gx::gb::k_var<float>), dim3((unsigned)blocks), dim3(256), 0, s, static_cast<const float*>(sum_sqr), static_cast<const float*>(sum), count, n, ddof, mode, out, mask_out, nulls); break;
-    default: return GX_EDTYPE;
-  }
+  if (sum_dtype == GX_INT64)
+    hipLaunchKernelGGL((gx::gb::k_var<int64_t>), dim3((unsigned)blocks), dim3(256), 0, s, static_cast<const int64_t*>(sum_sqr), static_cast<const int64_t*>(sum), count, n, ddof, mode, out, mask_out, nulls);
+  else
+    hipLaunchKernelGGL((gx::gb::k_var<double>), dim3((unsigned)blocks), dim3(256), 0, s, static_cast<const double*>(sum_sqr), static_cast<const double*>(sum), count, n, ddof, mode, out, mask_out, nulls);
   GX_LAUNCH_CHECK();
   return 0;
 }

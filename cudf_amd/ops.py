@@ -885,15 +885,30 @@ def _sum_dtype(dt) -> np.dtype:
 
 
 def groupby_var_std(keys: Column, values: Column, ddof: int = 1):
-    """groupby VARIANCE / STD / M2 the way the reference's hash path computes them: SUM, COUNT_VALID and
-    SUM_OF_SQUARES per group, then M2 = sum_sqr - sum^2/count, VAR = M2/(count - ddof), STD = sqrt(VAR)
-    (src/groupby/common/m2_var_std.cu:44-61,153-190).  Returns (keys, var, std, m2, count_valid) with
-    the groups in ascending key order; var / std are null where count - ddof <= 0."""
+    """groupby VARIANCE / STD / M2: VAR = M2/(count - ddof), STD = sqrt(VAR) (src/groupby/common/m2_var_std.cu:44-61,153-190).
+    Integer values, the way the reference's hash path computes them: SUM, COUNT_VALID and SUM_OF_SQUARES per group in
+    wrapping int64, then M2 = sum_sqr - sum^2/count in double (within 8 * 2^-53 * sum_sqr while sum_sqr < 2^53).
+    Float values (FLOAT32 is cast to FLOAT64 first): a shifted two-pass, since that formula cancels -- mean = SUM / COUNT_VALID,
+    then M2 = the group sums of (x - mean[group of the row])^2 (gx_square_centered over a row -> group lookup).  With u = 2^-53:
+    |M2 - exact| <= 16u * exact + 64u^2 * sum x^2, M2 >= 0 and VAR >= 0, STD is never NaN for finite values, and a group holding
+    a NaN or an infinity gives a valid NaN for all three.
+    Returns (keys, var, std, m2, count_valid) with the groups in ascending key order; var / std are null where
+    count - ddof <= 0, m2 of a group without a valid value is 0."""
     n = keys.size
+    centred = values.dtype.kind == "f"
+    if centred and values.dtype != np.float64:
+        values = cast(values, np.float64)
     k, s, cv, _ = groupby_sum_count(keys, values)
     sq = Column(device_bytes(n * _sum_dtype(values.dtype).itemsize), _sum_dtype(values.dtype), n, values.mask,
                 values.null_count)
-    L.check(_lib.gx_square(values.gx, values.data_ptr, n, sq.data_ptr, stream_ptr()), "gx_square")
+    if centred:
+        mean = Column.empty(np.float64, k.size)
+        L.check(_lib.gx_mean_from_sum(s.gx, s.data_ptr, cv.data_ptr, k.size, mean.data_ptr, stream_ptr()), "gx_mean_from_sum")
+        gid = HashJoin(k).lookup(keys)  # row -> position of its key in k (negative for null keys)
+        L.check(_lib.gx_square_centered(values.data_ptr, gid.data_ptr, mean.data_ptr, n, k.size, sq.data_ptr, stream_ptr()),
+                "gx_square_centered")
+    else:
+        L.check(_lib.gx_square(values.gx, values.data_ptr, n, sq.data_ptr, stream_ptr()), "gx_square")
     k2, ss, _, _ = groupby_sum_count(keys, sq)
     o1, o2 = sorted_order(k), sorted_order(k2)  # the two hash passes emit the groups in their own orders
     k, s, cv, ss = gather(k, o1), gather(s, o1), gather(cv, o1), gather(ss, o2)
@@ -902,7 +917,7 @@ def groupby_var_std(keys: Column, values: Column, ddof: int = 1):
     for mode in (1, 2, 0):
         o = Column.empty(np.float64, g, nullable=True)
         cnt = _dev_i64()
-        L.check(_lib.gx_var_from_sums(s.gx, ss.data_ptr, s.data_ptr, cv.data_ptr, g, int(ddof), mode, o.data_ptr,
+        L.check(_lib.gx_var_from_sums(s.gx, ss.data_ptr, None if centred else s.data_ptr, cv.data_ptr, g, int(ddof), mode, o.data_ptr,
                                       o.mask_ptr, ptr(cnt), stream_ptr()), "gx_var_from_sums")
         o.null_count = int(cnt.item())
         outs.append(o)

@@ -821,14 +821,22 @@ int gx_groupby_min_max(int key_dtype, const void* keys, const uint32_t* keys_val
  * gx_square: out[i] = in[i]^2 in the SUM accumulator type of `dtype` (integers -> int64 wrapping mod
  *   2^64, FLOAT32/64 keep their type): the values of the reference's single-pass SUM_OF_SQUARES
  *   (include/cudf/detail/aggregation/aggregation.hpp:944-954), summed by gx_groupby_sum_count.
- * gx_var_from_sums: mode 0 M2 = sum_sqr - sum^2/count (valid for every group), 1 VARIANCE = M2/(count-ddof),
+ * gx_square_centered: out[i] = (in[i] - mean[group_of_row[i]])^2 in FLOAT64, 0 where group_of_row[i] is
+ *   outside [0, num_groups) (a row whose key is null).  The second pass of the float VARIANCE / STD / M2:
+ *   mean = gx_mean_from_sum of the SUM pass, the squares are summed by the same SUM pass as the values.
+ * gx_var_from_sums: mode 0 M2 (valid for every group), 1 VARIANCE = M2/(count-ddof),
  *   2 STD = sqrt(VARIANCE); null where count == 0 or count - ddof <= 0
  *   (src/groupby/common/m2_var_std.cu:44-61,153-190; hash_compound_agg_finalizer.cu:135-186).
- *   sum_dtype GX_INT64 / GX_FLOAT64 / GX_FLOAT32; mask_out holds ceil(n/32) words; *null_count_dev = nulls.
+ *   sum != NULL (integer values, sum_dtype GX_INT64; also GX_FLOAT64): M2 = sum_sqr - sum^2/count in double.
+ *   sum == NULL (float values, sum_dtype GX_FLOAT64): sum_sqr is the sum of gx_square_centered and M2 is that
+ *   sum, with a negative one raised to 0 and a NaN kept.
+ *   mask_out holds ceil(n/32) words; *null_count_dev = nulls.
  * gx_groupby_arg_select: ARGMIN / ARGMAX (global_memory_aggregator.cuh: ARGMIN/ARGMAX updates): out_rows[g] =
  *   the smallest row i with group_of_row[i] == g, a valid value and vals[i] == target[g] (target = the
  *   group's MIN or MAX; floats NaN == NaN); 0x7F7F7F7F where the group has no valid value. */
 int gx_square(int dtype, const void* in, int64_t n, void* out, gx_stream_t stream);
+int gx_square_centered(const double* in, const int32_t* group_of_row, const double* mean, int64_t n,
+                       int64_t num_groups, double* out, gx_stream_t stream);
 int gx_var_from_sums(int sum_dtype, const void* sum_sqr, const void* sum, const int32_t* count, int64_t n,
                      int ddof, int mode, double* out, uint32_t* mask_out, int64_t* null_count_dev,
                      gx_stream_t stream);

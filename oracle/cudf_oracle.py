@@ -20,6 +20,7 @@ CCCL, cuco, rmm and an NVIDIA GPU), so there is no ``oracle/_ref``.
 from __future__ import annotations
 
 import math
+from fractions import Fraction
 from typing import Optional, Sequence, Tuple
 
 import numpy as np
@@ -656,6 +657,33 @@ def _exact_group_sums(labels: np.ndarray, values: np.ndarray, ngroups: int) -> n
     for g in range(ngroups):
         out[g] = exact_sum(sv[bounds[g] : bounds[g + 1]])
     return out
+
+
+def exact_m2(m, q, labels: np.ndarray, ngroups: int):
+    """The exact second moments of groups of dyadic values x = m * 2^-q (m: integers, q: one exponent or one per row; rows with
+    a negative label belong to no group).  Per group with c rows, in Python integers on the group's largest q:
+    N = c * sum(m^2) - sum(m)^2, then M2 = sum (x - mean)^2 = N / (c * 4^q) and S2 = sum x^2 = sum(m^2) / 4^q, each rounded
+    ONCE to float64 (Fraction -> float rounds correctly).  Returns (M2, S2, count); an empty group gives 0, 0, 0."""
+    labels = np.asarray(labels).reshape(-1)
+    m = np.asarray(m, dtype=object).reshape(-1)
+    q = np.broadcast_to(np.asarray(q, np.int64), labels.shape)
+    keep = labels >= 0
+    order = np.argsort(labels[keep], kind="stable")
+    lab, ms, qs = labels[keep][order], m[keep][order].tolist(), q[keep][order].tolist()
+    bounds = np.searchsorted(lab, np.arange(ngroups + 1)).tolist()
+    m2, s2, cnt = np.zeros(ngroups, np.float64), np.zeros(ngroups, np.float64), np.zeros(ngroups, np.int64)
+    for g in range(ngroups):
+        lo, hi = bounds[g], bounds[g + 1]
+        c = hi - lo
+        if c == 0:
+            continue
+        qg = max(qs[lo:hi])
+        mg = [int(a) << (qg - b) for a, b in zip(ms[lo:hi], qs[lo:hi])]
+        s1, sq = sum(mg), sum(a * a for a in mg)
+        m2[g] = float(Fraction(c * sq - s1 * s1, c * 4**qg))
+        s2[g] = float(Fraction(sq, 4**qg))
+        cnt[g] = c
+    return m2, s2, cnt
 
 
 def groupby_agg(keys: np.ndarray, values: np.ndarray, aggs: Sequence[str],
