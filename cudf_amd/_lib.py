@@ -43,6 +43,10 @@ UNOPS = ("SIN", "COS", "TAN", "ARCSIN", "ARCCOS", "ARCTAN", "SINH", "COSH", "TAN
          "SQRT", "CBRT", "CEIL", "FLOOR", "ABS", "RINT", "BIT_COUNT", "BIT_INVERT", "NOT", "NEGATE")
 UNOP = {name: code for code, name in enumerate(UNOPS)}
 UNOP.update(IS_NAN=100, IS_NOT_NAN=101)
+# gx_interp (== cudf::interpolation), gx_quantile_mode, gx_quantile_path
+INTERP = {"linear": 0, "lower": 1, "higher": 2, "midpoint": 3, "nearest": 4}
+QUANTILE_MODE = {"auto": 0, "select": 1, "sort": 2}
+QUANTILE_PATH = {1: "select", 2: "select_direct", 3: "sort"}
 
 _PROTOS = {
     "gx_version": (ctypes.c_char_p, []),
@@ -226,6 +230,15 @@ _PROTOS = {
     "gx_repeat_map": (_i, [_p, _i64, _i64, _p, _p, _sz, _p]),
     "gx_fill_range": (_i, [_i, _p, _i64, _i64, _p, _p]),
     "gx_sequence": (_i, [_i, _p, _i64, _p, _p, _p]),
+    # quantiles (gx_quantile.hip): select / sort paths for an unsorted column, the lookup kernel for known order
+    "gx_quantile_tile_rows": (_i, []),
+    "gx_quantile_index": (_i, [_i64, ctypes.c_double, ctypes.POINTER(_i64), ctypes.POINTER(_i64), ctypes.POINTER(_i64),
+                               ctypes.POINTER(ctypes.c_double)]),
+    "gx_quantile": (_i, [_i, _p, _p, _i64, _i64, ctypes.POINTER(ctypes.c_double), _i, _i, _i, _p, _p, _p, ctypes.POINTER(_i), _p, _sz, _p]),
+    "gx_quantile_status": (_i, [_p, ctypes.POINTER(_i), _p]),
+    "gx_quantile_lookup": (_i, [_i, _p, _p, _i64, _p, _i64, _p, _p, ctypes.POINTER(ctypes.c_double), _i, _i, _i, _p, _p, _p, _p]),
+    "gx_quantile_set_thresholds": (None, [_i64, ctypes.c_double]),
+    "gx_quantile_get_thresholds": (None, [ctypes.POINTER(_i64), ctypes.POINTER(ctypes.c_double)]),
 }
 
 for _name, (_res, _args) in _PROTOS.items():

@@ -118,6 +118,22 @@ class Column:
         from . import ops
         return ops.repeat(self, repeats)
 
+    def quantile(self, q=0.5, interpolation: str = "linear"):
+        """pandas' Series.quantile: nulls are skipped.  A scalar q gives a Python float (None when no row is valid), a list a FLOAT64
+        Column (ops.quantile)."""
+        from . import ops
+        qs = list(q) if np.ndim(q) else [q]
+        if any(not 0.0 <= float(x) <= 1.0 for x in qs):
+            raise ValueError("percentiles should all be in the interval [0, 1]")
+        out = ops.quantile(self, qs, interpolation)
+        if np.ndim(q):
+            return out
+        return None if out.null_count else float(out.to_numpy()[0])
+
+    def median(self):
+        """pandas' Series.median: the 0.5 quantile, linear"""
+        return self.quantile(0.5)
+
     def to_numpy(self) -> np.ndarray:
         nbytes = self.size * self.dtype.itemsize
         return self.data[:nbytes].cpu().numpy().view(self.dtype).copy()

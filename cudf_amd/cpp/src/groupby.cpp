@@ -240,7 +240,8 @@ std::pair<std::unique_ptr<table>, std::vector<aggregation_result>> groupby::aggr
   bool sort_path = _keys_are_sorted == sorted::YES || (_include_null_keys == null_policy::INCLUDE && cudf::has_nulls(_keys));
   for (auto const& r : requests)
     for (auto const& agg : r.aggregations)
-      sort_path = sort_path || agg->kind == aggregation::PRODUCT || agg->kind == aggregation::NTH_ELEMENT;
+      sort_path = sort_path || agg->kind == aggregation::PRODUCT || agg->kind == aggregation::NTH_ELEMENT || agg->kind == aggregation::MEDIAN ||
+                  agg->kind == aggregation::QUANTILE;
   if (sort_path && _keys.num_rows() > 0 && !requests.empty()) return sort_aggregate(requests, stream, mr);
   // Several 8-byte integer key columns, one request of SUM / COUNT / MEAN, no nulls: ONE partition pass with the rows compared
   // inside the LDS tables (gx_groupby_sum_count_wide) -- no row encoding, no certificate.  The device may decline (-2).

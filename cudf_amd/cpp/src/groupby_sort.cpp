@@ -14,6 +14,7 @@
 #include <cudf/sorting.hpp>
 
 #include <algorithm>
+#include <limits>
 
 namespace cudf {
 namespace groupby {
@@ -366,9 +367,38 @@ std::pair<std::unique_ptr<table>, std::vector<aggregation_result>> groupby::sort
           out = std::move(t->release().front());
           break;
         }
+        case aggregation::MEDIAN:
+        case aggregation::QUANTILE: {
+          // sort/group_quantiles.cu: the values ordered inside their groups -- one stable order over (group label, value) with the
+          // value nulls after --, then one lookup thread per (group, quantile) over the group's valid count: FLOAT64, group-major,
+          // null for a group without a valid value
+          auto const* qa = dynamic_cast<cudf::detail::quantile_aggregation const*>(agg.get());
+          CUDF_EXPECTS(qa != nullptr, "groupby MEDIAN / QUANTILE need a quantile aggregation");
+          auto const nq = static_cast<size_type>(qa->_quantiles.size());
+          CUDF_EXPECTS(nq >= 1 && nq <= 64, "groupby QUANTILE: between 1 and 64 quantiles per aggregation", std::invalid_argument);
+          CUDF_EXPECTS(static_cast<int64_t>(g) * nq <= std::numeric_limits<size_type>::max(), "groupby QUANTILE: result exceeds size_type",
+                       std::overflow_error);
+          CUDF_EXPECTS(is_numeric(sv.type()) && sv.type().id() != type_id::BOOL8, "groupby MEDIAN / QUANTILE need a numeric, non-boolean column",
+                       cudf::data_type_error);
+          ensure_counts();
+          out = make_fixed_width_column(data_type{type_id::FLOAT64}, g * nq, mask_state::UNALLOCATED, stream, mr);
+          if (g == 0) break;
+          column_view lab{data_type{type_id::INT32}, n, labels, nullptr, 0};
+          auto order = cudf::stable_sorted_order(table_view{{lab, sv}}, {}, {null_order::AFTER, null_order::AFTER}, stream);
+          rmm::device_buffer mask = create_null_mask(g * nq, mask_state::ALL_VALID, stream, mr);
+          rmm::device_buffer cnt{sizeof(int64_t), stream};
+          detail::gx_check(gx_quantile_lookup(detail::gx_type(sv.type()), detail::row0(sv), vmask, 0, order->view().head<int32_t>(), g,
+                                              h.group_offsets(stream), counts->view().head<int32_t>(), qa->_quantiles.data(), nq,
+                                              static_cast<int>(qa->_interpolation), 1, out->mutable_view().head<void>(),
+                                              static_cast<uint32_t*>(mask.data()), static_cast<int64_t*>(cnt.data()), detail::gxs(stream)),
+                           "groupby quantile");
+          auto const nulls = static_cast<size_type>(detail::read_i64(static_cast<int64_t const*>(cnt.data()), stream));
+          if (nulls > 0) out->set_null_mask(std::move(mask), nulls);
+          break;
+        }
         default:
           CUDF_FAIL("groupby aggregation kind not implemented (SUM, PRODUCT, MIN, MAX, COUNT, MEAN, SUM_OF_SQUARES, M2, VARIANCE, "
-                    "STD, ARGMIN, ARGMAX, NTH_ELEMENT are)");
+                    "STD, ARGMIN, ARGMAX, NTH_ELEMENT, MEDIAN, QUANTILE are)");
       }
       results[i].results.emplace_back(std::move(out));
     }

@@ -24,7 +24,7 @@ int gx_op_of(aggregation::Kind k)
     case aggregation::PRODUCT: return GX_OP_PRODUCT;
     case aggregation::MIN: return GX_OP_MIN;
     case aggregation::MAX: return GX_OP_MAX;
-    default: CUDF_FAIL("aggregation kind not implemented on this path (SUM, PRODUCT, MIN, MAX, MEAN, COUNT_VALID, COUNT_ALL, ANY, ALL are)");
+    default: CUDF_FAIL("aggregation kind not implemented on this path (SUM, PRODUCT, MIN, MAX, MEAN, COUNT_VALID, COUNT_ALL, ANY, ALL, MEDIAN, QUANTILE are)");
   }
 }
 
@@ -128,6 +128,36 @@ std::unique_ptr<scalar> reduce_any_all(column_view const& col, bool is_any, data
   return std::make_unique<numeric_scalar<bool>>(result, valid, stream, mr);
 }
 
+// MEDIAN / QUANTILE (reductions/quantile.cu; reductions.cpp: exactly one quantile, else std::invalid_argument): the order statistic
+// of the valid elements through gx_quantile in AUTO mode -- the select path where it applies, no sort of the whole column -- computed
+// in FLOAT64 and cast to the output type; no valid row -> an invalid scalar
+std::unique_ptr<scalar> reduce_quantile(column_view const& col, reduce_aggregation const& agg, data_type output_type,
+                                        rmm::cuda_stream_view stream, rmm::device_async_resource_ref mr)
+{
+  auto const* qa = dynamic_cast<detail::quantile_aggregation const*>(&agg);
+  CUDF_EXPECTS(qa != nullptr, "reduce: MEDIAN / QUANTILE need a quantile aggregation");
+  if (qa->_quantiles.size() != 1) throw std::invalid_argument{"Reduction quantile accepts only one quantile value"};
+  CUDF_EXPECTS(is_arithmetic_id(col.type().id()) && col.type().id() != type_id::BOOL8, "quantile reduction needs a numeric, non-boolean column",
+               cudf::data_type_error);
+  CUDF_EXPECTS(is_arithmetic_id(output_type.id()), "Unsupported output data type", cudf::data_type_error);
+  if (col.size() - col.null_count() == 0) return host_scalar<double>(output_type, 0.0, false, stream, mr);
+  rmm::device_buffer value{sizeof(double), stream}, cnt{sizeof(int64_t), stream};
+  double const q = qa->_quantiles[0];
+  auto tmp       = detail::run_with_scratch(
+    [&](void* t, std::size_t* b) {
+      return gx_quantile(detail::gx_type(col.type()), detail::row0(col), col.has_nulls() ? col.null_mask() : nullptr, col.offset(), col.size(),
+                         &q, 1, static_cast<int>(qa->_interpolation), GX_QUANTILE_AUTO, static_cast<double*>(value.data()), nullptr,
+                         static_cast<int64_t*>(cnt.data()), nullptr, t, b, detail::gxs(stream));
+    },
+    "reduce (quantile)", stream);
+  int status = 0;
+  detail::gx_check(gx_quantile_status(tmp.data(), &status, detail::gxs(stream)), "reduce (quantile): device-side bounds check");
+  double h = 0.0;
+  CUDF_CUDA_TRY(hipMemcpyAsync(&h, value.data(), sizeof(h), hipMemcpyDeviceToHost, stream.value()));
+  bool const valid = detail::read_i64(static_cast<int64_t const*>(cnt.data()), stream) > 0;
+  return host_scalar<double>(output_type, h, valid, stream, mr);
+}
+
 template <typename T>
 std::unique_ptr<scalar> make_result(void const* dev_value, bool valid, rmm::cuda_stream_view stream,
                                     rmm::device_async_resource_ref mr)
@@ -148,6 +178,8 @@ std::unique_ptr<scalar> reduce(column_view const& col, reduce_aggregation const&
     case aggregation::MEAN: return reduce_mean(col, output_type, stream, mr);
     case aggregation::ANY: return reduce_any_all(col, true, output_type, std::nullopt, stream, mr);
     case aggregation::ALL: return reduce_any_all(col, false, output_type, std::nullopt, stream, mr);
+    case aggregation::MEDIAN:
+    case aggregation::QUANTILE: return reduce_quantile(col, agg, output_type, stream, mr);
     default: break;
   }
   int const op = gx_op_of(agg.kind);

@@ -324,6 +324,22 @@ class DataFrame:
     def T(self) -> "DataFrame":
         return self.transpose()
 
+    def quantile(self, q=0.5, interpolation: str = "linear") -> "DataFrame":
+        """pandas' DataFrame.quantile over the numeric columns (bool columns are left out): one FLOAT64 row per quantile -- a scalar q
+        gives one row, where pandas gives a Series over the columns.  Nulls are skipped; a column without a valid row gives nulls."""
+        qs = list(q) if np.ndim(q) else [q]
+        if any(not 0.0 <= float(x) <= 1.0 for x in qs):
+            raise ValueError("percentiles should all be in the interval [0, 1]")
+        out = DataFrame()
+        for name, c in self._cols.items():
+            if c.dtype.kind in "iuf":
+                out._cols[name] = ops.quantile(c, qs, interpolation)
+        return out
+
+    def median(self) -> "DataFrame":
+        """pandas' DataFrame.median over the numeric columns, as one row"""
+        return self.quantile(0.5)
+
     def rolling(self, window: int, min_periods: Optional[int] = None, center: bool = False) -> "Rolling":
         """pandas' DataFrame.rolling(window, min_periods, center) over the rows: .sum() / .min() / .max() / .mean() of every column"""
         return Rolling(self, window, min_periods, center)
@@ -437,7 +453,7 @@ class Rolling:
 
 
 class GroupBy:
-    _SUPPORTED = ("sum", "count", "mean", "min", "max", "var", "std")
+    _SUPPORTED = ("sum", "count", "mean", "min", "max", "var", "std", "median")
 
     def __init__(self, df: DataFrame, by: Union[str, Sequence[str]]):
         self._df, self._by = df, ([by] if isinstance(by, str) else list(by))
@@ -470,8 +486,20 @@ class GroupBy:
     def std(self) -> DataFrame:
         return self._all("std")
 
+    def median(self) -> DataFrame:
+        return self._all("median")
+
+    def quantile(self, q: float = 0.5, interpolation: str = "linear") -> DataFrame:
+        """pandas' GroupBy.quantile for a scalar q: per group and value column, the quantile of the valid values (FLOAT64; null for a
+        group without one)"""
+        if np.ndim(q):
+            raise NotImplementedError("groupby quantile: one quantile per call")
+        if not 0.0 <= float(q) <= 1.0:
+            raise ValueError("percentiles should all be in the interval [0, 1]")
+        return self._all(("quantile", float(q), interpolation))
+
     def agg(self, spec: Dict[str, Union[str, Sequence[str]]], _exact: bool = False) -> DataFrame:
-        """{value column: "sum" | "count" | "mean" | "min" | "max" | "var" | "std" | [..]} -> one row per group, sorted by key
+        """{value column: "sum" | "count" | "mean" | "min" | "max" | "var" | "std" | "median" | [..]} -> one row per group, sorted by key
         (pandas' default sort=True).  Null keys are dropped (dropna=True), null values are skipped."""
         by = self._by
         k0 = self._df[by[0]]
@@ -486,9 +514,9 @@ class GroupBy:
         out = DataFrame()
         first = True
         for name, fns in spec.items():
-            fns = [fns] if isinstance(fns, str) else list(fns)
+            fns = [fns] if isinstance(fns, (str, tuple)) else list(fns)
             for f in fns:
-                if f not in self._SUPPORTED:
+                if f not in self._SUPPORTED and not (isinstance(f, tuple) and f[0] == "quantile"):
                     raise NotImplementedError(f"groupby aggregation {f!r} is not on this path yet")
             k, s, cv, _ = ops.groupby_sum_count(keys, self._df[name])
             order = ops.sorted_order(k)
@@ -519,8 +547,11 @@ class GroupBy:
             if any(f in ("var", "std") for f in fns):  # ddof = 1, groups come back in ascending key order
                 _, var, std, _, _ = ops.groupby_var_std(keys, self._df[name])
             for f in fns:
-                label = name if len(fns) == 1 and len(spec) >= 1 and all(isinstance(v, str) for v in spec.values()) else f"{name}_{f}"
-                if f == "sum":
+                label = name if len(fns) == 1 and len(spec) >= 1 and all(isinstance(v, (str, tuple)) for v in spec.values()) else f"{name}_{f}"
+                if f == "median" or isinstance(f, tuple):  # the sort path: rows ordered by (key, value), one lookup per result
+                    qv, how = (0.5, "linear") if f == "median" else (f[1], f[2])
+                    _, out._cols[label], _ = ops.groupby_quantile(keys, self._df[name], [qv], how)
+                elif f == "sum":
                     out._cols[label] = s
                 elif f == "count":
                     out._cols[label] = cv

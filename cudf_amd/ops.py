@@ -2100,6 +2100,185 @@ def fill(col: Column, begin: int, end: int, value) -> Column:
 
 
 # ------------------------------------------------------------------------------------------------
+# quantiles  (cudf::quantile / quantiles: quantiles.hpp; the MEDIAN / QUANTILE aggregations) -- gx_quantile.hip
+# ------------------------------------------------------------------------------------------------
+QUANTILE_MAX_Q = 64  # quantiles of one gx_quantile / gx_quantile_lookup call
+
+
+def _quantile_args(col: Column, q, interpolation: str, what: str):
+    if col.dtype.kind not in "iuf" or col.dtype.itemsize not in (1, 2, 4, 8) or (col.dtype.kind == "f" and col.dtype.itemsize == 2):
+        raise TypeError(f"{what}: {col.dtype} is not a numeric type")  # cudf::data_type_error
+    qs = [float(x) for x in (list(q) if np.ndim(q) else [q])]
+    if any(x != x for x in qs):
+        raise ValueError(f"{what}: a quantile is NaN")
+    if len(qs) > QUANTILE_MAX_Q:
+        raise ValueError(f"{what}: at most {QUANTILE_MAX_Q} quantiles per call")
+    if interpolation not in L.INTERP:
+        raise ValueError(f"{what}: interpolation must be one of {sorted(L.INTERP)}")
+    return qs, L.INTERP[interpolation]
+
+
+def quantile_index(count: int, q: float):
+    """(lower, higher, nearest, frac) of quantile q over `count` >= 1 rows: the one index rule of the kernels (gx_quantile_index)"""
+    lo, hi, ne = ctypes.c_int64(0), ctypes.c_int64(0), ctypes.c_int64(0)
+    fr = ctypes.c_double(0.0)
+    L.check(_lib.gx_quantile_index(int(count), float(q), ctypes.byref(lo), ctypes.byref(hi), ctypes.byref(ne), ctypes.byref(fr)),
+            "gx_quantile_index")
+    return lo.value, hi.value, ne.value, fr.value
+
+
+def _all_null(dtype, n: int) -> Column:
+    out = Column.empty(dtype, n, nullable=True)
+    out.null_count = n
+    if n == 0:
+        out.mask = None
+    return out
+
+
+def quantile(col: Column, q, interpolation: str = "linear", exact: bool = True, mode: str = "auto", return_info: bool = False):
+    """Quantiles of an UNSORTED column, nulls excluded (what Series.quantile and cudf::reduce MEDIAN / QUANTILE ask for): gx_quantile
+    -- three streaming passes and a sort of the few candidate rows ("select"), or a sort of the valid rows ("sort"); "auto" picks.
+    Returns a Column of len(q) rows: FLOAT64, or with exact=False the column's dtype (linear / midpoint: the double cast to it; else
+    the element itself); every row null when the column has no valid row.  return_info=True: (Column, {"path", "nvalid", "elems"})
+    with elems = the (lower, higher) elements per quantile as a NumPy array of shape (len(q), 2)."""
+    qs, interp = _quantile_args(col, q, interpolation, "quantile")
+    if mode not in L.QUANTILE_MODE:
+        raise ValueError(f"quantile: mode must be one of {sorted(L.QUANTILE_MODE)}")
+    nq = len(qs)
+    out_dt = np.dtype(np.float64) if exact else col.dtype
+    if nq == 0:
+        out = Column.empty(out_dt, 0)
+        return (out, {"path": None, "nvalid": None, "elems": np.zeros((0, 2), col.dtype)}) if return_info else out
+    f64 = Column.empty(np.float64, nq)
+    elems = device_bytes(2 * nq * col.dtype.itemsize)
+    nv = _dev_i64()
+    path = ctypes.c_int(0)
+    qarr = (ctypes.c_double * nq)(*qs)
+    tmp = _run(_lib.gx_quantile, col.gx, col.data_ptr, col.mask_ptr if col.has_nulls() else None, 0, col.size, qarr, nq, interp,
+                    L.QUANTILE_MODE[mode], f64.data_ptr, ptr(elems), ptr(nv), ctypes.byref(path))
+    st = ctypes.c_int(0)
+    if _lib.gx_quantile_status(ptr(tmp), ctypes.byref(st), stream_ptr()) != 0:
+        raise L.GxError(f"gx_quantile: device-side bounds check failed (status {st.value})")
+    nvalid = int(nv.item())
+    e = elems[: 2 * nq * col.dtype.itemsize].cpu().numpy().view(col.dtype).reshape(nq, 2).copy()
+    if nvalid == 0:
+        out = _all_null(out_dt, nq)
+    elif exact:
+        out = f64
+    elif interpolation in ("linear", "midpoint"):
+        out = cast(f64, col.dtype)
+    else:
+        pick = []
+        for j, x in enumerate(qs):
+            lo, _, ne, _ = quantile_index(nvalid, x)
+            pick.append(e[j, 0] if interpolation == "lower" or (interpolation == "nearest" and ne == lo) else e[j, 1])
+        out = Column.from_numpy(np.array(pick, dtype=col.dtype))
+    return (out, {"path": L.QUANTILE_PATH.get(path.value), "nvalid": nvalid, "elems": e}) if return_info else out
+
+
+def _lookup(col: Column, order_ptr, nseg: int, offsets: torch.Tensor, counts_ptr, qs, interp: int, exact: bool) -> Column:
+    nq = len(qs)
+    out = Column.empty(np.float64 if exact else col.dtype, nseg * nq, nullable=True)
+    nulls = _dev_i64()
+    qarr = (ctypes.c_double * nq)(*qs)
+    L.check(_lib.gx_quantile_lookup(col.gx, col.data_ptr, col.mask_ptr if col.has_nulls() else None, 0, order_ptr, nseg, ptr(offsets),
+                                    counts_ptr, qarr, nq, interp, int(exact), out.data_ptr, out.mask_ptr, ptr(nulls), stream_ptr()),
+            "gx_quantile_lookup")
+    return _counted(out, nulls)
+
+
+def quantile_sorted(col: Column, q, interpolation: str = "linear", ordered_indices: Optional[Column] = None, exact: bool = True) -> Column:
+    """cudf::quantile: the quantiles of a column in its EXISTING order, or in the order of `ordered_indices` (an INT32 map of
+    col.size rows) -- nothing is sorted.  count = col.size, nulls included; a result is null when a row it reads is null (both
+    neighbours for linear / midpoint).  An empty column gives len(q) nulls, an empty q an empty column."""
+    qs, interp = _quantile_args(col, q, interpolation, "quantile_sorted")
+    out_dt = np.dtype(np.float64) if exact else col.dtype
+    if ordered_indices is not None and ordered_indices.size == 0 and col.size > 0:
+        ordered_indices = None
+    if ordered_indices is not None and (ordered_indices.dtype != np.int32 or ordered_indices.size != col.size or ordered_indices.has_nulls()):
+        raise ValueError("quantile_sorted: ordered_indices must be an INT32 column of the input's size")  # std::invalid_argument
+    if not qs:
+        return Column.empty(out_dt, 0)
+    if col.size == 0:
+        return _all_null(out_dt, len(qs))
+    offsets = torch.tensor([0, col.size], dtype=torch.int32, device="cuda")
+    return _lookup(col, ordered_indices.data_ptr if ordered_indices is not None else None, 1, offsets, None, qs, interp, exact)
+
+
+def _stable_order(cols: Sequence[Column], ascending: Sequence[bool], null_before: Sequence[bool]) -> Column:
+    order = None
+    for c, a, nb in reversed(list(zip(cols, ascending, null_before))):
+        order = sorted_order(c, a, nb) if order is None else gather(order, sorted_order(gather(c, order), a, nb))
+    return order
+
+
+def quantiles(cols: Sequence[Column], q, interpolation: str = "nearest", is_sorted: bool = False, ascending=True,
+              null_before=True) -> List[Column]:
+    """cudf::quantiles: whole ROWS of a table at the quantiles of its lexicographic order (sorted here unless is_sorted).  The
+    interpolation must pick a row: "lower", "higher" or "nearest"."""
+    cols = list(cols)
+    if not cols:
+        raise ValueError("quantiles: no columns")
+    if interpolation in ("linear", "midpoint"):
+        raise ValueError("quantiles: the interpolation must be non-arithmetic (lower, higher or nearest)")
+    if interpolation not in L.INTERP:
+        raise ValueError(f"quantiles: interpolation must be one of {sorted(L.INTERP)}")
+    n = cols[0].size
+    if any(c.size != n for c in cols):
+        raise ValueError("quantiles: columns of different lengths")
+    if n == 0:
+        raise ValueError("quantiles: the table has no rows")
+    qs = [float(x) for x in (list(q) if np.ndim(q) else [q])]
+    if any(x != x for x in qs):
+        raise ValueError("quantiles: a quantile is NaN")
+    idx = np.array([dict(zip(("lower", "higher", "nearest"), quantile_index(n, x)[:3]))[interpolation] for x in qs], dtype=np.int32)
+    gmap = Column.from_numpy(idx)
+    if not is_sorted:
+        asc, nb = _per_key(ascending, len(cols), "ascending"), _per_key(null_before, len(cols), "null_before")
+        gmap = gather(_stable_order(cols, asc, nb), gmap)
+    return [gather(c, gmap) for c in cols]
+
+
+def groupby_quantile(keys: Column, values: Column, q, interpolation: str = "linear"):
+    """groupby QUANTILE (MEDIAN = q 0.5, linear) of one values column by one key column: the rows ordered by (key, value) with null
+    values behind their group's valid ones (two stable argsorts), the group offsets, the valid count per group, then
+    gx_quantile_lookup: FLOAT64, len(q) results per group, group-major, null for a group without a valid value.
+    Returns (group keys in ascending order -- rows with a null key are dropped --, results, number of groups)."""
+    qs, interp = _quantile_args(values, q, interpolation, "groupby_quantile")
+    if keys.size != values.size:
+        raise RuntimeError("Size mismatch between request values and groupby keys.")
+    if not qs:
+        raise ValueError("groupby_quantile: no quantiles")
+    n = keys.size
+    if n == 0:
+        return Column.empty(keys.dtype, 0), Column.empty(np.float64, 0), 0
+    o1 = sorted_order(values, True, False)
+    order = gather(o1, sorted_order(gather(keys, o1), True, False))
+    ks, vs = gather(keys, order), gather(values, order)
+    heads = torch.empty(n, dtype=torch.uint8, device="cuda")
+    L.check(_lib.gx_group_heads(ks.gx, ks.data_ptr, ks.mask_ptr if ks.has_nulls() else None, None, n, 0, ptr(heads), stream_ptr()),
+            "gx_group_heads")
+    labels = torch.empty(n, dtype=torch.int32, device="cuda")
+    offsets = torch.empty(n + 1, dtype=torch.int32, device="cuda")
+    ng = _dev_i64()
+    _run(_lib.gx_group_offsets, ptr(heads), n, ptr(labels), ptr(offsets), None, ptr(ng))
+    g = int(ng.item())
+    counts = None
+    if vs.has_nulls():
+        counts = torch.zeros(g, dtype=torch.int32, device="cuda")
+        _run(_lib.gx_segmented_reduce, vs.gx, vs.data_ptr, vs.mask_ptr, ptr(heads), ptr(labels), n, L.OP_COUNT_VALID, None, ptr(counts))
+    if ks.has_nulls():
+        g -= 1  # nulls sort behind every key: their group is the last one
+    if g == 0:
+        return Column.empty(keys.dtype, 0), Column.empty(np.float64, 0), 0
+    res = _lookup(vs, None, g, offsets, ptr(counts), qs, interp, True)
+    starts = Column(offsets[:g].contiguous().view(torch.uint8), np.int32, g)
+    gk = gather(ks, starts)
+    gk.mask, gk.null_count = None, 0
+    return gk, res, g
+
+
+# ------------------------------------------------------------------------------------------------
 # synthetic data / checks (bench + tests)
 # ------------------------------------------------------------------------------------------------
 

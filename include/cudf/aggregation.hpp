@@ -1,7 +1,8 @@
 // cudf/aggregation.hpp -- aggregation descriptors and their factories
 // (reference: cpp/include/cudf/aggregation.hpp:73-330).  The Kind enumerators keep the reference's
 // order so integer values stay interchangeable; the hot path implements SUM, PRODUCT, MIN, MAX, COUNT_VALID,
-// COUNT_ALL, MEAN, ANY and ALL (cudf::reduce), SUM_OF_SQUARES, M2, VARIANCE, STD, ARGMIN, ARGMAX and (sort path) NTH_ELEMENT; others throw
+// COUNT_ALL, MEAN, ANY and ALL (cudf::reduce), SUM_OF_SQUARES, M2, VARIANCE, STD, ARGMIN, ARGMAX and (sort path) NTH_ELEMENT, MEDIAN,
+// QUANTILE (cudf::reduce and the groupby sort path); others throw
 // cudf::logic_error where they are used.
 // cudf::rolling_window / grouped_rolling_window (rolling.hpp) take SUM, MIN, MAX, MEAN, COUNT_VALID and COUNT_ALL through
 // rolling_aggregation; every other kind made for that base throws cudf::logic_error there.
@@ -9,7 +10,9 @@
 #include <cudf/types.hpp>
 #include <cudf/utilities/error.hpp>
 
+#include <functional>
 #include <memory>
+#include <vector>
 
 namespace cudf {
 
@@ -92,6 +95,42 @@ class nth_element_aggregation final : public groupby_aggregation, public reduce_
     return std::unique_ptr<aggregation>(static_cast<groupby_aggregation*>(new nth_element_aggregation(_n, _null_handling)));
   }
 };
+// MEDIAN / QUANTILE carry the quantiles and the interpolation (reference: detail/aggregation/aggregation.hpp quantile_aggregation,
+// _quantiles / _interpolation); MEDIAN is QUANTILE {0.5} LINEAR under its own kind
+class quantile_aggregation final : public groupby_aggregation, public reduce_aggregation {
+ public:
+  quantile_aggregation(aggregation::Kind k, std::vector<double> const& quantiles, interpolation interp)
+    : aggregation(k), _quantiles{quantiles}, _interpolation{interp}
+  {
+  }
+  std::vector<double> _quantiles;
+  interpolation _interpolation;
+  [[nodiscard]] bool is_equal(aggregation const& other) const override
+  {
+    auto const* o = dynamic_cast<quantile_aggregation const*>(&other);
+    return o != nullptr && o->kind == kind && o->_interpolation == _interpolation && o->_quantiles == _quantiles;
+  }
+  [[nodiscard]] std::size_t do_hash() const override
+  {
+    std::size_t h = static_cast<std::size_t>(kind) * 31u + static_cast<std::size_t>(_interpolation);
+    for (double q : _quantiles) h = h * 1000003u ^ std::hash<double>{}(q);
+    return h;
+  }
+  [[nodiscard]] std::unique_ptr<aggregation> clone() const override
+  {
+    return std::unique_ptr<aggregation>(static_cast<groupby_aggregation*>(new quantile_aggregation(kind, _quantiles, _interpolation)));
+  }
+};
+template <typename Base>
+std::unique_ptr<Base> make_quantile(aggregation::Kind k, std::vector<double> const& q, interpolation interp)
+{
+  return std::unique_ptr<Base>(static_cast<Base*>(new quantile_aggregation(k, q, interp)));
+}
+template <>
+inline std::unique_ptr<aggregation> make_quantile<aggregation>(aggregation::Kind k, std::vector<double> const& q, interpolation interp)
+{
+  return std::unique_ptr<aggregation>(static_cast<groupby_aggregation*>(new quantile_aggregation(k, q, interp)));
+}
 
 template <typename Base>
 std::unique_ptr<Base> make_std_var(aggregation::Kind k, size_type ddof)
@@ -155,6 +194,14 @@ template <>
 inline std::unique_ptr<aggregation> make_nth_element_aggregation<aggregation>(size_type n, null_policy null_handling)
 {
   return std::unique_ptr<aggregation>(static_cast<groupby_aggregation*>(new detail::nth_element_aggregation(n, null_handling)));
+}
+// MEDIAN and QUANTILE of the valid values (aggregation.hpp, make_median_aggregation / make_quantile_aggregation): FLOAT64 results
+template <typename Base = aggregation>
+std::unique_ptr<Base> make_median_aggregation() { return detail::make_quantile<Base>(aggregation::MEDIAN, {0.5}, interpolation::LINEAR); }
+template <typename Base = aggregation>
+std::unique_ptr<Base> make_quantile_aggregation(std::vector<double> const& quantiles, interpolation interp = interpolation::LINEAR)
+{
+  return detail::make_quantile<Base>(aggregation::QUANTILE, quantiles, interp);
 }
 // ARGMAX / ARGMIN: row index (size_type) of the group's maximum / minimum (aggregation.hpp:430-446)
 template <typename Base = aggregation>

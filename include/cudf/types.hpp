@@ -21,6 +21,8 @@ enum class null_order : bool { AFTER, BEFORE };
 enum class sorted : bool { NO, YES };
 enum class mask_state : int32_t { UNALLOCATED, UNINITIALIZED, ALL_VALID, ALL_NULL };
 enum class scan_type : bool { INCLUSIVE, EXCLUSIVE };
+// how a quantile between two rows is taken (reference: types.hpp, interpolation); the values of gx_interp
+enum class interpolation : int32_t { LINEAR, LOWER, HIGHER, MIDPOINT, NEAREST };
 
 struct order_info {
   sorted is_sorted;

@@ -589,6 +589,53 @@ int gx_fill_range(int elem_size, void* data, int64_t begin, int64_t end, const v
 int gx_sequence(int dtype, void* out, int64_t n, const void* init_dev, const void* step_dev, gx_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Quantiles (cudf_amd/csrc/gx_quantile.hip).  Replace the kernels behind cudf::quantile / quantiles (cpp/src/quantiles/quantile.cu,
+ * quantiles.cu), the MEDIAN / QUANTILE reductions (cpp/src/reductions/quantile.cu) and the groupby aggregations of the same name
+ * (cpp/src/groupby/sort/group_quantiles.cu).  The index and interpolation rules (pos = q * (count - 1); lower / higher / nearest;
+ * LINEAR and MIDPOINT without fused multiply-add) are stated once, in the header comment of gx_quantile.hip; gx_interp has the values
+ * of cudf::interpolation.  The order is that of the sorts (NaN greatest, -0.0 == +0.0, ties in input order); the ten numeric dtypes
+ * are taken, GX_BOOL8 is GX_EDTYPE.  1 <= nq <= 64; q_host is a HOST array, each q clamped to [0, 1], a NaN is GX_EINVAL.
+ * gx_quantile: order statistics of an UNSORTED column, nulls (bitmap read from valid_begin_bit on; NULL = none) excluded.
+ *   out_f64_dev[nq] = the interpolated results; out_elems_dev[2 * nq] (optional) = the elements at `lower` and `higher` of every q in
+ *   the column's own dtype, the very bytes of gx_sort_keys(valid rows)[rank]; *nvalid_dev (device int64) = valid rows: when it is 0
+ *   the outputs are unspecified and the caller makes the result null.  n in [0, 2^31).
+ *   mode (gx_quantile_mode): FORCE_SELECT = three streaming passes (range, 2048-bin histogram on the top 11 bits of the span, collect
+ *   of the rows in the wanted bins) + a sort of the candidates only; FORCE_SORT = valid rows compacted, gx_sort_keys, ranks read;
+ *   AUTO = SORT when n < min_rows, else the plan of the select path decides: SORT when candidates > max_share * n
+ *   (gx_quantile_set_thresholds, gx_knobs.h), else SELECT.  *path_host (optional, host) = what ran (gx_quantile_path): SELECT_DIRECT when
+ *   the span is below 2048 (a bin is a value; also one distinct value, and no valid row on the select side): no collect pass.
+ *   HOST ROUND TRIP: the call reads the plan's head (valid count, candidate count, shift) back once and waits for `stream` there --
+ *   except FORCE_SORT / AUTO below min_rows without a bitmap, which wait for nothing.  cub-style scratch query (tmp == NULL); the
+ *   scratch holds a candidate / compaction buffer and a sorted copy of n elements each beside the sort's own scratch.
+ *   GX_EINVAL: n outside [0, 2^31), nq outside [1, 64], NULL q_host / tmp_bytes, a NaN q, unknown interp / mode, a negative begin
+ *   bit; with tmp: NULL out_f64_dev / nvalid_dev, NULL data with rows; GX_ETMP.  All before anything touches the device.
+ * gx_quantile_status: the status word of the last gx_quantile on `tmp` (0 = ok; a non-zero word -- an index of the collect pass or
+ *   of the rank read-out met its bound, nothing was written out of bounds -- also returns GX_EINTERNAL).  Synchronises `stream`.
+ * gx_quantile_tile_rows (host): rows one workgroup handles per trip of the streaming passes.
+ * gx_quantile_index (host): the shared index helper: lower / higher / nearest / frac for `count` >= 1 rows.
+ * gx_quantile_lookup: quantiles of data whose order is KNOWN: out[s * nq + j] for segment s = rows [offsets[s], offsets[s + 1]) of
+ *   `order` (int32 map, NULL = the rows themselves), count = seg_counts_dev[s] (NULL = the segment's size): the rows in front of the
+ *   segment that take part (groupby: the valid ones, sorted with nulls after).  A whole column is nseg = 1, offsets {0, n}.
+ *   exact != 0: out is FLOAT64; else the input dtype (LINEAR / MIDPOINT: static_cast of the double; otherwise the element's bits).
+ *   An output is valid when the rows it reads are valid (both neighbours for LINEAR / MIDPOINT, the one row otherwise) and its
+ *   count is not 0.  out_valid (optional): (nseg * nq + 31) / 32 words, every one written; *out_null_count_dev (optional).
+ *   One thread per output, no scratch.  GX_EINVAL: nseg < 0, nseg * nq >= 2^31, nq outside [1, 64], NULL q_host, NaN q, unknown
+ *   interp, negative begin bit, NULL offsets_dev / out with segments.
+ * ------------------------------------------------------------------------------------------ */
+enum gx_interp { GX_INTERP_LINEAR = 0, GX_INTERP_LOWER = 1, GX_INTERP_HIGHER = 2, GX_INTERP_MIDPOINT = 3, GX_INTERP_NEAREST = 4 };
+enum gx_quantile_mode { GX_QUANTILE_AUTO = 0, GX_QUANTILE_FORCE_SELECT = 1, GX_QUANTILE_FORCE_SORT = 2 };
+enum gx_quantile_path { GX_QUANTILE_PATH_SELECT = 1, GX_QUANTILE_PATH_SELECT_DIRECT = 2, GX_QUANTILE_PATH_SORT = 3 };
+int gx_quantile_tile_rows(void);
+int gx_quantile_index(int64_t count, double q, int64_t* lower, int64_t* higher, int64_t* nearest, double* frac);
+int gx_quantile(int dtype, const void* data, const uint32_t* valid, int64_t valid_begin_bit, int64_t n, const double* q_host, int nq,
+                int interp, int mode, double* out_f64_dev, void* out_elems_dev, int64_t* nvalid_dev, int* path_host, void* tmp,
+                size_t* tmp_bytes, gx_stream_t stream);
+int gx_quantile_status(const void* tmp, int* status_host, gx_stream_t stream);
+int gx_quantile_lookup(int dtype, const void* data, const uint32_t* valid, int64_t begin_bit, const int32_t* order, int64_t nseg,
+                       const int32_t* offsets_dev, const int32_t* seg_counts_dev, const double* q_host, int nq, int interp, int exact,
+                       void* out, uint32_t* out_valid, int64_t* out_null_count_dev, gx_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * Hashing / partitioning.
  * gx_murmur3_32: cudf::hashing::detail::MurmurHash3_x86_32<T>
  * (include/cudf/hashing/detail/murmurhash3_x86_32.cuh:22-67), null -> UINT32_MAX, and the

@@ -227,6 +227,13 @@ void gx_rolling_set_kernel(int which);
  * slots of OTHER classes at small sizes. */
 void gx_distinct_set_hash_bits(int bits);
 
+/* Knobs (per calling thread) of gx_quantile in GX_QUANTILE_AUTO: below min_rows rows the sort path runs without a look at the column;
+ * from there on the select path's plan runs and the sort path takes over when the candidate count exceeds max_share * n.  A negative
+ * min_rows or a max_share outside [0, 1] restores that default (2^20 rows, 1/2: DESIGN.md 3.5i, the measured table).  Tests read the
+ * values back to predict the path. */
+void gx_quantile_set_thresholds(int64_t min_rows, double max_share);
+void gx_quantile_get_thresholds(int64_t* min_rows, double* max_share);
+
 #ifdef __cplusplus
 }
 #endif
