@@ -3838,13 +3838,35 @@ static HybridCfg hybrid_cfg(int64_t n, bool iota_payload, int algo)
   return c;
 }
 
-// cursor path (integer keys, keys only): configuration, again a pure function of (n, kind, knobs)
-struct FastCfg {
-  bool on;
+// cursor path (integer keys, keys only): configuration, again a pure function of (n, margin) -- the single-GPU sort (fast_cfg:
+// the margin is a knob) and the sharded sort (SORTX_MARGIN) size their level-0 slots and their cells by it
+struct CursorCfg {
   int bits2;         // level-1 bits (1..10), 8192-key cells
   int bits2_max;     // ... or one more, decided on the device from the exact level-0 histogram (k_hf_plan stage 2)
   int stride;        // sample: every stride-th 64-key chunk
   size_t slot_rows;  // keys the padded level-0 output holds
+};
+static inline CursorCfg cursor_cfg(int64_t n, double margin)
+{
+  CursorCfg f{};
+  int B = 9;
+  while (B < 18 && (double)n / (double)(1ull << B) > 0.955 * 8192.0) ++B;
+  f.bits2     = B - 8;
+  f.bits2_max = f.bits2 < 10 ? f.bits2 + 1 : 10;
+  f.stride    = n >= (1ll << 27) ? 32 : 8;
+  // sum of the slot capacities k_hf_plan hands out (Cauchy-Schwarz over the 2048 slots; the kernel checks it again)
+  const double m   = margin > 0 ? margin : 0.0;
+  const double dev = m * 1.25 * f.stride * __builtin_sqrt((double)(NRANGE * BINS) * ((double)n / f.stride + 2.0 * NRANGE * BINS));
+  f.slot_rows      = (size_t)((double)n * 1.002 + dev) + (size_t)(NRANGE * BINS) * (size_t)(2 * f.stride * HF_CHUNK + 64 + 16) + 65536;
+  return f;
+}
+// cell buffer of the cursor path: per-bucket slots (HybridPlan::ccap) -- n keys, 1/16 for the neighbour smoothing, the slack per cell
+static inline size_t cursor_cell_rows(int64_t n, int bits2_max)
+{
+  return (size_t)n + (size_t)n / 16 + ((size_t)BINS << bits2_max) * cell_slack(1 << 13) + 65536;
+}
+struct FastCfg : CursorCfg {
+  bool on;
 };
 static thread_local int g_soft_fault      = 0;     // 1: an abandoned look-back wait is REPORTED through the status word (the caller reads it); 0: it traps
 static thread_local int g_spin_ms         = 0;     // look-back wait limit in ms (0: SPIN_SECONDS); tests shorten it
@@ -3858,71 +3880,183 @@ static thread_local float g_cursor_margin = 8.0f;  // standard deviations of sla
 template <typename KeyT, int KIND, bool HAS_VAL>
 static FastCfg fast_cfg(int64_t n, int algo, bool hybrid_on)
 {
-  FastCfg f{false, 9, 9, 32, 0};
+  FastCfg f{{9, 9, 32, 0}, false};
   // 64-bit keys: wherever the hybrid path applies; 32-bit integer keys (round 3): the same two partition levels, the cells sorted
   // by k_local_place on 32-bit words, the LSD passes as the only fallback
   // (round 5) float64 keys only: the cursor path runs on the total-order flip (K_FTOTAL) and verifies on every key that the column holds
   // no NaN and no -0.0 -- the values on which an unordered sort and the reference's stable one could differ; else the look-back path
   if ((sizeof(KeyT) != 8 && sizeof(KeyT) != 4) || HAS_VAL || (KIND == K_FLOAT && (sizeof(KeyT) != 8 || !g_float_cursor)) || algo != 0 || !g_cursor || n < (1ll << 25)) return f;
   if (sizeof(KeyT) == 8 ? !hybrid_on : !g_hybrid) return f;
-  int B = 9;
-  while (B < 18 && (double)n / (double)(1ull << B) > 0.955 * 8192.0) ++B;
-  if ((double)n / (double)(1ull << B) > 0.97 * 8192.0) return f;
-  f.bits2  = B - 8;
-  f.bits2_max = f.bits2 < 10 ? f.bits2 + 1 : 10;
-  f.stride = n >= (1ll << 27) ? 32 : 8;
-  // sum of the slot capacities k_hf_plan hands out (Cauchy-Schwarz over the 2048 slots; the kernel checks it again)
-  const double m   = g_cursor_margin > 0 ? g_cursor_margin : 0.0;
-  const double dev = m * 1.25 * f.stride * __builtin_sqrt((double)(NRANGE * BINS) * ((double)n / f.stride + 2.0 * NRANGE * BINS));
-  f.slot_rows      = (size_t)((double)n * 1.002 + dev) + (size_t)(NRANGE * BINS) * (size_t)(2 * f.stride * HF_CHUNK + 64 + 16) + 65536;
-  f.on             = true;
+  const CursorCfg c = cursor_cfg(n, g_cursor_margin);
+  if ((double)n / (double)(1ull << (8 + c.bits2)) > 0.97 * 8192.0) return f;  // more than 2^18 cells of 8192 keys
+  static_cast<CursorCfg&>(f) = c;
+  f.on = true;
   return f;
+}
+
+// ---- launch shapes that the single-GPU sort and the halves of the sharded sort share
+constexpr int MIN_SHIFT2 = 8;  // key bits that must be left below level 1 (k_local_sort's sub-bucket split takes 7 + 1)
+template <typename KeyT>
+constexpr int hf_tile() { return BT * hf_kpt<KeyT>(); }  // k_hf_scatter's tile
+template <typename KeyT>
+static inline size_t hf_scatter_lds(int nb) { return (size_t)hf_tile<KeyT>() * sizeof(KeyT) + (size_t)(3 * nb + 16 + 4) * 4 + (size_t)2 * NW * 8; }
+static inline size_t local_sort_lds(size_t word_bytes, int cl2) { return (word_bytes << cl2) + (size_t)(((1 << cl2) / 16 / GX_WAVE) * BINS + 32 + 2 * BINS) * 4; }
+struct SampleGrid {
+  int64_t ftiles;    // tiles of k_hf_scatter
+  int64_t frange;    // rows per input range (whole tiles; the last range takes the rest)
+  unsigned sblocks;  // workgroups of k_hf_sample
+};
+template <typename KeyT>
+static inline SampleGrid sample_grid(int64_t n, int stride)
+{
+  const int64_t ftiles  = div_up(n, (int64_t)hf_tile<KeyT>());
+  const int64_t sblocks = div_up(div_up(n, (int64_t)stride * HF_CHUNK), (int64_t)4 * 4);
+  return {ftiles, (ftiles / NRANGE) * hf_tile<KeyT>(), (unsigned)(sblocks > 2048 ? 2048 : sblocks)};
+}
+
+// ---- scratch.  What the cell stages of both sorts see of it; SortLayout (one GPU) and SortxLayout (sharded) carve these among
+// their other arrays
+constexpr size_t CELL_TABLE_BYTES = (size_t)4 * BINS * NB2MAX * sizeof(uint32_t);  // what starts at zero: hist2 .. the rescue cursors
+template <typename KeyT>
+struct CellScratch {
+  SortPlan* plan;
+  uint32_t* hist2;             // cell sizes | base2 | xoff | rescue cursors, one take
+  uint32_t* base2;             // cell output positions
+  uint32_t* xoff;              // (cursor path: big cells) first key in X
+  uint32_t* todo;              // cells k_local_place leaves to k_local_sort
+  uint32_t* biglist;           // cursor path, big cells: (cell, first key in X)
+  unsigned long long* status;  // look-back status words
+  size_t status_words;
+  KeyT* cells;                 // level-1 output = the cell buffer; X (the keys of the big cells) afterwards
+  KeyT* level0;                // cursor path: padded level-0 output; its halves hold X between the LSD passes
+  size_t level0_rows;
+};
+template <typename KeyT>
+static inline void carve_cell_tables(Carver& c, CellScratch<KeyT>& s, bool cells, bool big)
+{
+  if (cells) {
+    s.hist2 = c.take<uint32_t>((size_t)4 * BINS * NB2MAX);
+    s.base2 = s.hist2 ? s.hist2 + BINS * NB2MAX : nullptr;
+    s.xoff  = s.hist2 ? s.hist2 + 2 * BINS * NB2MAX : nullptr;
+    s.todo  = c.take<uint32_t>((size_t)BINS * NB2MAX);
+  }
+  if (big) s.biglist = c.take<uint32_t>((size_t)2 * BIG_LIST);
+}
+
+// ---- cursor path, level 1 and the cells: the stage behind level 0 on one GPU and behind the exchange in the sharded sort.
+// l1_tiles: one per tile of keys + one tail per slot / region.  cfg: bits2, bits2_max of n.  single_gpu: what only the one-GPU
+// sort has -- level 1's second output (the hint), the ablation bits, the fill of splitter mode's narrow buckets (no-op unless
+// that mode ran), the profile's events
+template <typename KeyT, int CK>
+static int cursor_cells(const Device& dev, hipStream_t stream, const CellScratch<KeyT>& s, const CursorCfg& cfg, int64_t n, int64_t l1_tiles, KeyT* out, KeyT desc_mask,
+                        bool single_gpu)
+{
+  constexpr int WORD_BYTES = (int)sizeof(typename PlaceWord<KeyT, CK, false>::type);
+  constexpr int LS_BT      = (1 << 13) / 16;
+  KeyT* hint_out           = single_gpu ? out : nullptr;
+  const int exp            = single_gpu ? g_exp : 0;
+  const KeyT* level0       = s.level0;
+  typedef void (*HfK)(const KeyT*, KeyT*, KeyT, SortPlan*, uint32_t*, uint32_t, int64_t, KeyT*, uint32_t);
+  // (the level-1 kernel and the cell grids are sized for bits2_max: the device may take the extra bit)
+  HfK kf1 = cfg.bits2_max <= 8 ? (HfK)k_hf_scatter<KeyT, CK, 1, 8> : (cfg.bits2_max == 9 ? (HfK)k_hf_scatter<KeyT, CK, 1, 9> : (HfK)k_hf_scatter<KeyT, CK, 1, 10>);
+  HfK kf2 = cfg.bits2_max <= 8 ? (HfK)k_hf_scatter<KeyT, CK, 2, 8> : (cfg.bits2_max == 9 ? (HfK)k_hf_scatter<KeyT, CK, 2, 9> : (HfK)k_hf_scatter<KeyT, CK, 2, 10>);
+  const size_t lds_hf = hf_scatter_lds<KeyT>(cfg.bits2_max <= 8 ? 256 : (1 << cfg.bits2_max));
+  GX_HIP_TRY(launch_lds(dev, kf1, dim3((unsigned)l1_tiles), dim3(BT), lds_hf, stream, level0, s.cells, desc_mask, s.plan, s.hist2, 1u << 13, n, hint_out, 0u));
+  if (single_gpu) prof_mark_h(2, stream);
+  hipLaunchKernelGGL(k_plan2, dim3(BINS), dim3(GX_WAVE), 0, stream, s.plan, s.hist2, s.base2, (int)sizeof(KeyT), 1);
+  if (single_gpu) prof_mark_h(3, stream);
+  if constexpr (sizeof(KeyT) == 8) {
+    if (single_gpu && g_split)
+      hipLaunchKernelGGL((k_sp_fill<CK>), dim3(BINS, SP_FILL_Y), dim3(256), 0, stream, out, (uint64_t)desc_mask, (const SortPlan*)s.plan, (const uint32_t*)s.base2);
+  }
+  // (one workgroup per cell of the plan n suggests; when the device took the extra level-1 bit each of them walks two cells)
+  GX_HIP_TRY(launch_lds(dev, (k_local_place<KeyT, CK, false, 13>), dim3(local_place_grid(BINS << cfg.bits2)), dim3(LS_BT), place_lds_bytes(13, WORD_BYTES), stream,
+                        (const KeyT*)s.cells, out, (const uint32_t*)nullptr, (uint32_t*)nullptr, desc_mask, s.plan, s.hist2, s.base2, s.todo, exp, 1));
+  // the cells k_local_place left: 64-bit words (32-bit keys are widened to their sortable form on the way in)
+  GX_HIP_TRY(launch_lds(dev, (k_local_sort<uint64_t, CK, false, 13, KeyT>), dim3(local_sort_grid(BINS << cfg.bits2_max)), dim3(LS_BT), local_sort_lds(8, 13), stream,
+                        (const KeyT*)s.cells, out, (const uint32_t*)nullptr, (uint32_t*)nullptr, (uint64_t)desc_mask, s.plan, s.hist2, s.base2, exp, 1, (const uint32_t*)s.todo));
+  if (single_gpu) prof_mark_h(4, stream);
+  if (single_gpu) g_prof.hybrid_marked = g_prof.enabled;
+  // big cells (a hot value): plan X (at most half the level-0 buffer), fetch their keys again from the level-1 input into X = the
+  // cell buffer (every other cell has left it by now); the LSD passes then sort X between the two halves of the level-0 buffer
+  hipLaunchKernelGGL(k_big_plan, dim3(1), dim3(BINS), 0, stream, s.plan, (unsigned long long)(s.level0_rows / 2));
+  hipLaunchKernelGGL(k_big_cells, dim3(BINS), dim3(GX_WAVE), 0, stream, (const SortPlan*)s.plan, (const uint32_t*)s.hist2, s.xoff, s.biglist);
+  GX_HIP_TRY(launch_lds(dev, kf2, dim3(role_grid(dev, Role::fallback, l1_tiles)), dim3(BT), lds_hf, stream, level0, s.cells, desc_mask, s.plan, s.hist2, 1u << 13, n,
+                        hint_out, (uint32_t)l1_tiles));
+  hipLaunchKernelGGL(k_hf_clear_status, dim3(2048), dim3(256), 0, stream, s.plan, reinterpret_cast<uint4*>(s.status), s.status_words / 2);
+  return 0;
+}
+
+// ---- LSD path, behind its plan (k_hist_all, k_plan): the passes over PassArgs' buffers, the copy of the result to its place and,
+// behind a cursor path (s.level0), sorted X dealt to the big cells' places in big_out.  algo 0: look-back passes, 1: three
+// kernels per pass (`partials` is the scan's scratch), 2: look-back passes, one predecessor per round; cells: a cell path ran
+// ahead, the passes may sort X only (their MULTI form); grid_tiles: tiles the pass grids cover; marks: record the profile's events
+template <typename KeyT, int KIND, bool HAS_VAL>
+static int lsd_passes(const Device& dev, hipStream_t stream, const CellScratch<KeyT>& s, PassArgs a, int algo, bool cells, int64_t grid_tiles, unsigned finalize_grid,
+                      uint32_t* partials, KeyT* big_out, bool marks)
+{
+  constexpr int KPT    = kpt_for<KeyT>(HAS_VAL);
+  constexpr size_t lds = pass_lds_bytes<KeyT, HAS_VAL, KPT>();
+  auto kern_lb         = (algo == 2) ? k_radix_pass<KeyT, KIND, HAS_VAL, KPT, 1>
+                                     : (cells ? k_radix_pass<KeyT, KIND, HAS_VAL, KPT, 4, true> : k_radix_pass<KeyT, KIND, HAS_VAL, KPT, 4>);
+  auto kern_pre        = k_radix_pass<KeyT, KIND, HAS_VAL, KPT, 0>;
+  uint32_t* tile_hist  = const_cast<uint32_t*>(a.tile_off);
+  for (int pass = 0; pass < (int)sizeof(KeyT); ++pass) {
+    a.pass = pass;
+    if (marks) prof_mark(2 + 2 * pass, stream);
+    if (algo != 1) {
+      const int64_t lb_grid = (cells && algo != 2) ? div_up(grid_tiles, (int64_t)PASS_TPB) : grid_tiles;
+      GX_HIP_TRY(launch_lds(dev, kern_lb, dim3((unsigned)lb_grid), dim3(BT), lds, stream, a));
+    } else {
+      hipLaunchKernelGGL((k_tile_hist<KeyT, KIND, KPT>), dim3((unsigned)grid_tiles), dim3(BT), 0, stream, a, tile_hist);
+      scan::PlainLoader<uint32_t, uint32_t> ld{tile_hist, nullptr, 0u};
+      int rc = scan::device_scan<uint32_t, uint32_t>(ld, grid_tiles * BINS, 0u, SumOp(), false, tile_hist, partials,
+                                                     stream, &a.plan->pass_skip[pass]);
+      if (rc) return rc;
+      GX_HIP_TRY(launch_lds(dev, kern_pre, dim3((unsigned)grid_tiles), dim3(BT), lds, stream, a));
+    }
+    if (marks) prof_mark(3 + 2 * pass, stream);
+  }
+  hipLaunchKernelGGL((k_finalize_copy<KeyT, HAS_VAL>), dim3(finalize_grid), dim3(256), 0, stream, a);
+  if (s.level0)
+    hipLaunchKernelGGL((k_big_distribute<KeyT>), dim3(2048), dim3(256), 0, stream, a.plan, (const KeyT*)s.level0, big_out, (const uint32_t*)s.biglist, (const uint32_t*)s.base2);
+  return 0;
 }
 
 template <typename KeyT, int KIND, bool HAS_VAL>
 int sort_impl(const void* keys_in, void* keys_out, const int32_t* vals_in, int32_t* vals_out, int64_t n,
               int descending, bool radix_nan_rule, void* tmp, size_t* tmp_bytes, hipStream_t stream)
 {
-  constexpr int KPT   = kpt_for<KeyT>(HAS_VAL);
-  constexpr int TILE  = BT * KPT;
+  constexpr int TILE  = BT * kpt_for<KeyT>(HAS_VAL);
   constexpr int NPASS = sizeof(KeyT);
   if (n < 0 || tmp_bytes == nullptr) return GX_EINVAL;
   if (n > 0x7FFFFFFFll) return GX_EINVAL;  // offsets are 32-bit: cudf::size_type rows (types.hpp:76)
-  const int64_t ntiles = n > 0 ? div_up(n, TILE) : 0;
-  const int algo       = g_algorithm;
-
-  Carver c(tmp);
-  SortPlan* plan             = c.take<SortPlan>(1);
-  unsigned long long* status = nullptr;
-  uint32_t* tile_hist        = nullptr;
-  uint32_t* partials         = nullptr;
+  const int algo = g_algorithm;
   // hybrid MSD path: 64-bit keys; pairs only with the iota payload (sorted_order), whose value is the
   // tie-break the packed local sort relies on
   HybridCfg hc     = hybrid_cfg<KeyT, KIND, HAS_VAL>(n, vals_in == nullptr, algo);
   const FastCfg fc = fast_cfg<KeyT, KIND, HAS_VAL>(n, algo, hc.on);
-  // cell buffer of the cursor path: per-bucket slots (HybridPlan::ccap) -- n keys, 1/16 for the neighbour smoothing, the slack per cell
-  const size_t fc_cells = fc.on ? (size_t)n + (size_t)n / 16 + ((size_t)BINS << fc.bits2_max) * cell_slack(1 << 13) + 65536 : 0;
   // the look-back path is the cursor path's first fallback (a sample that was not representative).  Up to 2^17 cells of 8192 keys
   // (n <= 1.03e9) its FIXED cell slots are about the size of that buffer; above, it would switch to 16384-key slots (17.2 GB for
   // 1.25e9 keys of 10 GB): there the LSD passes are the fallback, as for 32-bit keys, and the scratch stays proportional to n
+  const size_t fc_cells = fc.on ? cursor_cell_rows(n, fc.bits2_max) : 0;
   if (fc.on && hc.on && hc.cl2 == 14 && (((size_t)BINS << hc.bits2) << 14) > fc_cells + (size_t)n / 4) hc.on = false;
-  const bool try_hybrid = hc.on;
-  const int hyb_kpt     = hc.kpt;
-  const int nb1         = hc.bits2 > 8 ? NB9 : BINS;  // bins (and look-back granules per tile) of the level-1 pass
+  // the scratch, in the order it is carved (*tmp_bytes and the plan at offset 0 are part of the ABI; tests/test_sort_scratch_host.py)
+  const bool cells = hc.on || fc.on;  // (the cursor path of 32-bit keys runs without the look-back hybrid)
+  Carver c(tmp);
+  CellScratch<KeyT> S{};
+  S.plan          = c.take<SortPlan>(1);
   uint32_t* base1 = c.take<uint32_t>((size_t)NRANGE * NB2MAX);
-  const bool cells = try_hybrid || fc.on;  // (the cursor path of 32-bit keys runs without the look-back hybrid)
-  // cell sizes | cell output positions | (cursor path: big cells) first key in X | rescue cursors
-  uint32_t* hist2 = cells ? c.take<uint32_t>((size_t)4 * BINS * NB2MAX) : nullptr;
-  uint32_t* base2 = cells ? hist2 + BINS * NB2MAX : nullptr;
-  uint32_t* xoff  = cells ? hist2 + 2 * BINS * NB2MAX : nullptr;
-  uint32_t* todo  = cells ? c.take<uint32_t>((size_t)BINS * NB2MAX) : nullptr;  // cells k_local_place leaves to k_local_sort
-  uint32_t* biglist = fc.on ? c.take<uint32_t>((size_t)2 * BIG_LIST) : nullptr;  // big cells: (cell, first key in X)
-  const int64_t msd_tile     = (int64_t)BT * hyb_kpt;  // tile of the hybrid partition passes
+  carve_cell_tables(c, S, cells, fc.on);
+  const int64_t ntiles       = n > 0 ? div_up(n, TILE) : 0;
+  const int64_t msd_tile     = (int64_t)BT * hc.kpt;  // tile of the hybrid partition passes
   const int64_t msd_ntiles   = n > 0 ? div_up(n, msd_tile) : 0;
   const int64_t status_tiles = (msd_ntiles > ntiles ? msd_ntiles : ntiles) + BINS + 2 * NRANGE;  // segment tails add at most one tile each
-  const size_t status_words  = (size_t)status_tiles * (try_hybrid ? nb1 : BINS);
+  const int nb1              = hc.bits2 > 8 ? NB9 : BINS;  // bins (and look-back granules per tile) of the level-1 pass
+  S.status_words             = (size_t)status_tiles * (hc.on ? nb1 : BINS);
+  uint32_t *tile_hist = nullptr, *partials = nullptr;
   if (algo != 1) {
-    status = c.take<unsigned long long>(status_words);
+    S.status = c.take<unsigned long long>(S.status_words);
   } else {
     tile_hist = c.take<uint32_t>((size_t)ntiles * BINS);
     partials  = c.take<uint32_t>(scan::partials_count(ntiles * BINS));
@@ -3931,13 +4065,14 @@ int sort_impl(const void* keys_in, void* keys_out, const int32_t* vals_in, int32
   // exact level-0 histogram (HybridPlan::ccap: the bucket's mean cell + 6 sigma + 64 keys), so the cell buffer holds n keys + that
   // slack per cell instead of (256 << bits2) slots of the full cell capacity (8.6 / 17.2 GB -> 9.3 GB for the 1e9-row sort)
   // (cursor path only: the look-back path -- floats, pairs, the cursor path's fallback -- keeps (256 << bits2) slots of the full capacity)
-  size_t padded = try_hybrid ? ((size_t)BINS << hc.bits2) << (hc.cl2_alt ? hc.cl2_alt : hc.cl2) : 0;
+  size_t padded = hc.on ? ((size_t)BINS << hc.bits2) << (hc.cl2_alt ? hc.cl2_alt : hc.cl2) : 0;
   if (fc_cells > padded) padded = fc_cells;
   const size_t nb_buf = padded > (size_t)n ? padded : (size_t)n;
-  KeyT* kb_scratch = c.take<KeyT>(nb_buf);
-  KeyT* slot0_buf  = fc.on ? c.take<KeyT>(fc.slot_rows) : nullptr;  // cursor path: padded level-0 output
-  KeyT* ka_scratch = keys_out ? nullptr : c.take<KeyT>((size_t)n);
-  uint32_t* vb     = HAS_VAL ? c.take<uint32_t>(nb_buf) : nullptr;
+  S.cells             = c.take<KeyT>(nb_buf);
+  S.level0_rows       = fc.on ? fc.slot_rows : 0;
+  S.level0            = fc.on ? c.take<KeyT>(S.level0_rows) : nullptr;
+  KeyT* ka_scratch    = keys_out ? nullptr : c.take<KeyT>((size_t)n);
+  uint32_t* vb        = HAS_VAL ? c.take<uint32_t>(nb_buf) : nullptr;
   if (tmp == nullptr) {
     *tmp_bytes = c.total();
     return 0;
@@ -3946,17 +4081,19 @@ int sort_impl(const void* keys_in, void* keys_out, const int32_t* vals_in, int32
   if (n > 0 && (keys_in == nullptr || (HAS_VAL && vals_out == nullptr))) return GX_EINVAL;
   if (n > 0 && keys_in == keys_out) return GX_EINVAL;
 
-  GX_HIP_TRY(hipMemsetAsync(plan, 0, sizeof(SortPlan), stream));
+  GX_HIP_TRY(hipMemsetAsync(S.plan, 0, sizeof(SortPlan), stream));
   if (n == 0) return 0;
   Device dev;
   GX_HIP_TRY(device(&dev));
-  if (algo != 1 && !fc.on) GX_HIP_TRY(hipMemsetAsync(status, 0, status_words * sizeof(unsigned long long), stream));
+  if (algo != 1 && !fc.on) GX_HIP_TRY(hipMemsetAsync(S.status, 0, S.status_words * sizeof(unsigned long long), stream));
   // the cell tables start at zero: on the cursor path its first kernel, k_hf_sample, clears them on its way
-  const size_t hist2_bytes = (size_t)4 * BINS * NB2MAX * sizeof(uint32_t);
-  if (cells && !fc.on) GX_HIP_TRY(hipMemsetAsync(hist2, 0, hist2_bytes, stream));
-  const int64_t range_rows = try_hybrid ? div_up(msd_ntiles, NRANGE) * msd_tile : div_up(ntiles, NRANGE) * TILE;
+  if (cells && !fc.on) GX_HIP_TRY(hipMemsetAsync(S.hist2, 0, CELL_TABLE_BYTES, stream));
+  const int64_t range_rows = hc.on ? div_up(msd_ntiles, NRANGE) * msd_tile : div_up(ntiles, NRANGE) * TILE;
 
   const KeyT desc_mask = descending ? KeyT(~KeyT(0)) : KeyT(0);
+  const KeyT* kin      = static_cast<const KeyT*>(keys_in);
+  KeyT* bufA           = keys_out ? static_cast<KeyT*>(keys_out) : ka_scratch;
+  uint32_t* valA       = reinterpret_cast<uint32_t*>(vals_out);
   g_prof.npass = NPASS;
   int64_t hblocks = div_up(n, (int64_t)BT * 8);
   if (hblocks > 2048) hblocks = 2048;
@@ -3970,37 +4107,23 @@ int sort_impl(const void* keys_in, void* keys_out, const int32_t* vals_in, int32
     if (fc.on) {
       // cursor path: speculative plan from a sample, verified by level 0; on a miss everything below is a no-op and the
       // look-back path further down sorts the column
-      constexpr int FT = BT * hf_kpt<KeyT>();  // k_hf_scatter's tile
-      constexpr int MIN_SHIFT2 = 8;  // key bits that must be left below level 1 (k_local_sort's sub-bucket split takes 7 + 1)
-      constexpr int WORD_BYTES = (int)sizeof(typename PlaceWord<KeyT, CK, HAS_VAL>::type);
-      const int64_t ftiles  = div_up(n, (int64_t)FT);
-      const int64_t frange  = (ftiles / NRANGE) * FT;  // rows per input range (whole tiles; the last range takes the rest)
-      auto lds_hf = [&](int nb) { return (size_t)FT * sizeof(KeyT) + (size_t)(3 * nb + 16 + 4) * 4 + (size_t)2 * NW * 8; };
-      typedef void (*HfK)(const KeyT*, KeyT*, KeyT, SortPlan*, uint32_t*, uint32_t, int64_t, KeyT*, uint32_t);
-      // (the level-1 kernel and the cell grids are sized for bits2_max: the device may take the extra bit)
-      HfK kf1 = fc.bits2_max <= 8 ? (HfK)k_hf_scatter<KeyT, CK, 1, 8> : (fc.bits2_max == 9 ? (HfK)k_hf_scatter<KeyT, CK, 1, 9> : (HfK)k_hf_scatter<KeyT, CK, 1, 10>);
-      HfK kf2 = fc.bits2_max <= 8 ? (HfK)k_hf_scatter<KeyT, CK, 2, 8> : (fc.bits2_max == 9 ? (HfK)k_hf_scatter<KeyT, CK, 2, 9> : (HfK)k_hf_scatter<KeyT, CK, 2, 10>);
-      const int nbf = fc.bits2_max <= 8 ? 256 : (1 << fc.bits2_max);
-      const int64_t step = (int64_t)fc.stride * HF_CHUNK;
-      int64_t sblocks    = div_up(div_up(n, step), (int64_t)4 * 4);
-      if (sblocks > 2048) sblocks = 2048;
-      const KeyT* kin = static_cast<const KeyT*>(keys_in);
-      KeyT* bufA      = keys_out ? static_cast<KeyT*>(keys_out) : ka_scratch;
-      hipLaunchKernelGGL((k_hf_sample<KeyT, CK, false>), dim3((unsigned)sblocks), dim3(256), 0, stream, kin, n, desc_mask, plan, fc.stride, frange,
-                         reinterpret_cast<uint4*>(hist2), hist2_bytes / sizeof(uint4));
-      hipLaunchKernelGGL(k_hf_plan, dim3(1), dim3(BINS), 0, stream, plan, 0, (int)(8 * sizeof(KeyT)), n, fc.bits2, 1 << 13, fc.stride, frange, FT,
+      constexpr int FT   = hf_tile<KeyT>();
+      const SampleGrid g = sample_grid<KeyT>(n, fc.stride);
+      hipLaunchKernelGGL((k_hf_sample<KeyT, CK, false>), dim3(g.sblocks), dim3(256), 0, stream, kin, n, desc_mask, S.plan, fc.stride, g.frange,
+                         reinterpret_cast<uint4*>(S.hist2), CELL_TABLE_BYTES / sizeof(uint4));
+      hipLaunchKernelGGL(k_hf_plan, dim3(1), dim3(BINS), 0, stream, S.plan, 0, (int)(8 * sizeof(KeyT)), n, fc.bits2, 1 << 13, fc.stride, g.frange, FT,
                          (unsigned long long)fc.slot_rows, g_cursor_margin, MIN_SHIFT2, fc.bits2_max, 0ull, CK == K_SIGNED ? 1 : 0, (KIND == K_FLOAT) ? 0 : g_counting);
       {
         // counting sort of a column whose varying bits are its low <= 15 (state 5; no-ops otherwise): histogram in LDS, scan, fill
         // (counters | group starts | group values live in the cell tables, unused on this branch and zeroed above)
-        GX_HIP_TRY(launch_lds(dev, (k_cs_count<KeyT, CK>), dim3(256), dim3(CS_BT), (size_t)4 << CS_MAXBITS, stream, kin, n, desc_mask, plan, hist2));
-        hipLaunchKernelGGL(k_cs_scan, dim3(1), dim3(CS_BT), 0, stream, plan, (const uint32_t*)hist2, base2, xoff, n, NPASS);
-        hipLaunchKernelGGL((k_cs_fill<KeyT, CK>), dim3(4096), dim3(256), 0, stream, bufA, n, desc_mask, (const SortPlan*)plan, (const uint32_t*)base2,
-                           (const uint32_t*)xoff);
+        GX_HIP_TRY(launch_lds(dev, (k_cs_count<KeyT, CK>), dim3(256), dim3(CS_BT), (size_t)4 << CS_MAXBITS, stream, kin, n, desc_mask, S.plan, S.hist2));
+        hipLaunchKernelGGL(k_cs_scan, dim3(1), dim3(CS_BT), 0, stream, S.plan, (const uint32_t*)S.hist2, S.base2, S.xoff, n, NPASS);
+        hipLaunchKernelGGL((k_cs_fill<KeyT, CK>), dim3(4096), dim3(256), 0, stream, bufA, n, desc_mask, (const SortPlan*)S.plan, (const uint32_t*)S.base2,
+                           (const uint32_t*)S.xoff);
       }
-      hipLaunchKernelGGL((k_hf_sample<KeyT, CK, true>), dim3((unsigned)sblocks), dim3(256), 0, stream, kin, n, desc_mask, plan, fc.stride, frange);
+      hipLaunchKernelGGL((k_hf_sample<KeyT, CK, true>), dim3(g.sblocks), dim3(256), 0, stream, kin, n, desc_mask, S.plan, fc.stride, g.frange);
       const int allow_split = (sizeof(KeyT) == 8 && g_split) ? 1 : 0;
-      hipLaunchKernelGGL(k_hf_plan, dim3(1), dim3(BINS), 0, stream, plan, 1, (int)(8 * sizeof(KeyT)), n, fc.bits2, 1 << 13, fc.stride, frange, FT,
+      hipLaunchKernelGGL(k_hf_plan, dim3(1), dim3(BINS), 0, stream, S.plan, 1, (int)(8 * sizeof(KeyT)), n, fc.bits2, 1 << 13, fc.stride, g.frange, FT,
                          (unsigned long long)fc.slot_rows, g_cursor_margin, MIN_SHIFT2, fc.bits2_max, 0ull, 0, 0, allow_split);
       // splitter mode (round 5; no-ops unless stage 1 asked for it): plan the splitters from 16384 sampled keys, take the sample
       // histogram again on the splitter digit, size the level-0 slots from it (stage 1 once more), cut the column with k_sp_level0
@@ -4009,10 +4132,10 @@ int sort_impl(const void* keys_in, void* keys_out, const int32_t* vals_in, int32
         if (allow_split) {
           ftiles_s               = div_up(n, (int64_t)SP_TILE);
           const int64_t frange_s = (ftiles_s / NRANGE) * SP_TILE;
-          GX_HIP_TRY(launch_lds(dev, (k_sp_plan<CK>), dim3(1), dim3(1024), (size_t)SP_NSAMP * 8, stream, kin, n, (uint64_t)desc_mask, plan, fc.bits2_max));
+          GX_HIP_TRY(launch_lds(dev, (k_sp_plan<CK>), dim3(1), dim3(1024), (size_t)SP_NSAMP * 8, stream, kin, n, (uint64_t)desc_mask, S.plan, fc.bits2_max));
           // (half the workgroups of k_hf_sample: each flushes 2048 + 4096 counters)
-          hipLaunchKernelGGL((k_sp_sample<CK>), dim3((unsigned)(sblocks > 1024 ? 1024 : sblocks)), dim3(256), 0, stream, kin, n, (uint64_t)desc_mask, plan, fc.stride, frange_s);
-          hipLaunchKernelGGL(k_hf_plan, dim3(1), dim3(BINS), 0, stream, plan, 1, (int)(8 * sizeof(KeyT)), n, fc.bits2, 1 << 13, fc.stride, frange_s, FT,
+          hipLaunchKernelGGL((k_sp_sample<CK>), dim3(g.sblocks > 1024 ? 1024 : g.sblocks), dim3(256), 0, stream, kin, n, (uint64_t)desc_mask, S.plan, fc.stride, frange_s);
+          hipLaunchKernelGGL(k_hf_plan, dim3(1), dim3(BINS), 0, stream, S.plan, 1, (int)(8 * sizeof(KeyT)), n, fc.bits2, 1 << 13, fc.stride, frange_s, FT,
                              (unsigned long long)fc.slot_rows, g_cursor_margin, MIN_SHIFT2, fc.bits2_max, 0ull, 0, 0, allow_split);
         }
       }
@@ -4020,43 +4143,19 @@ int sort_impl(const void* keys_in, void* keys_out, const int32_t* vals_in, int32
       prof_mark_h(0, stream);
       {
         // level 0, whichever form the plan picked: one workgroup per tile of the form with more tiles (SP_TILE < FT), its LDS request
-        const int64_t tiles0 = ftiles_s > ftiles ? ftiles_s : ftiles;
-        const size_t lds0    = ftiles_s > 0 && sp_level0_lds() > lds_hf(256) ? sp_level0_lds() : lds_hf(256);
-        GX_HIP_TRY(launch_lds(dev, (k_level0<KeyT, CK>), dim3((unsigned)tiles0), dim3(BT), lds0, stream, kin, slot0_buf, desc_mask, plan, hist2, n, ftiles, ftiles_s));
+        const int64_t tiles0 = ftiles_s > g.ftiles ? ftiles_s : g.ftiles;
+        const size_t lds0    = ftiles_s > 0 && sp_level0_lds() > hf_scatter_lds<KeyT>(256) ? sp_level0_lds() : hf_scatter_lds<KeyT>(256);
+        GX_HIP_TRY(launch_lds(dev, (k_level0<KeyT, CK>), dim3((unsigned)tiles0), dim3(BT), lds0, stream, kin, S.level0, desc_mask, S.plan, S.hist2, n, g.ftiles, ftiles_s));
       }
-      hipLaunchKernelGGL(k_hf_plan, dim3(1), dim3(BINS), 0, stream, plan, 2, (int)(8 * sizeof(KeyT)), n, fc.bits2, 1 << 13, fc.stride, frange, FT,
+      hipLaunchKernelGGL(k_hf_plan, dim3(1), dim3(BINS), 0, stream, S.plan, 2, (int)(8 * sizeof(KeyT)), n, fc.bits2, 1 << 13, fc.stride, g.frange, FT,
                          (unsigned long long)fc.slot_rows, g_cursor_margin, MIN_SHIFT2, fc.bits2_max, (unsigned long long)nb_buf);
       prof_mark_h(1, stream);
-      GX_HIP_TRY(launch_lds(dev, kf1, dim3((unsigned)(ftiles + NRANGE * BINS)), dim3(BT), lds_hf(nbf), stream, slot0_buf, kb_scratch, desc_mask, plan, hist2, 1u << 13, n, bufA, 0u));
-      prof_mark_h(2, stream);
-      hipLaunchKernelGGL(k_plan2, dim3(BINS), dim3(GX_WAVE), 0, stream, plan, hist2, base2, NPASS, 1);
-      prof_mark_h(3, stream);
-      if constexpr (sizeof(KeyT) == 8) {
-        if (allow_split)  // splitter mode: the narrow buckets (one value per cell) are filled from their cell starts
-          hipLaunchKernelGGL((k_sp_fill<CK>), dim3(BINS, SP_FILL_Y), dim3(256), 0, stream, bufA, (uint64_t)desc_mask, (const SortPlan*)plan, (const uint32_t*)base2);
-      }
-      // (one workgroup per cell of the plan n suggests; when the device took the extra level-1 bit each of them walks two cells)
-      GX_HIP_TRY(launch_lds(dev, (k_local_place<KeyT, CK, HAS_VAL, 13>), dim3(local_place_grid(BINS << fc.bits2)), dim3((1 << 13) / 16),
-                                 place_lds_bytes(13, WORD_BYTES), stream, kb_scratch, bufA, (const uint32_t*)nullptr, (uint32_t*)nullptr, desc_mask, plan, hist2,
-                                 base2, todo, g_exp, 1));
-      // the cells k_local_place left: 64-bit words (32-bit keys are widened to their sortable form on the way in)
-      GX_HIP_TRY(launch_lds(dev, (k_local_sort<uint64_t, CK, HAS_VAL, 13, KeyT>), dim3(local_sort_grid(BINS << fc.bits2_max)), dim3((1 << 13) / 16),
-                                 ((size_t)8 << 13) + (size_t)(((1 << 13) / 16 / GX_WAVE) * BINS + 32 + 2 * BINS) * 4, stream, (const KeyT*)kb_scratch, bufA,
-                                 (const uint32_t*)nullptr, (uint32_t*)nullptr, (uint64_t)desc_mask, plan, hist2, base2, g_exp, 1, (const uint32_t*)todo));
-      prof_mark_h(4, stream);
-      g_prof.hybrid_marked = g_prof.enabled;
-      cursor_marked        = true;
-      // big cells (a hot value): plan X, fetch their keys again from the level-1 input into X = the level-1 buffer (every other
-      // cell has left it by now); the LSD passes below then sort X between the two halves of the level-0 buffer
-      hipLaunchKernelGGL(k_big_plan, dim3(1), dim3(BINS), 0, stream, plan, (unsigned long long)(fc.slot_rows / 2));
-      hipLaunchKernelGGL(k_big_cells, dim3(BINS), dim3(GX_WAVE), 0, stream, (const SortPlan*)plan, (const uint32_t*)hist2, xoff, biglist);
-      GX_HIP_TRY(launch_lds(dev, kf2, dim3(role_grid(dev, Role::fallback, ftiles + NRANGE * BINS)), dim3(BT), lds_hf(nbf), stream, slot0_buf, kb_scratch, desc_mask, plan,
-                            hist2, 1u << 13, n, bufA, (uint32_t)(ftiles + NRANGE * BINS)));
-      hipLaunchKernelGGL(k_hf_clear_status, dim3(2048), dim3(256), 0, stream, plan, reinterpret_cast<uint4*>(status), status_words / 2);
+      if (int rc = cursor_cells<KeyT, CK>(dev, stream, S, fc, n, g.ftiles + NRANGE * BINS, bufA, desc_mask, true)) return rc;
+      cursor_marked = true;
     }
   }
   if constexpr (sizeof(KeyT) == 8) {
-    if (try_hybrid) {
+    if (hc.on) {
       // hybrid MSD path: every kernel below is a no-op unless the device-side plan enables it
       constexpr size_t pay   = HAS_VAL ? 4 : 0;
       constexpr bool STABLE  = KIND == K_FLOAT || HAS_VAL;
@@ -4066,63 +4165,47 @@ int sort_impl(const void* keys_in, void* keys_out, const int32_t* vals_in, int32
         const int wrows = STABLE ? ((HAS_VAL && nb == NB9) ? NW / 2 : NW) : 2;
         return (size_t)BT * kpt * (sizeof(KeyT) + pay) + (size_t)(wrows * nb + 2 * nb + 16 + 4) * 4;
       };
-      auto lds_loc = [&](int cl2) { return ((size_t)sizeof(KeyT) << cl2) + (size_t)(((1 << cl2) / 16 / GX_WAVE) * BINS + 32 + 2 * BINS) * 4; };
       typedef void (*MsdK)(MsdArgs);
       MsdK kmsd0 = HAS_VAL ? (MsdK)k_msd_pass<KeyT, KIND, HAS_VAL, 10, 4, 8>
-                           : (hyb_kpt == 8 ? (MsdK)k_msd_pass<KeyT, KIND, HAS_VAL, 8, 4, 8>
-                                           : (hyb_kpt == 12 ? (MsdK)k_msd_pass<KeyT, KIND, HAS_VAL, 12, 4, 8> : (MsdK)k_msd_pass<KeyT, KIND, HAS_VAL, 16, 4, 8>));
+                           : (hc.kpt == 8 ? (MsdK)k_msd_pass<KeyT, KIND, HAS_VAL, 8, 4, 8>
+                                           : (hc.kpt == 12 ? (MsdK)k_msd_pass<KeyT, KIND, HAS_VAL, 12, 4, 8> : (MsdK)k_msd_pass<KeyT, KIND, HAS_VAL, 16, 4, 8>));
       MsdK kmsd1 = kmsd0;
-      auto kloc  = k_local_sort<KeyT, KIND, HAS_VAL, 14>;
-      int ls_bt  = (1 << 14) / 16;
-      int kpt1 = hyb_kpt;
       if constexpr (SMALLOK) {
         if (hc.bits2 > 8) {
+          if (hc.kpt != SKPT) return GX_EINTERNAL;  // the 9-bit pass exists for 16 keys per thread only (g_msd_kpt knob)
           kmsd1 = (MsdK)k_msd_pass<KeyT, KIND, HAS_VAL, SKPT, 4, 9>;
-          kpt1  = SKPT;
         }
-        if constexpr (!HAS_VAL) if (g_lbw != 4 && hyb_kpt == 16) {  // A/B knob: predecessors examined per look-back round
+        if constexpr (!HAS_VAL) if (g_lbw != 4 && hc.kpt == 16) {  // A/B knob: predecessors examined per look-back round
           kmsd0 = g_lbw == 8 ? (MsdK)k_msd_pass<KeyT, KIND, HAS_VAL, 16, 8, 8> : (MsdK)k_msd_pass<KeyT, KIND, HAS_VAL, 16, 16, 8>;
           if (hc.bits2 > 8) kmsd1 = g_lbw == 8 ? (MsdK)k_msd_pass<KeyT, KIND, HAS_VAL, 16, 8, 9> : (MsdK)k_msd_pass<KeyT, KIND, HAS_VAL, 16, 16, 9>;
           else kmsd1 = kmsd0;
         }
-        if (hc.cl2 == 13) {
-          kloc  = k_local_sort<KeyT, KIND, HAS_VAL, 13>;
-          ls_bt = (1 << 13) / 16;
-        }
       }
-      if (kpt1 != hyb_kpt) return GX_EINTERNAL;  // the 9-bit pass exists for 16 keys per thread only (g_msd_kpt knob)
       // behind a cursor-path sort of integer keys this chain is a fallback: bounded grids, the kernels walk their tiles / cells (the
       // partition passes in their MULTI form, which exists for the default knobs; with others they keep one workgroup per ticket).
       // Float keys: the chain is what sorts every column with a NaN or a -0.0 -- primary role, launched as without the cursor path
       const Role lb_role = (fc.on && SMALLOK) ? Role::fallback : Role::primary;
-      bool msd_multi     = false;
+      Role msd_role      = Role::primary;
       if constexpr (!HAS_VAL && SMALLOK) {
-        if (lb_role == Role::fallback && hyb_kpt == 16 && g_lbw == 16) {
+        if (lb_role == Role::fallback && hc.kpt == 16 && g_lbw == 16) {
           kmsd0 = (MsdK)k_msd_pass<KeyT, KIND, HAS_VAL, 16, 16, 8, true>;
           kmsd1 = hc.bits2 > 8 ? (MsdK)k_msd_pass<KeyT, KIND, HAS_VAL, 16, 16, 9, true> : kmsd0;
-          msd_multi = true;
+          msd_role = Role::fallback;
         }
       }
-      const Role msd_role = msd_multi ? Role::fallback : Role::primary;
       // ---- up-front: varying bits + level-0 histogram (one read of the keys), plan
-      hipLaunchKernelGGL((k_hy_hist<KeyT, KIND, true>), dim3((unsigned)hblocks), dim3(BT), 0, stream,
-                         static_cast<const KeyT*>(keys_in), n, desc_mask, plan, range_rows);
-      hipLaunchKernelGGL(k_hy_plan, dim3(1), dim3(BINS), 0, stream, plan, 0, (int)(8 * sizeof(KeyT)), n, hc.bits2, 1 << hc.cl2,
+      hipLaunchKernelGGL((k_hy_hist<KeyT, KIND, true>), dim3((unsigned)hblocks), dim3(BT), 0, stream, kin, n, desc_mask, S.plan, range_rows);
+      hipLaunchKernelGGL(k_hy_plan, dim3(1), dim3(BINS), 0, stream, S.plan, 0, (int)(8 * sizeof(KeyT)), n, hc.bits2, 1 << hc.cl2,
                          HAS_VAL ? hc.cl2 : 0, range_rows, (int)msd_tile, base1, 0, KIND == K_SIGNED ? 1 : 0);
-      hipLaunchKernelGGL((k_hy_hist<KeyT, KIND, false>), dim3((unsigned)hblocks), dim3(BT), 0, stream,
-                         static_cast<const KeyT*>(keys_in), n, desc_mask, plan, range_rows);
-      hipLaunchKernelGGL(k_hy_plan, dim3(1), dim3(BINS), 0, stream, plan, 1, (int)(8 * sizeof(KeyT)), n, hc.bits2, 1 << hc.cl2,
+      hipLaunchKernelGGL((k_hy_hist<KeyT, KIND, false>), dim3((unsigned)hblocks), dim3(BT), 0, stream, kin, n, desc_mask, S.plan, range_rows);
+      hipLaunchKernelGGL(k_hy_plan, dim3(1), dim3(BINS), 0, stream, S.plan, 1, (int)(8 * sizeof(KeyT)), n, hc.bits2, 1 << hc.cl2,
                          HAS_VAL ? hc.cl2 : 0, range_rows, (int)msd_tile, base1, hc.cl2_alt ? (1 << hc.cl2_alt) : 0);
       if (!cursor_marked) prof_mark(1, stream);
-      KeyT* bufA = keys_out ? static_cast<KeyT*>(keys_out) : ka_scratch;
-      KeyT* bufB = kb_scratch;
-      uint32_t* valA = reinterpret_cast<uint32_t*>(vals_out);
-      uint32_t* valB = vb;
       MsdArgs m;
       m.vin  = nullptr;  // iota
       m.vout = valA;
-      m.plan      = plan;
-      m.status    = status;
+      m.plan      = S.plan;
+      m.status    = S.status;
       m.n         = n;
       m.desc_mask = (uint64_t)desc_mask;
       m.in        = keys_in;
@@ -4131,59 +4214,59 @@ int sort_impl(const void* keys_in, void* keys_out, const int32_t* vals_in, int32
       m.level     = 0;
       m.exp       = ((HAS_VAL && keys_out == nullptr) ? 64 : 0) | (g_exp & 32);  // bit 6: the caller wants the permutation only (sorted_order): no key
                                                                                   // write-back; bit 5 (knob): k_local_sort's sub-bucket path for every cell
-      m.cellcount = hist2;
+      m.cellcount = S.hist2;
       m.cellcap   = 1u << hc.cl2;
       m.spin_ticks  = (unsigned long long)g_spin_ms * 100000ull | (g_soft_fault ? SPIN_SOFT_BIT : 0ull);
       m.inject_tile = g_inject_tile;
       if (!cursor_marked) prof_mark_h(0, stream);
-      GX_HIP_TRY(launch_lds(dev, kmsd0, dim3(role_grid(dev, msd_role, msd_ntiles + NRANGE)), dim3(BT), lds_msd(hyb_kpt, BINS), stream, m));
+      GX_HIP_TRY(launch_lds(dev, kmsd0, dim3(role_grid(dev, msd_role, msd_ntiles + NRANGE)), dim3(BT), lds_msd(hc.kpt, BINS), stream, m));
       if (!cursor_marked) prof_mark_h(1, stream);
       m.in    = bufA;
-      m.out   = bufB;
+      m.out   = S.cells;
       m.vin   = valA;
-      m.vout  = valB;
+      m.vout  = vb;
       m.level = 1;
-      GX_HIP_TRY(launch_lds(dev, kmsd1, dim3(role_grid(dev, msd_role, msd_ntiles + BINS + NRANGE)), dim3(BT), lds_msd(hyb_kpt, nb1), stream, m));
+      GX_HIP_TRY(launch_lds(dev, kmsd1, dim3(role_grid(dev, msd_role, msd_ntiles + BINS + NRANGE)), dim3(BT), lds_msd(hc.kpt, nb1), stream, m));
       if (!cursor_marked) prof_mark_h(2, stream);
-      hipLaunchKernelGGL(k_plan2, dim3(BINS), dim3(GX_WAVE), 0, stream, plan, hist2, base2, NPASS, 0);
+      hipLaunchKernelGGL(k_plan2, dim3(BINS), dim3(GX_WAVE), 0, stream, S.plan, S.hist2, S.base2, NPASS, 0);
       if (!cursor_marked) prof_mark_h(3, stream);
-      // the cells: k_local_place sorts all but the crowded ones, k_local_sort those (and every cell when the placement does not apply)
-      auto kplace = k_local_place<KeyT, KIND, HAS_VAL, 14>;
-      if constexpr (SMALLOK) {
-        if (hc.cl2 == 13) kplace = k_local_place<KeyT, KIND, HAS_VAL, 13>;
-      }
-      GX_HIP_TRY(launch_lds(dev, kplace, dim3(role_grid(dev, lb_role, local_place_grid(BINS << hc.bits2))), dim3(ls_bt), place_lds_bytes(hc.cl2), stream, (const KeyT*)bufB, bufA,
-                                 (const uint32_t*)valB, valA, desc_mask, plan, hist2, base2, todo, m.exp, 0));
-      GX_HIP_TRY(launch_lds(dev, kloc, dim3(role_grid(dev, lb_role, local_sort_grid(BINS << hc.bits2))), dim3(ls_bt), lds_loc(hc.cl2), stream, bufB, bufA, valB, valA, desc_mask,
-                                 plan, hist2, base2, m.exp, 0, (const uint32_t*)todo));
-      if (hc.cl2_alt == 14) {  // the cell sort on 16384-key cells, should k_hy_plan have switched to them (no-ops otherwise)
-        GX_HIP_TRY(launch_lds(dev, (k_local_place<KeyT, KIND, HAS_VAL, 14>), dim3(role_grid(dev, lb_role, local_place_grid(BINS << hc.bits2))), dim3((1 << 14) / 16), place_lds_bytes(14), stream,
-                                   (const KeyT*)bufB, bufA, (const uint32_t*)valB, valA, desc_mask, plan, hist2, base2, todo, m.exp, 0));
-        GX_HIP_TRY(launch_lds(dev, (k_local_sort<KeyT, KIND, HAS_VAL, 14>), dim3(role_grid(dev, lb_role, local_sort_grid(BINS << hc.bits2))), dim3((1 << 14) / 16), lds_loc(14), stream, bufB, bufA,
-                                   valB, valA, desc_mask, plan, hist2, base2, m.exp, 0, (const uint32_t*)todo));
+      // the cells: k_local_place sorts all but the crowded ones, k_local_sort those (and every cell when the placement does not apply);
+      // then the same on 16384-key cells, should k_hy_plan have switched to them (cl2_alt, which is 0 or 14; no-ops otherwise)
+      const dim3 place_grid(role_grid(dev, lb_role, local_place_grid(BINS << hc.bits2))), sort_grid(role_grid(dev, lb_role, local_sort_grid(BINS << hc.bits2)));
+      for (int cl2 : {hc.cl2, hc.cl2_alt}) {
+        if (cl2 == 0) continue;
+        auto kplace = k_local_place<KeyT, KIND, HAS_VAL, 14>;
+        auto kloc   = k_local_sort<KeyT, KIND, HAS_VAL, 14>;
+        if constexpr (SMALLOK) {
+          if (cl2 == 13) kplace = k_local_place<KeyT, KIND, HAS_VAL, 13>;
+          if (cl2 == 13) kloc = k_local_sort<KeyT, KIND, HAS_VAL, 13>;
+        }
+        GX_HIP_TRY(launch_lds(dev, kplace, place_grid, dim3((1 << cl2) / 16), place_lds_bytes(cl2), stream, (const KeyT*)S.cells, bufA, (const uint32_t*)vb, valA, desc_mask,
+                              S.plan, S.hist2, S.base2, S.todo, m.exp, 0));
+        GX_HIP_TRY(launch_lds(dev, kloc, sort_grid, dim3((1 << cl2) / 16), local_sort_lds(sizeof(KeyT), cl2), stream, S.cells, bufA, vb, valA, desc_mask, S.plan, S.hist2,
+                              S.base2, m.exp, 0, (const uint32_t*)S.todo));
       }
       if (!cursor_marked) prof_mark_h(4, stream);
       if (!cursor_marked) g_prof.hybrid_marked = g_prof.enabled;
     }
   }
   // LSD path: byte histograms + plan (no-ops when the hybrid path has sorted the column)
-  hipLaunchKernelGGL((k_hist_all<KeyT, KIND>), dim3((unsigned)hblocks), dim3(BT), 0, stream,
-                     static_cast<const KeyT*>(keys_in), n, desc_mask, plan, range_rows, (const KeyT*)kb_scratch);
-  hipLaunchKernelGGL(k_plan, dim3(1), dim3(BINS), 0, stream, plan, NPASS, n, KIND == K_SIGNED ? 1 : 0);
-  if (!try_hybrid && !cursor_marked) prof_mark(1, stream);
+  hipLaunchKernelGGL((k_hist_all<KeyT, KIND>), dim3((unsigned)hblocks), dim3(BT), 0, stream, kin, n, desc_mask, S.plan, range_rows, (const KeyT*)S.cells);
+  hipLaunchKernelGGL(k_plan, dim3(1), dim3(BINS), 0, stream, S.plan, NPASS, n, KIND == K_SIGNED ? 1 : 0);
+  if (!hc.on && !cursor_marked) prof_mark(1, stream);
 
   PassArgs a;
   a.kbuf[0]   = const_cast<void*>(keys_in);
-  a.kbuf[1]   = keys_out ? keys_out : static_cast<void*>(ka_scratch);
-  a.kbuf[2]   = kb_scratch;
-  a.kbufB[0]  = kb_scratch;                                              // X (HybridPlan::lsd_mode)
-  a.kbufB[1]  = slot0_buf;                                               // sorted X
-  a.kbufB[2]  = slot0_buf ? slot0_buf + fc.slot_rows / 2 : nullptr;
+  a.kbuf[1]   = bufA;
+  a.kbuf[2]   = S.cells;
+  a.kbufB[0]  = S.cells;   // X (HybridPlan::lsd_mode)
+  a.kbufB[1]  = S.level0;  // sorted X
+  a.kbufB[2]  = S.level0 ? S.level0 + S.level0_rows / 2 : nullptr;
   a.vbuf[0]   = reinterpret_cast<uint32_t*>(const_cast<int32_t*>(vals_in));
-  a.vbuf[1]   = reinterpret_cast<uint32_t*>(vals_out);
+  a.vbuf[1]   = valA;
   a.vbuf[2]   = vb;
-  a.plan      = plan;
-  a.status    = status;
+  a.plan      = S.plan;
+  a.status    = S.status;
   a.tile_off  = tile_hist;
   a.n         = n;
   a.ntiles    = ntiles;
@@ -4191,39 +4274,11 @@ int sort_impl(const void* keys_in, void* keys_out, const int32_t* vals_in, int32
   a.order_mode = g_order_mode;
   a.spin_ticks  = (unsigned long long)g_spin_ms * 100000ull | (g_soft_fault ? SPIN_SOFT_BIT : 0ull);
   a.inject_tile = g_inject_tile;
-
-  constexpr size_t lds = pass_lds_bytes<KeyT, HAS_VAL, KPT>();
-  auto kern_lb         = (algo == 2) ? k_radix_pass<KeyT, KIND, HAS_VAL, KPT, 1>
-                                       : (cells ? k_radix_pass<KeyT, KIND, HAS_VAL, KPT, 4, true> : k_radix_pass<KeyT, KIND, HAS_VAL, KPT, 4>);
-  auto kern_pre        = k_radix_pass<KeyT, KIND, HAS_VAL, KPT, 0>;
-  for (int pass = 0; pass < NPASS; ++pass) {
-    a.pass = pass;
-    prof_mark(2 + 2 * pass, stream);
-    if (algo != 1) {
-      const int64_t lb_grid = (cells && algo != 2) ? div_up(ntiles, PASS_TPB) : ntiles;
-      GX_HIP_TRY(launch_lds(dev, kern_lb, dim3((unsigned)lb_grid), dim3(BT), lds, stream, a));
-    } else {
-      hipLaunchKernelGGL((k_tile_hist<KeyT, KIND, KPT>), dim3((unsigned)ntiles), dim3(BT), 0, stream, a, tile_hist);
-      scan::PlainLoader<uint32_t, uint32_t> ld{tile_hist, nullptr, 0u};
-      int rc = scan::device_scan<uint32_t, uint32_t>(ld, ntiles * BINS, 0u, SumOp(), false, tile_hist, partials,
-                                                     stream, &plan->pass_skip[pass]);
-      if (rc) return rc;
-      GX_HIP_TRY(launch_lds(dev, kern_pre, dim3((unsigned)ntiles), dim3(BT), lds, stream, a));
-    }
-    prof_mark(3 + 2 * pass, stream);
-  }
-  {
-    int64_t blocks = div_up(n, 256 * 8);
-    if (blocks > 4096) blocks = 4096;
-    hipLaunchKernelGGL((k_finalize_copy<KeyT, HAS_VAL>), dim3((unsigned)blocks), dim3(256), 0, stream, a);
-    if (fc.on)
-      hipLaunchKernelGGL((k_big_distribute<KeyT>), dim3(2048), dim3(256), 0, stream, plan, (const KeyT*)slot0_buf,
-                         keys_out ? static_cast<KeyT*>(keys_out) : ka_scratch, (const uint32_t*)biglist, (const uint32_t*)base2);
-    if (KIND == K_FLOAT && descending && radix_nan_rule && sizeof(KeyT) >= 4) {
-      hipLaunchKernelGGL((k_reverse_nan_block<KeyT, HAS_VAL>), dim3(256), dim3(256), 0, stream,
-                         static_cast<KeyT*>(a.kbuf[1]), a.vbuf[1], n);
-    }
-  }
+  int64_t fin_blocks = div_up(n, 256 * 8);
+  if (fin_blocks > 4096) fin_blocks = 4096;
+  if (int rc = lsd_passes<KeyT, KIND, HAS_VAL>(dev, stream, S, a, algo, cells, ntiles, (unsigned)fin_blocks, partials, bufA, true)) return rc;
+  if (KIND == K_FLOAT && descending && radix_nan_rule && sizeof(KeyT) >= 4)
+    hipLaunchKernelGGL((k_reverse_nan_block<KeyT, HAS_VAL>), dim3(256), dim3(256), 0, stream, bufA, valA, n);
   GX_LAUNCH_CHECK();
   return 0;
 }
@@ -4238,22 +4293,10 @@ int sort_impl(const void* keys_in, void* keys_out, const int32_t* vals_in, int32
 // input range) of what arrived.  No separate range-partition pass on the sender, no level 0 on the receiver
 // (the reference's shape: sample -> boundaries -> shuffle -> local sort, cudf_polars collectives/sort.py).
 // ==================================================================================================================
-struct SortxCfg {
-  int bits2, bits2_max, stride;
-  size_t slot_rows;
-};
-static inline SortxCfg sortx_cfg(int64_t n)
-{
-  SortxCfg f{1, 2, 8, 0};
-  int B = 9;
-  while (B < 18 && (double)n / (double)(1ull << B) > 0.955 * 8192.0) ++B;
-  f.bits2     = B - 8;
-  f.bits2_max = f.bits2 < 10 ? f.bits2 + 1 : 10;
-  f.stride    = n >= (1ll << 27) ? 32 : 8;
-  const double dev = 8.0 * 1.25 * f.stride * __builtin_sqrt((double)(NRANGE * BINS) * ((double)n / f.stride + 2.0 * NRANGE * BINS));
-  f.slot_rows = (size_t)((double)n * 1.002 + dev) + (size_t)(NRANGE * BINS) * (size_t)(2 * f.stride * HF_CHUNK + 64 + 16) + 65536;
-  return f;
-}
+// The halves are the cursor path's stages around the exchange: its configuration with a fixed margin (all ranks must agree on the
+// layout whatever knob a caller's thread has set), its launch shapes, and behind the exchange cursor_cells and the X-only LSD passes
+constexpr float SORTX_MARGIN = 8.0f;  // standard deviations of slack per level-0 slot
+static inline CursorCfg sortx_cfg(int64_t n) { return cursor_cfg(n, SORTX_MARGIN); }
 constexpr int SORTX_MAXREG = BINS * 16 * NRANGE;  // regions a receiver can see: every bin from 16 ranks x 8 input ranges
 
 // Receiver: one block, thread t = level-0 bucket t.  From the external region table (bucket-major; breg0[t] = first region of
@@ -4316,13 +4359,8 @@ __global__ void __launch_bounds__(BINS) k_hfx_plan(SortPlan* plan, long long n, 
 }
 
 template <typename KeyT>
-struct SortxLayout {
-  SortPlan* plan;
-  uint32_t *hist2, *base2, *xoff, *todo, *biglist;
-  unsigned long long* status;
-  size_t status_words;
-  KeyT *cells, *level0;
-  size_t cells_rows, level0_rows;  // level0 = this rank's slots (slot_rows of its own n) followed by the receive area
+struct SortxLayout : CellScratch<KeyT> {  // level0 = this rank's slots (slot_rows of its own n) followed by the receive area
+  size_t cells_rows;
   uint32_t *x_tile0, *x_start, *x_count, *x_bucket, *breg0;
   size_t total;
 };
@@ -4331,15 +4369,10 @@ static SortxLayout<KeyT> sortx_layout(void* tmp, int64_t n, int64_t recv_rows_ma
 {
   SortxLayout<KeyT> L{};
   Carver c(tmp);
-  const SortxCfg cs = sortx_cfg(n), cr = sortx_cfg(recv_rows_max);
   L.plan          = c.take<SortPlan>(1);
-  L.hist2         = c.take<uint32_t>((size_t)4 * BINS * NB2MAX);
-  L.base2         = L.hist2 ? L.hist2 + BINS * NB2MAX : nullptr;
-  L.xoff          = L.hist2 ? L.hist2 + 2 * BINS * NB2MAX : nullptr;
-  L.todo          = c.take<uint32_t>((size_t)BINS * NB2MAX);
-  L.biglist       = c.take<uint32_t>((size_t)2 * BIG_LIST);
-  L.level0_rows   = cs.slot_rows + (size_t)recv_rows_max + 65536;
-  L.cells_rows    = (size_t)recv_rows_max + (size_t)recv_rows_max / 16 + ((size_t)BINS << cr.bits2_max) * cell_slack(1 << 13) + 65536;  // per-bucket cell slots (HybridPlan::ccap)
+  carve_cell_tables(c, L, true, true);
+  L.level0_rows   = sortx_cfg(n).slot_rows + (size_t)recv_rows_max + 65536;
+  L.cells_rows    = cursor_cell_rows(recv_rows_max, sortx_cfg(recv_rows_max).bits2_max);
   const size_t xt = L.level0_rows / 2 / (size_t)(BT * 16) + BINS + 2 * NRANGE;  // tiles of the largest X the LSD passes may sort
   L.status_words  = xt * BINS;
   L.status        = c.take<unsigned long long>(L.status_words);
@@ -4364,17 +4397,12 @@ int sortx_sample(const void* keys, int64_t n, int64_t recv_rows_max, void* tmp, 
     return 0;
   }
   if (*tmp_bytes < L.total) return GX_ETMP;
-  const SortxCfg cs = sortx_cfg(n);
+  const CursorCfg cs = sortx_cfg(n);
   GX_HIP_TRY(hipMemsetAsync(L.plan, 0, sizeof(SortPlan), stream));
-  GX_HIP_TRY(hipMemsetAsync(L.hist2, 0, (size_t)4 * BINS * NB2MAX * sizeof(uint32_t), stream));
+  GX_HIP_TRY(hipMemsetAsync(L.hist2, 0, CELL_TABLE_BYTES, stream));
   if (n == 0) return 0;
-  constexpr int FT      = BT * hf_kpt<KeyT>();
-  const int64_t ftiles  = div_up(n, (int64_t)FT);
-  const int64_t frange  = (ftiles / NRANGE) * FT;
-  const int64_t step    = (int64_t)cs.stride * HF_CHUNK;
-  int64_t sblocks       = div_up(div_up(n, step), (int64_t)4 * 4);
-  if (sblocks > 2048) sblocks = 2048;
-  hipLaunchKernelGGL((k_hf_sample<KeyT, KIND, false>), dim3((unsigned)sblocks), dim3(256), 0, stream, static_cast<const KeyT*>(keys), n, KeyT(0), L.plan, cs.stride, frange);
+  const SampleGrid g = sample_grid<KeyT>(n, cs.stride);
+  hipLaunchKernelGGL((k_hf_sample<KeyT, KIND, false>), dim3(g.sblocks), dim3(256), 0, stream, static_cast<const KeyT*>(keys), n, KeyT(0), L.plan, cs.stride, g.frange);
   GX_LAUNCH_CHECK();
   return 0;
 }
@@ -4385,15 +4413,8 @@ int sortx_level0(const void* keys, int64_t n, int64_t recv_rows_max, const unsig
 {
   auto L = sortx_layout<KeyT>(tmp, n, recv_rows_max);
   if (n == 0) return 0;
-  const SortxCfg cs = sortx_cfg(n);
-  constexpr int FT      = BT * hf_kpt<KeyT>();
-  constexpr int MIN_SHIFT2 = 8;
-  const int64_t ftiles  = div_up(n, (int64_t)FT);
-  const int64_t frange  = (ftiles / NRANGE) * FT;
-  const int64_t step    = (int64_t)cs.stride * HF_CHUNK;
-  int64_t sblocks       = div_up(div_up(n, step), (int64_t)4 * 4);
-  if (sblocks > 2048) sblocks = 2048;
-  const size_t lds0 = (size_t)FT * sizeof(KeyT) + (size_t)(3 * 256 + 16 + 4) * 4 + (size_t)2 * NW * 8;
+  const CursorCfg cs = sortx_cfg(n);
+  const SampleGrid g = sample_grid<KeyT>(n, cs.stride);
   Device dev;
   GX_HIP_TRY(device(&dev));
   // the masks of all ranks replace the sample's; forced_masks tells the verdict after level 0 not to compare the local top bit
@@ -4404,14 +4425,14 @@ int sortx_level0(const void* keys, int64_t n, int64_t recv_rows_max, const unsig
   GX_HIP_TRY(hipStreamSynchronize(stream));  // (host sources)
   const KeyT* kin = static_cast<const KeyT*>(keys);
   // bits2 only decides whether enough key bits are left below level 1 (the receiver picks its own from what it receives)
-  hipLaunchKernelGGL(k_hf_plan, dim3(1), dim3(BINS), 0, stream, L.plan, 0, (int)(8 * sizeof(KeyT)), n, bits2_hint, 1 << 13, cs.stride, frange, FT,
-                     (unsigned long long)cs.slot_rows, 8.0f, MIN_SHIFT2, bits2_hint);
-  hipLaunchKernelGGL((k_hf_sample<KeyT, KIND, true>), dim3((unsigned)sblocks), dim3(256), 0, stream, kin, n, KeyT(0), L.plan, cs.stride, frange);
-  hipLaunchKernelGGL(k_hf_plan, dim3(1), dim3(BINS), 0, stream, L.plan, 1, (int)(8 * sizeof(KeyT)), n, bits2_hint, 1 << 13, cs.stride, frange, FT,
-                     (unsigned long long)cs.slot_rows, 8.0f, MIN_SHIFT2, bits2_hint);
-  GX_HIP_TRY(launch_lds(dev, (k_hf_scatter<KeyT, KIND, 0, 8>), dim3((unsigned)ftiles), dim3(BT), lds0, stream, kin, L.level0, KeyT(0), L.plan, L.hist2, 1u << 13, n, (KeyT*)nullptr, 0u));
-  hipLaunchKernelGGL(k_hf_plan, dim3(1), dim3(BINS), 0, stream, L.plan, 2, (int)(8 * sizeof(KeyT)), n, bits2_hint, 1 << 13, cs.stride, frange, FT,
-                     (unsigned long long)cs.slot_rows, 8.0f, MIN_SHIFT2, bits2_hint);
+  for (int stage = 0; stage < 3; ++stage) {  // the plan's stages, with the second sample before stage 1 and level 0 before stage 2
+    if (stage == 1) hipLaunchKernelGGL((k_hf_sample<KeyT, KIND, true>), dim3(g.sblocks), dim3(256), 0, stream, kin, n, KeyT(0), L.plan, cs.stride, g.frange);
+    if (stage == 2)
+      GX_HIP_TRY(launch_lds(dev, (k_hf_scatter<KeyT, KIND, 0, 8>), dim3((unsigned)g.ftiles), dim3(BT), hf_scatter_lds<KeyT>(256), stream, kin, L.level0, KeyT(0), L.plan, L.hist2,
+                            1u << 13, n, (KeyT*)nullptr, 0u));
+    hipLaunchKernelGGL(k_hf_plan, dim3(1), dim3(BINS), 0, stream, L.plan, stage, (int)(8 * sizeof(KeyT)), n, bits2_hint, 1 << 13, cs.stride, g.frange, hf_tile<KeyT>(),
+                       (unsigned long long)cs.slot_rows, SORTX_MARGIN, MIN_SHIFT2, bits2_hint);
+  }
   GX_LAUNCH_CHECK();
   return 0;
 }
@@ -4425,9 +4446,9 @@ int sortx_finish(int64_t n_send, int64_t recv_rows_max, int64_t n, const unsigne
   if (nreg < 0 || nreg > SORTX_MAXREG || n > recv_rows_max + n_send) return GX_EINVAL;
   // a fresh plan: the sender's is spent (its tables have been read by the caller)
   GX_HIP_TRY(hipMemsetAsync(L.plan, 0, sizeof(SortPlan), stream));
-  GX_HIP_TRY(hipMemsetAsync(L.hist2, 0, (size_t)4 * BINS * NB2MAX * sizeof(uint32_t), stream));
+  GX_HIP_TRY(hipMemsetAsync(L.hist2, 0, CELL_TABLE_BYTES, stream));
   if (n == 0) return 0;
-  const SortxCfg cr = sortx_cfg(n), cmax = sortx_cfg(recv_rows_max);
+  const CursorCfg cr = sortx_cfg(n), cmax = sortx_cfg(recv_rows_max);
   if (cr.bits2_max > cmax.bits2_max) return GX_EINVAL;
   std::vector<uint32_t> breg0(BINS + 1, 0);
   for (int q = 0; q < nreg; ++q) {
@@ -4440,38 +4461,17 @@ int sortx_finish(int64_t n_send, int64_t recv_rows_max, int64_t n, const unsigne
   GX_HIP_TRY(hipMemcpyAsync(L.x_bucket, reg_bucket_host, sizeof(uint32_t) * nreg, hipMemcpyHostToDevice, stream));
   GX_HIP_TRY(hipMemcpyAsync(L.breg0, breg0.data(), sizeof(uint32_t) * (BINS + 1), hipMemcpyHostToDevice, stream));
   GX_HIP_TRY(hipStreamSynchronize(stream));  // (host sources)
-  constexpr int FT         = BT * hf_kpt<KeyT>();
-  constexpr int MIN_SHIFT2 = 8;
-  constexpr int WORD_BYTES = (int)sizeof(typename PlaceWord<KeyT, KIND, false>::type);
-  auto lds_hf = [&](int nb) { return (size_t)FT * sizeof(KeyT) + (size_t)(3 * nb + 16 + 4) * 4 + (size_t)2 * NW * 8; };
-  typedef void (*HfK)(const KeyT*, KeyT*, KeyT, SortPlan*, uint32_t*, uint32_t, int64_t, KeyT*, uint32_t);
-  HfK kf1 = cr.bits2_max <= 8 ? (HfK)k_hf_scatter<KeyT, KIND, 1, 8> : (cr.bits2_max == 9 ? (HfK)k_hf_scatter<KeyT, KIND, 1, 9> : (HfK)k_hf_scatter<KeyT, KIND, 1, 10>);
-  HfK kf2 = cr.bits2_max <= 8 ? (HfK)k_hf_scatter<KeyT, KIND, 2, 8> : (cr.bits2_max == 9 ? (HfK)k_hf_scatter<KeyT, KIND, 2, 9> : (HfK)k_hf_scatter<KeyT, KIND, 2, 10>);
-  const int nbf = cr.bits2_max <= 8 ? 256 : (1 << cr.bits2_max);
-  const size_t lds_ls = ((size_t)8 << 13) + (size_t)(((1 << 13) / 16 / GX_WAVE) * BINS + 32 + 2 * BINS) * 4;
-  constexpr int KPT_L = kpt_for<KeyT>(false);
-  constexpr size_t lds_pass = pass_lds_bytes<KeyT, false, KPT_L>();
   Device dev;
   GX_HIP_TRY(device(&dev));
-  // tiles of the regions: one per FT keys + one tail per region
-  const int64_t l1_grid = div_up(n, (int64_t)FT) + nreg;
+  // tiles of the regions: one per tile of keys + one tail per region
+  const int64_t l1_tiles = div_up(n, (int64_t)hf_tile<KeyT>()) + nreg;
   KeyT* bufA = static_cast<KeyT*>(out);
-  hipLaunchKernelGGL(k_hfx_plan, dim3(1), dim3(BINS), 0, stream, L.plan, (long long)n, cr.bits2, cr.bits2_max, 1 << 13, MIN_SHIFT2, FT, masks2_host[0], masks2_host[1],
-                     (uint32_t)nreg, (const uint32_t*)L.breg0, L.x_tile0, (const uint32_t*)L.x_start, (const uint32_t*)L.x_count, (const uint32_t*)L.x_bucket,
-                     (unsigned long long)L.cells_rows);
-  GX_HIP_TRY(launch_lds(dev, kf1, dim3((unsigned)l1_grid), dim3(BT), lds_hf(nbf), stream, (const KeyT*)L.level0, L.cells, KeyT(0), L.plan, L.hist2, 1u << 13, n, (KeyT*)nullptr, 0u));
-  hipLaunchKernelGGL(k_plan2, dim3(BINS), dim3(GX_WAVE), 0, stream, L.plan, L.hist2, L.base2, (int)sizeof(KeyT), 1);
-  GX_HIP_TRY(launch_lds(dev, (k_local_place<KeyT, KIND, false, 13>), dim3(local_place_grid(BINS << cr.bits2)), dim3((1 << 13) / 16), place_lds_bytes(13, WORD_BYTES), stream,
-                             (const KeyT*)L.cells, bufA, (const uint32_t*)nullptr, (uint32_t*)nullptr, KeyT(0), L.plan, L.hist2, L.base2, L.todo, 0, 1));
-  GX_HIP_TRY(launch_lds(dev, (k_local_sort<uint64_t, KIND, false, 13, KeyT>), dim3(local_sort_grid(BINS << cr.bits2_max)), dim3((1 << 13) / 16), lds_ls, stream,
-                             (const KeyT*)L.cells, bufA, (const uint32_t*)nullptr, (uint32_t*)nullptr, (uint64_t)0, L.plan, L.hist2, L.base2, 0, 1, (const uint32_t*)L.todo));
+  hipLaunchKernelGGL(k_hfx_plan, dim3(1), dim3(BINS), 0, stream, L.plan, (long long)n, cr.bits2, cr.bits2_max, 1 << 13, MIN_SHIFT2, hf_tile<KeyT>(), masks2_host[0],
+                     masks2_host[1], (uint32_t)nreg, (const uint32_t*)L.breg0, L.x_tile0, (const uint32_t*)L.x_start, (const uint32_t*)L.x_count,
+                     (const uint32_t*)L.x_bucket, (unsigned long long)L.cells_rows);
   // big cells: X in the cell buffer, the LSD passes between the two halves of the level-0 area (every region has been read by then)
   const size_t xcap = L.level0_rows / 2;
-  hipLaunchKernelGGL(k_big_plan, dim3(1), dim3(BINS), 0, stream, L.plan, (unsigned long long)xcap);
-  hipLaunchKernelGGL(k_big_cells, dim3(BINS), dim3(GX_WAVE), 0, stream, (const SortPlan*)L.plan, (const uint32_t*)L.hist2, L.xoff, L.biglist);
-  GX_HIP_TRY(launch_lds(dev, kf2, dim3(role_grid(dev, Role::fallback, l1_grid)), dim3(BT), lds_hf(nbf), stream, (const KeyT*)L.level0, L.cells, KeyT(0), L.plan, L.hist2, 1u << 13, n,
-                        (KeyT*)nullptr, (uint32_t)l1_grid));
-  hipLaunchKernelGGL(k_hf_clear_status, dim3(2048), dim3(256), 0, stream, L.plan, reinterpret_cast<uint4*>(L.status), L.status_words / 2);
+  if (int rc = cursor_cells<KeyT, KIND>(dev, stream, L, cr, n, l1_tiles, bufA, KeyT(0), false)) return rc;
   int64_t hblocks = div_up(n, (int64_t)BT * 8);
   if (hblocks > 2048) hblocks = 2048;
   hblocks = div_up(hblocks, NRANGE) * NRANGE;
@@ -4489,14 +4489,8 @@ int sortx_finish(int64_t n_send, int64_t recv_rows_max, int64_t n, const unsigne
   a.n         = 0;
   a.ntiles    = 0;
   a.desc_mask = 0;
-  const int64_t xtiles = div_up((int64_t)(n < (int64_t)xcap ? n : (int64_t)xcap), (int64_t)(BT * KPT_L));
-  for (int pass = 0; pass < (int)sizeof(KeyT); ++pass) {
-    a.pass = pass;
-    GX_HIP_TRY(launch_lds(dev, (k_radix_pass<KeyT, KIND, false, KPT_L, 4, true>), dim3((unsigned)div_up(xtiles, (int64_t)PASS_TPB)), dim3(BT), lds_pass, stream, a));
-  }
-  hipLaunchKernelGGL((k_finalize_copy<KeyT, false>), dim3(1024), dim3(256), 0, stream, a);
-  hipLaunchKernelGGL((k_big_distribute<KeyT>), dim3(2048), dim3(256), 0, stream, (const SortPlan*)L.plan, (const KeyT*)L.level0, bufA, (const uint32_t*)L.biglist,
-                     (const uint32_t*)L.base2);
+  const int64_t xtiles = div_up((int64_t)(n < (int64_t)xcap ? n : (int64_t)xcap), (int64_t)(BT * kpt_for<KeyT>(false)));
+  if (int rc = lsd_passes<KeyT, KIND, false>(dev, stream, L, a, 0, true, xtiles, 1024u, nullptr, bufA, false)) return rc;
   GX_LAUNCH_CHECK();
   return 0;
 }
@@ -4703,19 +4697,12 @@ void* gx_sortx_level0_buffer(int dtype, void* tmp, int64_t n, int64_t recv_rows_
 {
   using namespace gx::sort;
   if (!tmp || n < 0 || recv_rows_max < 0) return nullptr;
-  if (dtype == GX_INT64 || dtype == GX_UINT64) {
-    auto L = sortx_layout<uint64_t>(tmp, n, recv_rows_max);
-    if (own_rows) *own_rows = (int64_t)sortx_cfg(n).slot_rows;
-    if (total_rows) *total_rows = (int64_t)L.level0_rows;
-    return L.level0;
-  }
-  if (dtype == GX_INT32 || dtype == GX_UINT32) {
-    auto L = sortx_layout<uint32_t>(tmp, n, recv_rows_max);
-    if (own_rows) *own_rows = (int64_t)sortx_cfg(n).slot_rows;
-    if (total_rows) *total_rows = (int64_t)L.level0_rows;
-    return L.level0;
-  }
-  return nullptr;
+  const bool k64 = dtype == GX_INT64 || dtype == GX_UINT64;
+  if (!k64 && dtype != GX_INT32 && dtype != GX_UINT32) return nullptr;
+  const auto L64 = sortx_layout<uint64_t>(tmp, n, recv_rows_max);  // (the row counts do not depend on the key width)
+  if (own_rows) *own_rows = (int64_t)sortx_cfg(n).slot_rows;
+  if (total_rows) *total_rows = (int64_t)L64.level0_rows;
+  return k64 ? (void*)L64.level0 : (void*)sortx_layout<uint32_t>(tmp, n, recv_rows_max).level0;
 }
 int gx_sortx_finish(int dtype, int64_t n_send, int64_t recv_rows_max, int64_t n, const uint64_t* masks2_host, const uint32_t* reg_start_host,
                     const uint32_t* reg_count_host, const uint32_t* reg_bucket_host, int nreg, void* out, void* tmp, gx_stream_t s)
