@@ -8,6 +8,7 @@
 #include <stdint.h>
 
 #include "../../include/cudf_amd/gx.h"
+#include "gx_dtype.hpp"  // KeyKind, with_dtype: the one dtype table
 #include "gx_lds_book.hpp"
 
 #define GX_WAVE 64
@@ -50,6 +51,16 @@ inline int with_width(int elem_size, F&& f)
   }
 }
 
+// The scratch convention of every entry point that takes (void* tmp, size_t* tmp_bytes), once it knows it needs `need` bytes:
+// false = return *rc now -- 0 with the size stored in *tmp_bytes on a query (tmp is NULL), GX_ETMP when the caller's *tmp_bytes is
+// too small -- true = go on.  Call sites: `if (int rc; !c.ready(tmp_bytes, &rc)) return rc;`
+inline bool scratch_ready(const void* tmp, size_t need, size_t* tmp_bytes, int* rc)
+{
+  *rc = (tmp && *tmp_bytes < need) ? GX_ETMP : 0;
+  if (!tmp) *tmp_bytes = need;
+  return tmp && *rc == 0;
+}
+
 // carve helper for caller-provided scratch
 struct Carver {
   char* base;
@@ -64,6 +75,7 @@ struct Carver {
     return r;
   }
   size_t total() const { return align_up(off, 256); }
+  bool ready(size_t* tmp_bytes, int* rc) const { return scratch_ready(base, total(), tmp_bytes, rc); }  // after the last take()
 };
 
 // ---------------------------------------------------------------- launch layer (host)
@@ -624,7 +636,6 @@ __device__ __forceinline__ unsigned wave_split_sort_x2(uint64_t* keysA, uint32_t
 //  <=> equivalent under the row comparator (NaN == NaN, -0 == +0).
 //  K_FTOTAL (round 5): the IEEE total-order flip alone -- a BIJECTION (from_sortable below), which is the cudf order exactly on
 //  columns that hold no NaN and no -0.0 ("clean" float columns: the sort's unordered levels check every key and fall back).
-enum KeyKind { K_UNSIGNED = 0, K_SIGNED = 1, K_FLOAT = 2, K_FTOTAL = 3 };
 template <typename U, int KIND>
 __host__ __device__ __forceinline__ U to_sortable(U bits, U desc_mask)
 {

@@ -293,15 +293,7 @@ int compare_launch(const void* in, const uint32_t* valid, int64_t n, int cmp, ui
 static inline int select_prologue(int64_t n, void* tmp, size_t* tmp_bytes, int64_t* count_dev, Plan& p, hipStream_t s, int& rc)
 {
   p = carve(tmp, n);
-  if (!tmp) {
-    *tmp_bytes = p.bytes;
-    rc         = 0;
-    return 1;
-  }
-  if (*tmp_bytes < p.bytes) {
-    rc = GX_ETMP;
-    return 1;
-  }
+  if (!scratch_ready(tmp, p.bytes, tmp_bytes, &rc)) return 1;
   if (n == 0) {
     rc = 0;
     if (count_dev) {
@@ -431,19 +423,9 @@ int gx_compare_scalar(int dtype, const void* in, const uint32_t* in_valid, int64
   if (n > 0 && (!in || !out_bool8)) return GX_EINVAL;
   if (n == 0) return 0;
   hipStream_t s = (hipStream_t)stream;
-  switch (dtype) {
-    case GX_INT8: return compare_launch<int8_t>(in, in_valid, n, cmp, scalar_bits, out_bool8, s);
-    case GX_UINT8:
-    case GX_BOOL8: return compare_launch<uint8_t>(in, in_valid, n, cmp, scalar_bits, out_bool8, s);
-    case GX_INT16: return compare_launch<int16_t>(in, in_valid, n, cmp, scalar_bits, out_bool8, s);
-    case GX_UINT16: return compare_launch<uint16_t>(in, in_valid, n, cmp, scalar_bits, out_bool8, s);
-    case GX_INT32: return compare_launch<int32_t>(in, in_valid, n, cmp, scalar_bits, out_bool8, s);
-    case GX_UINT32: return compare_launch<uint32_t>(in, in_valid, n, cmp, scalar_bits, out_bool8, s);
-    case GX_INT64: return compare_launch<int64_t>(in, in_valid, n, cmp, scalar_bits, out_bool8, s);
-    case GX_UINT64: return compare_launch<uint64_t>(in, in_valid, n, cmp, scalar_bits, out_bool8, s);
-    case GX_FLOAT32: return compare_launch<float>(in, in_valid, n, cmp, scalar_bits, out_bool8, s);
-    default: return compare_launch<double>(in, in_valid, n, cmp, scalar_bits, out_bool8, s);
-  }
+  return with_dtype(dtype, [&](auto t) {
+    return compare_launch<typename decltype(t)::value_type>(in, in_valid, n, cmp, scalar_bits, out_bool8, s);
+  });
 }
 
 }  // extern "C"

@@ -310,11 +310,7 @@ int gx_concatenate(int elem_size, int ninputs, const void* const* cols_host, con
   const char** src       = cv.take<const char*>((size_t)ninputs);
   const uint32_t** valid = cv.take<const uint32_t*>((size_t)ninputs);
   long long* bbit        = cv.take<long long>((size_t)ninputs);
-  if (!tmp) {
-    *tmp_bytes = cv.total();
-    return 0;
-  }
-  if (*tmp_bytes < cv.total()) return GX_ETMP;
+  if (int rc; !cv.ready(tmp_bytes, &rc)) return rc;
   if ((!cols_host && out) || !rows_host) return GX_EINVAL;
   int64_t n = 0;
   for (int k = 0; k < ninputs; ++k) {

@@ -252,11 +252,7 @@ int gx_select_unique(int nkeys, const int* dtypes_host, const void* const* cols_
   UniquePred pred{};
   if (int rc = check_args(nkeys, dtypes_host, cols_host, valid_ptrs_host, begin_bits_host, n, keep, flags, sel_tmp, tmp_bytes, pred.keys)) return rc;
   const Plan p = compact::carve(sel_tmp, n);
-  if (!sel_tmp) {
-    *tmp_bytes = p.bytes;
-    return 0;
-  }
-  if (*tmp_bytes < p.bytes) return GX_ETMP;
+  if (int rc; !scratch_ready(sel_tmp, p.bytes, tmp_bytes, &rc)) return rc;
   hipStream_t s = (hipStream_t)stream;
   if (n == 0) return zero_count(count_dev, s);
   pred.n    = n;
@@ -271,11 +267,7 @@ int gx_select_distinct(int nkeys, const int* dtypes_host, const void* const* col
   Keys keys;
   if (int rc = check_args(nkeys, dtypes_host, cols_host, valid_ptrs_host, begin_bits_host, n, keep, flags, sel_tmp, tmp_bytes, keys)) return rc;
   Layout l = carve_all(sel_tmp, n, keep);
-  if (!sel_tmp) {
-    *tmp_bytes = l.bytes;
-    return 0;
-  }
-  if (*tmp_bytes < l.bytes) return GX_ETMP;
+  if (int rc; !scratch_ready(sel_tmp, l.bytes, tmp_bytes, &rc)) return rc;
   hipStream_t s = (hipStream_t)stream;
   if (n == 0) return zero_count(count_dev, s);
   const int hb = g_hash_bits.load(std::memory_order_relaxed);

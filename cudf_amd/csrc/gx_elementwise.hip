@@ -49,15 +49,6 @@ template <> struct class_of<float> { static constexpr int value = CLS_F32; };
 template <> struct class_of<double> { static constexpr int value = CLS_F64; };
 
 static inline bool dtype_ok(int d) { return d >= GX_INT8 && d <= GX_BOOL8; }
-static inline int dtype_bytes(int d)
-{
-  switch (d) {
-    case GX_INT8: case GX_UINT8: case GX_BOOL8: return 1;
-    case GX_INT16: case GX_UINT16: return 2;
-    case GX_INT32: case GX_UINT32: case GX_FLOAT32: return 4;
-    default: return 8;
-  }
-}
 
 // R consecutive elements moved as one access of R * sizeof(T) <= 16 bytes where the column's first row is aligned to that size
 // (row0 is a multiple of R, so the base decides for every access: a wave-uniform choice); a sliced view that starts elsewhere is
@@ -552,7 +543,7 @@ static inline int max3(int a, int b, int c) { return a > b ? (a > c ? a : c) : (
 static int unary_launch(int op, int in_dtype, const void* in, int64_t n, int out_dtype, void* out, hipStream_t s)
 {
   const Operand l{{in, nullptr, 0, nullptr, 0}, in_dtype};
-  const int widest = dtype_bytes(in_dtype) > dtype_bytes(out_dtype) ? dtype_bytes(in_dtype) : dtype_bytes(out_dtype);
+  const int widest = gx_dtype_size(in_dtype) > gx_dtype_size(out_dtype) ? gx_dtype_size(in_dtype) : gx_dtype_size(out_dtype);
   return ew_dispatch<KIND_UNARY>(class_of_dtype(in_dtype), widest, op, l, l, n, out_dtype, out, nullptr, nullptr, 0, s);
 }
 
@@ -608,8 +599,8 @@ int gx_binary_op(int op, int lhs_dtype, const void* lhs, const uint32_t* lhs_val
   const gx::Operand r{{rhs, rhs_is_scalar ? nullptr : rhs_valid, rhs_begin_bit, rhs_scalar_valid_dev, rhs_is_scalar}, rhs_dtype};
   const int cl = gx::class_of_dtype(lhs_dtype), cr = gx::class_of_dtype(rhs_dtype);
   const int c  = cl > cr ? cl : cr;
-  const int widest   = gx::max3(gx::dtype_bytes(lhs_dtype), gx::dtype_bytes(rhs_dtype), gx::dtype_bytes(out_dtype));
-  const int lhs_bits = gx::dtype_bytes(lhs_dtype) * 8;
+  const int widest   = gx::max3(gx_dtype_size(lhs_dtype), gx_dtype_size(rhs_dtype), gx_dtype_size(out_dtype));
+  const int lhs_bits = gx_dtype_size(lhs_dtype) * 8;
   int64_t* nulls     = out_valid ? out_null_count_dev : nullptr;  // without a bitmap there are no nulls: the count stays 0
   switch (gx::binop_kind(op)) {
     case gx::KIND_BASIC: return gx::ew_dispatch<gx::KIND_BASIC>(c, widest, op, l, r, n, out_dtype, out, out_valid, nulls, lhs_bits, s);

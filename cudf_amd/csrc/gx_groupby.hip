@@ -1320,11 +1320,7 @@ int groupby_impl(const void* keys, const uint32_t* kvalid, const void* vals, con
   const bool partitioned = (!Agg::values_optional || vals != nullptr) && g_gb_algorithm != 1 && n > 0 &&
                            (g_gb_algorithm == 2 || n >= PART_MIN_ROWS);
   Scratch<K, V, Agg> sc(tmp, cap, n, partitioned, vvalid != nullptr);
-  if (!tmp) {
-    *tmp_bytes = sc.total;
-    return 0;
-  }
-  if (*tmp_bytes < sc.total) return GX_ETMP;
+  if (int rc; !gx::scratch_ready(tmp, sc.total, tmp_bytes, &rc)) return rc;
   // state, table and the zero-initialised accumulators are contiguous: one memset up to the all-ones block (MIN) or `pos`
   char* ones = static_cast<char*>(Agg::ones(sc.acc));
   GX_HIP_TRY(hipMemsetAsync(tmp, 0, (size_t)((ones ? ones : reinterpret_cast<char*>(sc.pos)) - static_cast<char*>(tmp)), s));
@@ -1364,38 +1360,22 @@ template <typename K, template <typename, bool> class AggOf, typename Out>
 int dispatch_val(int val_dtype, const void* keys, const uint32_t* kvalid, const void* vals, const uint32_t* vvalid,
                  int64_t n, int64_t max_groups, void* out_keys, Out out, int64_t* ngroups, void* tmp, size_t* tmp_bytes, hipStream_t s)
 {
-#define GX_GB(V, F) \
-  return groupby_impl<K, V, AggOf<V, F>>(keys, kvalid, vals, vvalid, n, max_groups, out_keys, out, ngroups, tmp, tmp_bytes, s)
-  switch (val_dtype) {
-    case GX_INT8: GX_GB(int8_t, false);
-    case GX_INT16: GX_GB(int16_t, false);
-    case GX_INT32: GX_GB(int32_t, false);
-    case GX_INT64: GX_GB(int64_t, false);
-    case GX_BOOL8:
-    case GX_UINT8: GX_GB(uint8_t, false);
-    case GX_UINT16: GX_GB(uint16_t, false);
-    case GX_UINT32: GX_GB(uint32_t, false);
-    case GX_UINT64: GX_GB(uint64_t, false);
-    case GX_FLOAT32: GX_GB(float, true);
-    case GX_FLOAT64: GX_GB(double, true);
-    default: return GX_EDTYPE;
-  }
-#undef GX_GB
+  return with_dtype(val_dtype, [&](auto t) {
+    using V = typename decltype(t)::value_type;
+    return groupby_impl<K, V, AggOf<V, decltype(t)::kind == K_FLOAT>>(keys, kvalid, vals, vvalid, n, max_groups, out_keys, out, ngroups, tmp,
+                                                                      tmp_bytes, s);
+  });
 }
 
 template <template <typename, bool> class AggOf, typename Out>
 int dispatch(int key_dtype, int val_dtype, const void* keys, const uint32_t* kvalid, const void* vals, const uint32_t* vvalid,
              int64_t n, int64_t max_groups, void* out_keys, Out out, int64_t* ngroups, void* tmp, size_t* tmp_bytes, hipStream_t s)
 {
-  switch (key_dtype) {
-    case GX_INT32:
-    case GX_UINT32:
-      return dispatch_val<uint32_t, AggOf>(val_dtype, keys, kvalid, vals, vvalid, n, max_groups, out_keys, out, ngroups, tmp, tmp_bytes, s);
-    case GX_INT64:
-    case GX_UINT64:
-      return dispatch_val<uint64_t, AggOf>(val_dtype, keys, kvalid, vals, vvalid, n, max_groups, out_keys, out, ngroups, tmp, tmp_bytes, s);
-    default: return GX_EDTYPE;
-  }
+  return with_dtype(key_dtype, [&](auto t) -> int {
+    using K = typename decltype(t)::word_type;
+    if constexpr (decltype(t)::kind == K_FLOAT || sizeof(K) < 4) return GX_EDTYPE;  // integer keys of 4 or 8 bytes only
+    else return dispatch_val<K, AggOf>(val_dtype, keys, kvalid, vals, vvalid, n, max_groups, out_keys, out, ngroups, tmp, tmp_bytes, s);
+  });
 }
 
 }  // namespace gb
@@ -1695,24 +1675,13 @@ int gx_square(int dtype, const void* in, int64_t n, void* out, gx_stream_t s)
   if (n == 0) return 0;
   int64_t blocks = gx::div_up(n, (int64_t)256 * 8);
   if (blocks > 16384) blocks = 16384;
-#define GX_SQ(V, S) hipLaunchKernelGGL((gx::gb::k_square<V, S>), dim3((unsigned)blocks), dim3(256), 0, s, static_cast<const V*>(in), n, static_cast<S*>(out)); break
-  switch (dtype) {
-    case GX_INT8: GX_SQ(int8_t, int64_t);
-    case GX_INT16: GX_SQ(int16_t, int64_t);
-    case GX_INT32: GX_SQ(int32_t, int64_t);
-    case GX_INT64: GX_SQ(int64_t, int64_t);
-    case GX_BOOL8:
-    case GX_UINT8: GX_SQ(uint8_t, int64_t);
-    case GX_UINT16: GX_SQ(uint16_t, int64_t);
-    case GX_UINT32: GX_SQ(uint32_t, int64_t);
-    case GX_UINT64: GX_SQ(uint64_t, int64_t);
-    case GX_FLOAT32: GX_SQ(float, float);
-    case GX_FLOAT64: GX_SQ(double, double);
-    default: return GX_EDTYPE;
-  }
-#undef GX_SQ
-  GX_LAUNCH_CHECK();
-  return 0;
+  return gx::with_dtype(dtype, [&](auto t) {  // integers square into INT64, floats into their own type
+    using V = typename decltype(t)::value_type;
+    using S = std::conditional_t<decltype(t)::kind == gx::K_FLOAT, V, int64_t>;
+    hipLaunchKernelGGL((gx::gb::k_square<V, S>), dim3((unsigned)blocks), dim3(256), 0, s, static_cast<const V*>(in), n, static_cast<S*>(out));
+    GX_LAUNCH_CHECK();
+    return 0;
+  });
 }
 
 int gx_square_centered(const double* in, const int32_t* group_of_row, const double* mean, int64_t n, int64_t num_groups,
@@ -1753,22 +1722,9 @@ int gx_groupby_arg_select(int val_dtype, const void* vals, const uint32_t* vals_
   if (n < 0 || num_groups < 0 || (n > 0 && (!vals || !group_of_row)) || (num_groups > 0 && (!target || !out_rows)))
     return GX_EINVAL;
   if (num_groups == 0) return 0;
-#define GX_AS(V) return gx::gb::arg_select_impl<V>(vals, vals_valid, group_of_row, n, target, num_groups, out_rows, s)
-  switch (val_dtype) {
-    case GX_INT8: GX_AS(int8_t);
-    case GX_INT16: GX_AS(int16_t);
-    case GX_INT32: GX_AS(int32_t);
-    case GX_INT64: GX_AS(int64_t);
-    case GX_BOOL8:
-    case GX_UINT8: GX_AS(uint8_t);
-    case GX_UINT16: GX_AS(uint16_t);
-    case GX_UINT32: GX_AS(uint32_t);
-    case GX_UINT64: GX_AS(uint64_t);
-    case GX_FLOAT32: GX_AS(float);
-    case GX_FLOAT64: GX_AS(double);
-    default: return GX_EDTYPE;
-  }
-#undef GX_AS
+  return gx::with_dtype(val_dtype, [&](auto t) {
+    return gx::gb::arg_select_impl<typename decltype(t)::value_type>(vals, vals_valid, group_of_row, n, target, num_groups, out_rows, s);
+  });
 }
 
 }  // extern "C"
@@ -2129,11 +2085,7 @@ int wide_impl(const void* const* key_cols, const void* vals, int64_t n, int64_t 
   WideOut pk{};
   for (int w = 0; w < W; ++w) pk.k[w] = c.take<unsigned long long>(elems);
   V* pv = c.take<V>(elems);
-  if (tmp == nullptr) {
-    *tmp_bytes = c.total();
-    return 0;
-  }
-  if (*tmp_bytes < c.total()) return GX_ETMP;
+  if (int rc; !c.ready(tmp_bytes, &rc)) return rc;
   WideCols kc{};
   WideOut ok{};
   for (int w = 0; w < W; ++w) {

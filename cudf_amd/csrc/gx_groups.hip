@@ -206,20 +206,10 @@ int gx_group_heads(int dtype, const void* col, const uint32_t* valid, const int3
   using namespace gx::grp;
   if (n < 0 || (n > 0 && (!col || !heads))) return GX_EINVAL;
   if (n == 0) return 0;
-  switch (dtype) {
-    case GX_INT8: return heads_launch<uint8_t, K_SIGNED>(col, valid, order, n, combine, heads, s);
-    case GX_BOOL8:
-    case GX_UINT8: return heads_launch<uint8_t, K_UNSIGNED>(col, valid, order, n, combine, heads, s);
-    case GX_INT16: return heads_launch<uint16_t, K_SIGNED>(col, valid, order, n, combine, heads, s);
-    case GX_UINT16: return heads_launch<uint16_t, K_UNSIGNED>(col, valid, order, n, combine, heads, s);
-    case GX_INT32: return heads_launch<uint32_t, K_SIGNED>(col, valid, order, n, combine, heads, s);
-    case GX_UINT32: return heads_launch<uint32_t, K_UNSIGNED>(col, valid, order, n, combine, heads, s);
-    case GX_FLOAT32: return heads_launch<uint32_t, K_FLOAT>(col, valid, order, n, combine, heads, s);
-    case GX_INT64: return heads_launch<uint64_t, K_SIGNED>(col, valid, order, n, combine, heads, s);
-    case GX_UINT64: return heads_launch<uint64_t, K_UNSIGNED>(col, valid, order, n, combine, heads, s);
-    case GX_FLOAT64: return heads_launch<uint64_t, K_FLOAT>(col, valid, order, n, combine, heads, s);
-    default: return GX_EDTYPE;
-  }
+  return with_dtype(dtype, [&](auto t) {
+    using D = decltype(t);
+    return heads_launch<typename D::word_type, D::kind>(col, valid, order, n, combine, heads, s);
+  });
 }
 
 int gx_group_offsets(const uint8_t* heads, int64_t n, int32_t* labels, int32_t* offsets, int32_t* sizes, int64_t* ngroups_dev,
@@ -230,11 +220,7 @@ int gx_group_offsets(const uint8_t* heads, int64_t n, int32_t* labels, int32_t* 
   if (n < 0 || !tmp_bytes) return GX_EINVAL;
   Carver c(tmp);
   int32_t* partials = c.take<int32_t>(scan::partials_count(n));
-  if (!tmp) {
-    *tmp_bytes = c.total();
-    return 0;
-  }
-  if (*tmp_bytes < c.total()) return GX_ETMP;
+  if (int rc; !c.ready(tmp_bytes, &rc)) return rc;
   if (!ngroups_dev) return GX_EINVAL;
   if (n == 0) {
     GX_HIP_TRY(hipMemsetAsync(ngroups_dev, 0, sizeof(int64_t), s));
@@ -279,11 +265,7 @@ int gx_segmented_fill_nulls(int elem_size, const void* in, const uint32_t* in_va
   Carver c(tmp);
   SrcOut* src      = c.take<SrcOut>((size_t)n);
   SrcSeg* partials = c.take<SrcSeg>(scan::partials_count(n));
-  if (!tmp) {
-    *tmp_bytes = c.total();
-    return 0;
-  }
-  if (*tmp_bytes < c.total()) return GX_ETMP;
+  if (int rc; !c.ready(tmp_bytes, &rc)) return rc;
   if (n == 0) return 0;
   if (!in || !heads || !out || !out_valid) return GX_EINVAL;
   int rc = scan::device_scan<SrcSeg, SrcOut>(SrcLoader{in_valid, heads, n, backward}, n, SrcSeg{-1, 0u}, SrcOp(), true, src, partials, s);

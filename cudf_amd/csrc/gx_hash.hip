@@ -142,11 +142,7 @@ int partition_impl(int key_dtype, const uint32_t* row_hash, int64_t n, int npart
   K* pid         = c.take<K>((size_t)n);
   K* pid_sorted  = c.take<K>((size_t)n);
   char* sort_tmp = c.take<char>(sort_bytes);
-  if (!tmp) {
-    *tmp_bytes = c.total();
-    return 0;
-  }
-  if (*tmp_bytes < c.total()) return GX_ETMP;
+  if (int rc; !c.ready(tmp_bytes, &rc)) return rc;
   if (n > 0) {
     int64_t blocks = div_up(n, 256 * 8);
     if (blocks > 4096) blocks = 4096;
@@ -172,20 +168,11 @@ int gx_murmur3_32(int dtype, const void* in, const uint32_t* valid, int64_t n, u
   if (n < 0) return GX_EINVAL;
   if (n == 0) return 0;
   if (!in || !out) return GX_EINVAL;
-  switch (dtype) {
-    case GX_BOOL8: return gx::murmur_launch<uint8_t, 1>(in, valid, n, seed, combine, out, s);
-    case GX_INT8:
-    case GX_UINT8: return gx::murmur_launch<uint8_t, 0>(in, valid, n, seed, combine, out, s);
-    case GX_INT16:
-    case GX_UINT16: return gx::murmur_launch<uint16_t, 0>(in, valid, n, seed, combine, out, s);
-    case GX_INT32:
-    case GX_UINT32: return gx::murmur_launch<uint32_t, 0>(in, valid, n, seed, combine, out, s);
-    case GX_FLOAT32: return gx::murmur_launch<uint32_t, 2>(in, valid, n, seed, combine, out, s);
-    case GX_INT64:
-    case GX_UINT64: return gx::murmur_launch<uint64_t, 0>(in, valid, n, seed, combine, out, s);
-    case GX_FLOAT64: return gx::murmur_launch<uint64_t, 2>(in, valid, n, seed, combine, out, s);
-    default: return GX_EDTYPE;
-  }
+  return gx::with_dtype(dtype, [&](auto t) {  // integers hash their bytes whatever their sign; a BOOL8 byte hashes as 0 or 1
+    using D            = decltype(t);
+    constexpr int MODE = D::is_bool ? 1 : D::kind == gx::K_FLOAT ? 2 : 0;
+    return gx::murmur_launch<typename D::word_type, MODE>(in, valid, n, seed, combine, out, s);
+  });
 }
 
 int gx_identity_hash_32(int dtype, const void* in, const uint32_t* valid, int64_t n, int combine, uint32_t* out, gx_stream_t s)
@@ -193,20 +180,10 @@ int gx_identity_hash_32(int dtype, const void* in, const uint32_t* valid, int64_
   if (n < 0) return GX_EINVAL;
   if (n == 0) return 0;
   if (!in || !out) return GX_EINVAL;
-  switch (dtype) {
-    case GX_BOOL8: return gx::identity_launch<uint8_t, true>(in, valid, n, combine, out, s);
-    case GX_INT8: return gx::identity_launch<int8_t>(in, valid, n, combine, out, s);
-    case GX_UINT8: return gx::identity_launch<uint8_t>(in, valid, n, combine, out, s);
-    case GX_INT16: return gx::identity_launch<int16_t>(in, valid, n, combine, out, s);
-    case GX_UINT16: return gx::identity_launch<uint16_t>(in, valid, n, combine, out, s);
-    case GX_INT32: return gx::identity_launch<int32_t>(in, valid, n, combine, out, s);
-    case GX_UINT32: return gx::identity_launch<uint32_t>(in, valid, n, combine, out, s);
-    case GX_INT64: return gx::identity_launch<int64_t>(in, valid, n, combine, out, s);
-    case GX_UINT64: return gx::identity_launch<uint64_t>(in, valid, n, combine, out, s);
-    case GX_FLOAT32: return gx::identity_launch<float>(in, valid, n, combine, out, s);
-    case GX_FLOAT64: return gx::identity_launch<double>(in, valid, n, combine, out, s);
-    default: return GX_EDTYPE;
-  }
+  return gx::with_dtype(dtype, [&](auto t) {
+    using D = decltype(t);
+    return gx::identity_launch<typename D::value_type, D::is_bool>(in, valid, n, combine, out, s);
+  });
 }
 
 int gx_hash_partition_map(const uint32_t* row_hash, int64_t n, int num_partitions, int32_t* out_map,

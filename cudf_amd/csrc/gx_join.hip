@@ -399,11 +399,7 @@ int filter_impl(const void* keys, const uint32_t* valid, int64_t n, const void* 
   Carver c(tmp);
   uint64_t* bits  = c.take<uint64_t>((size_t)div_up(n, (int64_t)GX_WAVE) + 1);
   long long* part = c.take<long long>((size_t)nchunks + 1);
-  if (!tmp) {
-    *tmp_bytes = c.total();
-    return 0;
-  }
-  if (*tmp_bytes < c.total()) return GX_ETMP;
+  if (int rc; !c.ready(tmp_bytes, &rc)) return rc;
   const size_t need = sizeof(TableHeader) + (sizeof(Slot<K>) << lg);
   if (table_bytes < need) return GX_ETMP;
   if (n == 0) {
@@ -4132,11 +4128,7 @@ int partition_rows_hash(const void* keys, int64_t n, int pbits, int nparts, void
 {
   Carver c(tmp);
   PjPlan* plan = c.take<PjPlan>(1);
-  if (!tmp) {
-    *tmp_bytes = c.total();
-    return 0;
-  }
-  if (*tmp_bytes < c.total()) return GX_ETMP;
+  if (int rc; !c.ready(tmp_bytes, &rc)) return rc;
   int rc = pj_partition_fn<K, AltHash<K>>(static_cast<const K*>(keys), n, pbits < 3 ? 3 : pbits, plan, static_cast<K*>(out_keys), out_rows,
                                           PJ_CHUNK, s, AltHash<K>{(unsigned int)nparts}, false, row0, spec_cap);
   if (rc) return rc;
@@ -4151,11 +4143,7 @@ int partition_rows_range(const void* keys, int64_t n, int nparts, const void* sp
 {
   Carver c(tmp);
   PjPlan* plan = c.take<PjPlan>(1);
-  if (!tmp) {
-    *tmp_bytes = c.total();
-    return 0;
-  }
-  if (*tmp_bytes < c.total()) return GX_ETMP;
+  if (int rc; !c.ready(tmp_bytes, &rc)) return rc;
   RangeSplit<K, KIND> f;
   f.nsplit = nparts - 1;
   for (int i = 0; i < PJ_MAX_SPLIT; ++i)
@@ -4219,11 +4207,7 @@ int probe_partitioned_impl2(const K* keys, int64_t n, const Slot<K>* slots, uint
   const unsigned int ovf_cap = (unsigned int)ovf_cap64;
   PjRec* ovf              = longp ? c.take<PjRec>((size_t)ovf_cap * 256) : nullptr;
   unsigned int* ovf_count = longp ? c.take<unsigned int>(OVF_WGS) : nullptr;
-  if (!tmp) {
-    *tmp_bytes = c.total();
-    return 0;
-  }
-  if (*tmp_bytes < c.total()) return GX_ETMP;
+  if (int rc; !c.ready(tmp_bytes, &rc)) return rc;
   typedef TableTop<K> F;
   const F part_of{pbits};
   auto kspec  = k_pj2_scatter<K, 16, 1024, false, F>;
@@ -4381,11 +4365,7 @@ int probe_partitioned_impl(const void* keys, int64_t n, const void* table, size_
   PjPlan* plan   = c.take<PjPlan>(1);
   K* pkeys       = c.take<K>((size_t)n);
   int32_t* pidx  = c.take<int32_t>((size_t)n);
-  if (!tmp) {
-    *tmp_bytes = c.total();
-    return 0;
-  }
-  if (*tmp_bytes < c.total()) return GX_ETMP;
+  if (int rc; !c.ready(tmp_bytes, &rc)) return rc;
   const size_t need = sizeof(TableHeader) + (sizeof(Slot<K>) << lg) + ((size_t)1 << lg) / 2;
   if (table_bytes < need) return GX_ETMP;
   if (n == 0) return 0;
@@ -4447,11 +4427,7 @@ int build_partitioned_impl(const void* keys, int64_t n, void* table, size_t tabl
   int32_t* widx   = windows ? c.take<int32_t>((size_t)n) : nullptr;
   uint32_t* woffs = windows ? c.take<uint32_t>(((size_t)1 << pbits) * (BW_PER + 1)) : nullptr;
   BuildFix2* fix2 = windows ? c.take<BuildFix2>(1) : nullptr;
-  if (!tmp) {
-    *tmp_bytes = c.total();
-    return 0;
-  }
-  if (*tmp_bytes < c.total()) return GX_ETMP;
+  if (int rc; !c.ready(tmp_bytes, &rc)) return rc;
   const size_t need = sizeof(TableHeader) + (sizeof(Slot<K>) << lg) + ((size_t)1 << lg) / 2;
   if (table_bytes < need) return GX_ETMP;
   if (pbits == 0) return GX_EINVAL;
@@ -4872,11 +4848,7 @@ int gx_join_complement(const int32_t* build_idx, int64_t n, int64_t build_rows, 
 {
   if (n < 0 || build_rows < 0 || !tmp_bytes) return GX_EINVAL;
   const size_t need = gx::align_up((size_t)((build_rows + 31) / 32) * 4 + 4, 256);
-  if (!tmp) {
-    *tmp_bytes = need;
-    return 0;
-  }
-  if (*tmp_bytes < need) return GX_ETMP;
+  if (int rc; !gx::scratch_ready(tmp, need, tmp_bytes, &rc)) return rc;
   if (!cursor_dev) return GX_EINVAL;
   GX_HIP_TRY(hipMemsetAsync(tmp, 0, need, s));
   if (n > 0) {

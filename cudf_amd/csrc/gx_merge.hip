@@ -324,11 +324,7 @@ int gx_merge_order(int nkeys, const int* dtypes_host, const void* const* a_cols_
   const Meta m        = fill_meta(nkeys, descending_host, null_before_host);
   const bool nullable = A.has_bitmaps() || B.has_bitmaps();
   const Scratch sc = carve(tmp, n);
-  if (!tmp) {
-    *tmp_bytes = sc.bytes;
-    return 0;
-  }
-  if (*tmp_bytes < sc.bytes) return GX_ETMP;
+  if (int rc; !gx::scratch_ready(tmp, sc.bytes, tmp_bytes, &rc)) return rc;
   if (n == 0) return 0;
   if (!out_map) return GX_EINVAL;
   hipStream_t s = (hipStream_t)stream;

@@ -950,11 +950,7 @@ static int sorted_order_words(const void* keys, int64_t n, int descending, int32
   Layout L;
   int rc = layout(tmp, n, L);
   if (rc) return rc;
-  if (!tmp) {
-    *tmp_bytes = L.total;
-    return 0;
-  }
-  if (*tmp_bytes < L.total) return GX_ETMP;
+  if (int rc; !gx::scratch_ready(tmp, L.total, tmp_bytes, &rc)) return rc;
   if (!keys || !out) return GX_EINVAL;
   const uint64_t* k        = static_cast<const uint64_t*>(keys);
   const uint64_t desc_mask = descending ? ~0ull : 0ull;
@@ -1000,11 +996,7 @@ static int sorted_order_table(int ncols, const int* dtypes, const void* const* c
   Layout L;
   int rc = layout(tmp, n, L, ncols);
   if (rc) return rc;
-  if (!tmp) {
-    *tmp_bytes = L.total;
-    return 0;
-  }
-  if (*tmp_bytes < L.total) return GX_ETMP;
+  if (int rc; !gx::scratch_ready(tmp, L.total, tmp_bytes, &rc)) return rc;
   if (!out || !dtypes || !cols) return GX_EINVAL;
   TableDesc t;
   t.ncols = ncols;

@@ -635,26 +635,6 @@ __global__ void __launch_bounds__(BT) k_lookup(const void* data, const uint32_t*
 }
 
 // ---------------------------------------------------------------- host
-template <typename F>
-inline int with_numeric(int dtype, F&& f)
-{
-  using S = std::integral_constant<int, K_SIGNED>;
-  using N = std::integral_constant<int, K_UNSIGNED>;
-  using D = std::integral_constant<int, K_FLOAT>;
-  switch (dtype) {
-    case GX_INT8: return f(uint8_t{}, S{});
-    case GX_INT16: return f(uint16_t{}, S{});
-    case GX_INT32: return f(uint32_t{}, S{});
-    case GX_INT64: return f(uint64_t{}, S{});
-    case GX_UINT8: return f(uint8_t{}, N{});
-    case GX_UINT16: return f(uint16_t{}, N{});
-    case GX_UINT32: return f(uint32_t{}, N{});
-    case GX_UINT64: return f(uint64_t{}, N{});
-    case GX_FLOAT32: return f(uint32_t{}, D{});
-    case GX_FLOAT64: return f(uint64_t{}, D{});
-    default: return GX_EDTYPE;  // GX_BOOL8 too: a quantile of booleans is not defined
-  }
-}
 inline int unsigned_dtype(int width) { return width == 1 ? GX_UINT8 : width == 2 ? GX_UINT16 : width == 4 ? GX_UINT32 : GX_UINT64; }
 
 inline bool fill_q(QArgs& qa, const double* q_host, int nq)
@@ -752,7 +732,7 @@ int gx_quantile(int dtype, const void* data, const uint32_t* valid, int64_t vali
                 size_t* tmp_bytes, gx_stream_t stream)
 {
   int kind = 0, width = 0;
-  if (dtype == GX_BOOL8 || rows::key_kind_width(dtype, &kind, &width)) return GX_EDTYPE;
+  if (dtype == GX_BOOL8 || rows::key_kind_width(dtype, &kind, &width)) return GX_EDTYPE;  // GX_BOOL8 too: a quantile of booleans is not defined
   if (n < 0 || n >= (int64_t(1) << 31) || !tmp_bytes || !q_host || nq < 1 || nq > MAXQ || valid_begin_bit < 0) return GX_EINVAL;
   if (interp < INTERP_LINEAR || interp > INTERP_NEAREST || mode < GX_QUANTILE_AUTO || mode > GX_QUANTILE_FORCE_SORT) return GX_EINVAL;
   QArgs qa;
@@ -762,20 +742,16 @@ int gx_quantile(int dtype, const void* data, const uint32_t* valid, int64_t vali
     const int rc = carve(tmp, dtype, width, kind, n, valid != nullptr, sc);
     if (rc) return rc;
   }
-  if (!tmp) {
-    *tmp_bytes = sc.bytes;
-    return 0;
-  }
-  if (!out_f64_dev || !nvalid_dev || (n > 0 && !data)) return GX_EINVAL;
-  if (*tmp_bytes < sc.bytes) return GX_ETMP;
+  if (tmp && (!out_f64_dev || !nvalid_dev || (n > 0 && !data))) return GX_EINVAL;
+  if (int rc; !scratch_ready(tmp, sc.bytes, tmp_bytes, &rc)) return rc;
   hipStream_t s = (hipStream_t)stream;
   Device dev;
   GX_HIP_TRY(device(&dev));
   const unsigned grid = capped_grid(n, TILE, (int64_t)dev.cus * 8);
 
-  return with_numeric(dtype, [&](auto utag, auto ktag) -> int {
-    using U            = decltype(utag);
-    constexpr int KIND = decltype(ktag)::value;
+  return with_dtype(dtype, [&](auto t) -> int {
+    using U            = typename decltype(t)::word_type;
+    constexpr int KIND = decltype(t)::kind;
     auto interp_out    = [&](int path) -> int {
       hipLaunchKernelGGL((k_interp<U, KIND>), dim3(1), dim3(MAXQ), 0, s, sc.head, qa, interp, out_f64_dev, static_cast<U*>(out_elems_dev),
                          nvalid_dev);
@@ -861,7 +837,7 @@ int gx_quantile_lookup(int dtype, const void* data, const uint32_t* valid, int64
                        void* out, uint32_t* out_valid, int64_t* out_null_count_dev, gx_stream_t stream)
 {
   int kind = 0, width = 0;
-  if (dtype == GX_BOOL8 || rows::key_kind_width(dtype, &kind, &width)) return GX_EDTYPE;
+  if (dtype == GX_BOOL8 || rows::key_kind_width(dtype, &kind, &width)) return GX_EDTYPE;  // GX_BOOL8 too: a quantile of booleans is not defined
   if (nseg < 0 || !q_host || nq < 1 || nq > MAXQ || begin_bit < 0 || interp < INTERP_LINEAR || interp > INTERP_NEAREST) return GX_EINVAL;
   if (nseg * nq >= (int64_t(1) << 31)) return GX_EINVAL;
   QArgs qa;
@@ -870,9 +846,9 @@ int gx_quantile_lookup(int dtype, const void* data, const uint32_t* valid, int64
   hipStream_t s = (hipStream_t)stream;
   if (out_null_count_dev) GX_HIP_TRY(hipMemsetAsync(out_null_count_dev, 0, sizeof(int64_t), s));
   if (nseg == 0) return 0;
-  return with_numeric(dtype, [&](auto utag, auto ktag) -> int {
-    using U            = decltype(utag);
-    constexpr int KIND = decltype(ktag)::value;
+  return with_dtype(dtype, [&](auto t) -> int {
+    using U            = typename decltype(t)::word_type;
+    constexpr int KIND = decltype(t)::kind;
     hipLaunchKernelGGL((k_lookup<U, KIND>), dim3(capped_grid(nseg * nq, BT, 4096)), dim3(BT), 0, s, data, valid, begin_bit, order, nseg,
                        offsets_dev, seg_counts_dev, qa, interp, exact ? 1 : 0, out, out_valid,
                        reinterpret_cast<unsigned long long*>(out_null_count_dev));

@@ -246,11 +246,7 @@ int gx_dense_rank(int dtype, const void* keys, const uint32_t* valid, int64_t n,
   int32_t* order = c.take<int32_t>((size_t)n + 1);
   int32_t* flags = c.take<int32_t>((size_t)n + 1);
   char* sub      = c.take<char>(sort_bytes > scan_bytes ? sort_bytes : scan_bytes);
-  if (!tmp) {
-    *tmp_bytes = c.total();
-    return 0;
-  }
-  if (*tmp_bytes < c.total()) return GX_ETMP;
+  if (int rc; !c.ready(tmp_bytes, &rc)) return rc;
   if (!out_ids && n > 0) return GX_EINVAL;
   if (n == 0) {
     if (out_ngroups_dev) GX_HIP_TRY(hipMemsetAsync(out_ngroups_dev, 0, sizeof(int64_t), s));

@@ -75,18 +75,8 @@ struct Seg {
   T v;
   uint32_t f;  // 1 = this element starts a new key run
   uint32_t pad;
-  __host__ __device__ explicit operator double() const { return (double)v; }
-  __host__ __device__ explicit operator float() const { return (float)v; }
-  __host__ __device__ explicit operator long long() const { return (long long)v; }
-  __host__ __device__ explicit operator long() const { return (long)v; }
-  __host__ __device__ explicit operator int() const { return (int)v; }
-  __host__ __device__ explicit operator short() const { return (short)v; }
-  __host__ __device__ explicit operator signed char() const { return (signed char)v; }
-  __host__ __device__ explicit operator unsigned long long() const { return (unsigned long long)v; }
-  __host__ __device__ explicit operator unsigned long() const { return (unsigned long)v; }
-  __host__ __device__ explicit operator unsigned int() const { return (unsigned int)v; }
-  __host__ __device__ explicit operator unsigned short() const { return (unsigned short)v; }
-  __host__ __device__ explicit operator unsigned char() const { return (unsigned char)v; }
+  template <typename X>
+  __host__ __device__ explicit operator X() const { return (X)v; }
 };
 template <typename T, typename Op>
 struct SegOp {
@@ -131,20 +121,10 @@ int heads_launch(const void* keys, int64_t n, uint8_t* heads, hipStream_t s)
 
 static int heads_dispatch(int key_dtype, const void* keys, int64_t n, uint8_t* heads, hipStream_t s)
 {
-  switch (key_dtype) {
-    case GX_INT8: return heads_launch<uint8_t, K_SIGNED>(keys, n, heads, s);
-    case GX_BOOL8:
-    case GX_UINT8: return heads_launch<uint8_t, K_UNSIGNED>(keys, n, heads, s);
-    case GX_INT16: return heads_launch<uint16_t, K_SIGNED>(keys, n, heads, s);
-    case GX_UINT16: return heads_launch<uint16_t, K_UNSIGNED>(keys, n, heads, s);
-    case GX_INT32: return heads_launch<uint32_t, K_SIGNED>(keys, n, heads, s);
-    case GX_UINT32: return heads_launch<uint32_t, K_UNSIGNED>(keys, n, heads, s);
-    case GX_FLOAT32: return heads_launch<uint32_t, K_FLOAT>(keys, n, heads, s);
-    case GX_INT64: return heads_launch<uint64_t, K_SIGNED>(keys, n, heads, s);
-    case GX_UINT64: return heads_launch<uint64_t, K_UNSIGNED>(keys, n, heads, s);
-    case GX_FLOAT64: return heads_launch<uint64_t, K_FLOAT>(keys, n, heads, s);
-    default: return GX_EDTYPE;
-  }
+  return with_dtype(key_dtype, [&](auto t) {
+    using D = decltype(t);
+    return heads_launch<typename D::word_type, D::kind>(keys, n, heads, s);
+  });
 }
 
 // ---------------------------------------------------------------- identities
@@ -198,23 +178,26 @@ __global__ void k_store_result<FloatMin>(const FloatMin* res, int out_dtype, voi
   store_as<double>(static_cast<double>(*res), out_dtype, out);
 }
 
-template <typename InT, typename AccT, typename Op>
-int reduce_typed(const void* in, const uint32_t* valid, int64_t n, AccT identity, Op op, int out_dtype, void* out,
-                 void* tmp, size_t* tmp_bytes, hipStream_t s)
+// one reduction of the loader's elements: partials in the scratch, the result stored as out_dtype
+template <typename AccT, typename Loader, typename Op>
+int reduce_with(Loader ld, int64_t n, AccT identity, Op op, int out_dtype, void* out, void* tmp, size_t* tmp_bytes, hipStream_t s)
 {
   Carver c(tmp);
   AccT* partials = c.take<AccT>(scan::partials_count(n));
-  if (!tmp) {
-    *tmp_bytes = c.total();
-    return 0;
-  }
-  if (*tmp_bytes < c.total()) return GX_ETMP;
-  scan::PlainLoader<InT, AccT> ld{static_cast<const InT*>(in), valid, identity};
+  if (int rc; !c.ready(tmp_bytes, &rc)) return rc;
   int rc = scan::device_reduce<AccT>(ld, n, identity, op, partials, s);
   if (rc) return rc;
   hipLaunchKernelGGL((k_store_result<AccT>), dim3(1), dim3(1), 0, s, partials + scan::reduce_blocks(n), out_dtype, out);
   GX_LAUNCH_CHECK();
   return 0;
+}
+// ... of the column's values as AccT, a null being the identity
+template <typename InT, typename AccT, typename Op>
+int reduce_typed(const void* in, const uint32_t* valid, int64_t n, AccT identity, Op op, int out_dtype, void* out,
+                 void* tmp, size_t* tmp_bytes, hipStream_t s)
+{
+  return reduce_with<AccT>(scan::PlainLoader<InT, AccT>{static_cast<const InT*>(in), valid, identity}, n, identity, op, out_dtype, out,
+                           tmp, tmp_bytes, s);
 }
 
 // number of valid elements that are not zero (a NaN is not zero): what cudf::reduce ANY / ALL need -- the reference reduces
@@ -232,38 +215,8 @@ struct NonZeroLoader {
 template <typename InT>
 int reduce_nonzero(const void* in, const uint32_t* valid, int64_t n, int out_dtype, void* out, void* tmp, size_t* tmp_bytes, hipStream_t s)
 {
-  Carver c(tmp);
-  uint64_t* partials = c.take<uint64_t>(scan::partials_count(n));
-  if (!tmp) {
-    *tmp_bytes = c.total();
-    return 0;
-  }
-  if (*tmp_bytes < c.total()) return GX_ETMP;
-  NonZeroLoader<InT> ld{static_cast<const InT*>(in), valid};
-  int rc = scan::device_reduce<uint64_t>(ld, n, uint64_t(0), SumOp(), partials, s);
-  if (rc) return rc;
-  hipLaunchKernelGGL((k_store_result<uint64_t>), dim3(1), dim3(1), 0, s, partials + scan::reduce_blocks(n), out_dtype, out);
-  GX_LAUNCH_CHECK();
-  return 0;
-}
-
-template <typename InT>
-int reduce_dd(const void* in, const uint32_t* valid, int64_t n, int out_dtype, void* out, void* tmp,
-              size_t* tmp_bytes, hipStream_t s)
-{
-  Carver c(tmp);
-  DD* partials = c.take<DD>(scan::partials_count(n));
-  if (!tmp) {
-    *tmp_bytes = c.total();
-    return 0;
-  }
-  if (*tmp_bytes < c.total()) return GX_ETMP;
-  DDLoader<InT> ld{static_cast<const InT*>(in), valid};
-  int rc = scan::device_reduce<DD>(ld, n, DD{0.0, 0.0}, DDSum(), partials, s);
-  if (rc) return rc;
-  hipLaunchKernelGGL((k_store_result<DD>), dim3(1), dim3(1), 0, s, partials + scan::reduce_blocks(n), out_dtype, out);
-  GX_LAUNCH_CHECK();
-  return 0;
+  return reduce_with<uint64_t>(NonZeroLoader<InT>{static_cast<const InT*>(in), valid}, n, uint64_t(0), SumOp(), out_dtype, out, tmp,
+                               tmp_bytes, s);
 }
 
 // integers: SUM/PRODUCT in uint64 (wrap == two's complement), MIN/MAX in int64 or uint64
@@ -286,7 +239,7 @@ int reduce_float(const void* in, const uint32_t* valid, int64_t n, int op, int o
                  size_t* tmp_bytes, hipStream_t s)
 {
   switch (op) {
-    case GX_OP_SUM: return reduce_dd<InT>(in, valid, n, out_dtype, out, tmp, tmp_bytes, s);
+    case GX_OP_SUM: return reduce_with<DD>(DDLoader<InT>{static_cast<const InT*>(in), valid}, n, DD{0.0, 0.0}, DDSum(), out_dtype, out, tmp, tmp_bytes, s);
     case GX_OP_PRODUCT: return reduce_typed<InT, double>(in, valid, n, 1.0, ProdOp(), out_dtype, out, tmp, tmp_bytes, s);
     case GX_OP_MIN: return reduce_typed<InT, FloatMin>(in, valid, n, FloatMin::empty(), FloatMinOp(), out_dtype, out, tmp, tmp_bytes, s);
     case GX_OP_MAX: return reduce_typed<InT, double>(in, valid, n, Limits<double>::lowest(), FloatMaxOp(), out_dtype, out, tmp, tmp_bytes, s);
@@ -296,33 +249,14 @@ int reduce_float(const void* in, const uint32_t* valid, int64_t n, int op, int o
 }
 
 // ---------------------------------------------------------------- column scan
-template <typename InT, typename AccT, typename Op>
-int scan_typed(const void* in, const uint32_t* valid, int64_t n, AccT identity, Op op, int inclusive, void* out,
-               void* tmp, size_t* tmp_bytes, hipStream_t s)
+// one scan of the loader's elements into a column of InT: partials in the scratch
+template <typename InT, typename AccT, typename Loader, typename Op>
+int scan_with(Loader ld, int64_t n, AccT identity, Op op, int inclusive, void* out, void* tmp, size_t* tmp_bytes, hipStream_t s)
 {
   Carver c(tmp);
   AccT* partials = c.take<AccT>(scan::partials_count(n));
-  if (!tmp) {
-    *tmp_bytes = c.total();
-    return 0;
-  }
-  if (*tmp_bytes < c.total()) return GX_ETMP;
-  scan::PlainLoader<InT, AccT> ld{static_cast<const InT*>(in), valid, identity};
+  if (int rc; !c.ready(tmp_bytes, &rc)) return rc;
   return scan::device_scan<AccT, InT>(ld, n, identity, op, inclusive != 0, static_cast<InT*>(out), partials, s);
-}
-template <typename InT>
-int scan_dd(const void* in, const uint32_t* valid, int64_t n, int inclusive, void* out, void* tmp, size_t* tmp_bytes,
-            hipStream_t s)
-{
-  Carver c(tmp);
-  DD* partials = c.take<DD>(scan::partials_count(n));
-  if (!tmp) {
-    *tmp_bytes = c.total();
-    return 0;
-  }
-  if (*tmp_bytes < c.total()) return GX_ETMP;
-  DDLoader<InT> ld{static_cast<const InT*>(in), valid};
-  return scan::device_scan<DD, InT>(ld, n, DD{0.0, 0.0}, DDSum(), inclusive != 0, static_cast<InT*>(out), partials, s);
 }
 // exact commutative operators: the single-pass look-back scan (16 B/row)
 template <typename InT, typename AccT, typename Op>
@@ -331,11 +265,7 @@ int scan_lookback(const void* in, const uint32_t* valid, int64_t n, AccT identit
 {
   Carver c(tmp);
   char* scratch = c.take<char>(scan::lookback_bytes(n));
-  if (!tmp) {
-    *tmp_bytes = c.total();
-    return 0;
-  }
-  if (*tmp_bytes < c.total()) return GX_ETMP;
+  if (int rc; !c.ready(tmp_bytes, &rc)) return rc;
   scan::PlainLoader<InT, AccT> ld{static_cast<const InT*>(in), valid, identity};
   return scan::device_scan_lookback<AccT, InT>(ld, n, identity, op, inclusive != 0, static_cast<InT*>(out), scratch, s);
 }
@@ -357,8 +287,8 @@ int scan_float(const void* in, const uint32_t* valid, int64_t n, int op, int inc
                size_t* tmp_bytes, hipStream_t s)
 {
   switch (op) {
-    case GX_OP_SUM: return scan_dd<InT>(in, valid, n, inclusive, out, tmp, tmp_bytes, s);
-    case GX_OP_PRODUCT: return scan_typed<InT, double>(in, valid, n, 1.0, ProdOp(), inclusive, out, tmp, tmp_bytes, s);
+    case GX_OP_SUM: return scan_with<InT, DD>(DDLoader<InT>{static_cast<const InT*>(in), valid}, n, DD{0.0, 0.0}, DDSum(), inclusive, out, tmp, tmp_bytes, s);
+    case GX_OP_PRODUCT: return scan_with<InT, double>(scan::PlainLoader<InT, double>{static_cast<const InT*>(in), valid, 1.0}, n, 1.0, ProdOp(), inclusive, out, tmp, tmp_bytes, s);
     case GX_OP_MIN: return scan_lookback<InT, FloatMin>(in, valid, n, FloatMin::empty(), FloatMinOp(), inclusive, out, tmp, tmp_bytes, s);
     case GX_OP_MAX: return scan_lookback<InT, double>(in, valid, n, Limits<double>::lowest(), FloatMaxOp(), inclusive, out, tmp, tmp_bytes, s);
     default: return GX_EINVAL;
@@ -568,20 +498,12 @@ int gx_reduce(int in_dtype, const void* in, const uint32_t* valid, int64_t n, in
       hipLaunchKernelGGL(gx::rs::k_set_i64, dim3(1), dim3(1), 0, s, valid_count_dev, n);
     }
   }
-  switch (in_dtype) {
-    case GX_INT8: return reduce_int<int8_t, true>(in, valid, n, op, out_dtype, out_dev, tmp, tmp_bytes, s);
-    case GX_INT16: return reduce_int<int16_t, true>(in, valid, n, op, out_dtype, out_dev, tmp, tmp_bytes, s);
-    case GX_INT32: return reduce_int<int32_t, true>(in, valid, n, op, out_dtype, out_dev, tmp, tmp_bytes, s);
-    case GX_INT64: return reduce_int<int64_t, true>(in, valid, n, op, out_dtype, out_dev, tmp, tmp_bytes, s);
-    case GX_BOOL8:
-    case GX_UINT8: return reduce_int<uint8_t, false>(in, valid, n, op, out_dtype, out_dev, tmp, tmp_bytes, s);
-    case GX_UINT16: return reduce_int<uint16_t, false>(in, valid, n, op, out_dtype, out_dev, tmp, tmp_bytes, s);
-    case GX_UINT32: return reduce_int<uint32_t, false>(in, valid, n, op, out_dtype, out_dev, tmp, tmp_bytes, s);
-    case GX_UINT64: return reduce_int<uint64_t, false>(in, valid, n, op, out_dtype, out_dev, tmp, tmp_bytes, s);
-    case GX_FLOAT32: return reduce_float<float>(in, valid, n, op, out_dtype, out_dev, tmp, tmp_bytes, s);
-    case GX_FLOAT64: return reduce_float<double>(in, valid, n, op, out_dtype, out_dev, tmp, tmp_bytes, s);
-    default: return GX_EDTYPE;
-  }
+  return gx::with_dtype(in_dtype, [&](auto t) {
+    using D = decltype(t);
+    using T = typename D::value_type;
+    if constexpr (D::kind == gx::K_FLOAT) return reduce_float<T>(in, valid, n, op, out_dtype, out_dev, tmp, tmp_bytes, s);
+    else return reduce_int<T, D::kind == gx::K_SIGNED>(in, valid, n, op, out_dtype, out_dev, tmp, tmp_bytes, s);
+  });
 }
 
 int gx_scan(int dtype, const void* in, const uint32_t* valid, int64_t n, int op, int inclusive, void* out, void* tmp,
@@ -590,20 +512,12 @@ int gx_scan(int dtype, const void* in, const uint32_t* valid, int64_t n, int op,
   using namespace gx::rs;
   if (n < 0 || !tmp_bytes) return GX_EINVAL;
   if (tmp && n > 0 && (!in || !out)) return GX_EINVAL;
-  switch (dtype) {
-    case GX_INT8: return scan_int<int8_t, true>(in, valid, n, op, inclusive, out, tmp, tmp_bytes, s);
-    case GX_INT16: return scan_int<int16_t, true>(in, valid, n, op, inclusive, out, tmp, tmp_bytes, s);
-    case GX_INT32: return scan_int<int32_t, true>(in, valid, n, op, inclusive, out, tmp, tmp_bytes, s);
-    case GX_INT64: return scan_int<int64_t, true>(in, valid, n, op, inclusive, out, tmp, tmp_bytes, s);
-    case GX_BOOL8:
-    case GX_UINT8: return scan_int<uint8_t, false>(in, valid, n, op, inclusive, out, tmp, tmp_bytes, s);
-    case GX_UINT16: return scan_int<uint16_t, false>(in, valid, n, op, inclusive, out, tmp, tmp_bytes, s);
-    case GX_UINT32: return scan_int<uint32_t, false>(in, valid, n, op, inclusive, out, tmp, tmp_bytes, s);
-    case GX_UINT64: return scan_int<uint64_t, false>(in, valid, n, op, inclusive, out, tmp, tmp_bytes, s);
-    case GX_FLOAT32: return scan_float<float>(in, valid, n, op, inclusive, out, tmp, tmp_bytes, s);
-    case GX_FLOAT64: return scan_float<double>(in, valid, n, op, inclusive, out, tmp, tmp_bytes, s);
-    default: return GX_EDTYPE;
-  }
+  return gx::with_dtype(dtype, [&](auto t) {
+    using D = decltype(t);
+    using T = typename D::value_type;
+    if constexpr (D::kind == gx::K_FLOAT) return scan_float<T>(in, valid, n, op, inclusive, out, tmp, tmp_bytes, s);
+    else return scan_int<T, D::kind == gx::K_SIGNED>(in, valid, n, op, inclusive, out, tmp, tmp_bytes, s);
+  });
 }
 
 int gx_segmented_scan(int key_dtype, const void* sorted_keys, int val_dtype, const void* vals,
@@ -615,31 +529,19 @@ int gx_segmented_scan(int key_dtype, const void* sorted_keys, int val_dtype, con
   gx::Carver c(tmp);
   uint8_t* heads = c.take<uint8_t>((size_t)n);
   char* partials = c.take<char>(gx::scan::partials_count(n) * sizeof(Seg<double>));
-  if (!tmp) {
-    *tmp_bytes = c.total();
-    return 0;
-  }
-  if (*tmp_bytes < c.total()) return GX_ETMP;
+  if (int rc; !c.ready(tmp_bytes, &rc)) return rc;
   if (n == 0) return 0;
   const bool counting = op == GX_OP_COUNT_VALID || op == GX_OP_COUNT_ALL;
   if (!sorted_keys || (!vals && !counting) || !out) return GX_EINVAL;
   int rc = heads_dispatch(key_dtype, sorted_keys, n, heads, s);
   if (rc) return rc;
   if (counting) return seg_count(op == GX_OP_COUNT_ALL ? nullptr : vals_valid, heads, n, out, partials, s);
-  switch (val_dtype) {
-    case GX_INT8: return seg_int<int8_t, true>(vals, vals_valid, heads, n, op, out, partials, s);
-    case GX_INT16: return seg_int<int16_t, true>(vals, vals_valid, heads, n, op, out, partials, s);
-    case GX_INT32: return seg_int<int32_t, true>(vals, vals_valid, heads, n, op, out, partials, s);
-    case GX_INT64: return seg_int<int64_t, true>(vals, vals_valid, heads, n, op, out, partials, s);
-    case GX_BOOL8:
-    case GX_UINT8: return seg_int<uint8_t, false>(vals, vals_valid, heads, n, op, out, partials, s);
-    case GX_UINT16: return seg_int<uint16_t, false>(vals, vals_valid, heads, n, op, out, partials, s);
-    case GX_UINT32: return seg_int<uint32_t, false>(vals, vals_valid, heads, n, op, out, partials, s);
-    case GX_UINT64: return seg_int<uint64_t, false>(vals, vals_valid, heads, n, op, out, partials, s);
-    case GX_FLOAT32: return seg_float<float>(vals, vals_valid, heads, n, op, out, partials, s);
-    case GX_FLOAT64: return seg_float<double>(vals, vals_valid, heads, n, op, out, partials, s);
-    default: return GX_EDTYPE;
-  }
+  return gx::with_dtype(val_dtype, [&](auto t) {
+    using D = decltype(t);
+    using T = typename D::value_type;
+    if constexpr (D::kind == gx::K_FLOAT) return seg_float<T>(vals, vals_valid, heads, n, op, out, partials, s);
+    else return seg_int<T, D::kind == gx::K_SIGNED>(vals, vals_valid, heads, n, op, out, partials, s);
+  });
 }
 
 /* see gx.h */
@@ -650,11 +552,7 @@ int gx_segmented_reduce(int val_dtype, const void* vals, const uint32_t* vals_va
   if (n < 0 || !tmp_bytes) return GX_EINVAL;
   gx::Carver c(tmp);
   char* partials = c.take<char>(gx::scan::partials_count(n) * sizeof(SegC<DD>));
-  if (!tmp) {
-    *tmp_bytes = c.total();
-    return 0;
-  }
-  if (*tmp_bytes < c.total()) return GX_ETMP;
+  if (int rc; !c.ready(tmp_bytes, &rc)) return rc;
   if (n == 0) return 0;
   if (!heads || !labels || (!out && !out_count_valid)) return GX_EINVAL;
   if (op == GX_OP_COUNT_VALID) {
@@ -663,20 +561,12 @@ int gx_segmented_reduce(int val_dtype, const void* vals, const uint32_t* vals_va
     return segreduce_int<int32_t, true>(nullptr, vals_valid, heads, labels, n, op, nullptr, out_count_valid, partials, s);
   }
   if (!vals) return GX_EINVAL;
-  switch (val_dtype) {
-    case GX_INT8: return segreduce_int<int8_t, true>(vals, vals_valid, heads, labels, n, op, out, out_count_valid, partials, s);
-    case GX_INT16: return segreduce_int<int16_t, true>(vals, vals_valid, heads, labels, n, op, out, out_count_valid, partials, s);
-    case GX_INT32: return segreduce_int<int32_t, true>(vals, vals_valid, heads, labels, n, op, out, out_count_valid, partials, s);
-    case GX_INT64: return segreduce_int<int64_t, true>(vals, vals_valid, heads, labels, n, op, out, out_count_valid, partials, s);
-    case GX_BOOL8:
-    case GX_UINT8: return segreduce_int<uint8_t, false>(vals, vals_valid, heads, labels, n, op, out, out_count_valid, partials, s);
-    case GX_UINT16: return segreduce_int<uint16_t, false>(vals, vals_valid, heads, labels, n, op, out, out_count_valid, partials, s);
-    case GX_UINT32: return segreduce_int<uint32_t, false>(vals, vals_valid, heads, labels, n, op, out, out_count_valid, partials, s);
-    case GX_UINT64: return segreduce_int<uint64_t, false>(vals, vals_valid, heads, labels, n, op, out, out_count_valid, partials, s);
-    case GX_FLOAT32: return segreduce_float<float>(vals, vals_valid, heads, labels, n, op, out, out_count_valid, partials, s);
-    case GX_FLOAT64: return segreduce_float<double>(vals, vals_valid, heads, labels, n, op, out, out_count_valid, partials, s);
-    default: return GX_EDTYPE;
-  }
+  return gx::with_dtype(val_dtype, [&](auto t) {
+    using D = decltype(t);
+    using T = typename D::value_type;
+    if constexpr (D::kind == gx::K_FLOAT) return segreduce_float<T>(vals, vals_valid, heads, labels, n, op, out, out_count_valid, partials, s);
+    else return segreduce_int<T, D::kind == gx::K_SIGNED>(vals, vals_valid, heads, labels, n, op, out, out_count_valid, partials, s);
+  });
 }
 
 }  // extern "C"

@@ -484,11 +484,7 @@ int gx_replace_nulls_policy(int elem_size, const void* in, const uint32_t* in_va
   gx::Carver cv(tmp);
   int32_t* table = cv.take<int32_t>((size_t)tiles);
   int32_t* top   = cv.take<int32_t>((size_t)blocks);
-  if (!tmp) {
-    *tmp_bytes = cv.total();
-    return 0;
-  }
-  if (*tmp_bytes < cv.total()) return GX_ETMP;
+  if (int rc; !cv.ready(tmp_bytes, &rc)) return rc;
   if (n == 0) return 0;
   if (!in || !in_valid || !out || !out_valid) return GX_EINVAL;
   if (out_null_count_dev) GX_HIP_TRY(hipMemsetAsync(out_null_count_dev, 0, sizeof(int64_t), s));
@@ -545,27 +541,15 @@ int gx_clamp(int dtype, const void* in, int64_t n, const void* lo, const uint8_t
   if (!dtype_ok(dtype)) return GX_EDTYPE;
   if (n == 0) return 0;
   if (!in || !out) return GX_EINVAL;
-#define GX_CLAMP_GO(T, ISBOOL)                                                                                                          \
-  hipLaunchKernelGGL((k_clamp<T, ISBOOL>), dim3(tile_grid(n)), dim3(BT), 0, s, static_cast<const T*>(in), n, static_cast<const T*>(lo), \
-                     lo_valid_dev, static_cast<const T*>(lo_replace), static_cast<const T*>(hi), hi_valid_dev,                          \
-                     static_cast<const T*>(hi_replace), static_cast<T*>(out));                                                          \
-  break
-  switch (dtype) {
-    case GX_INT8: GX_CLAMP_GO(int8_t, false);
-    case GX_INT16: GX_CLAMP_GO(int16_t, false);
-    case GX_INT32: GX_CLAMP_GO(int32_t, false);
-    case GX_INT64: GX_CLAMP_GO(int64_t, false);
-    case GX_UINT8: GX_CLAMP_GO(uint8_t, false);
-    case GX_UINT16: GX_CLAMP_GO(uint16_t, false);
-    case GX_UINT32: GX_CLAMP_GO(uint32_t, false);
-    case GX_UINT64: GX_CLAMP_GO(uint64_t, false);
-    case GX_FLOAT32: GX_CLAMP_GO(float, false);
-    case GX_FLOAT64: GX_CLAMP_GO(double, false);
-    default: GX_CLAMP_GO(uint8_t, true);
-  }
-#undef GX_CLAMP_GO
-  GX_LAUNCH_CHECK();
-  return 0;
+  return gx::with_dtype(dtype, [&](auto t) {
+    using D = decltype(t);
+    using T = typename D::value_type;
+    hipLaunchKernelGGL((k_clamp<T, D::is_bool>), dim3(tile_grid(n)), dim3(BT), 0, s, static_cast<const T*>(in), n, static_cast<const T*>(lo),
+                       lo_valid_dev, static_cast<const T*>(lo_replace), static_cast<const T*>(hi), hi_valid_dev,
+                       static_cast<const T*>(hi_replace), static_cast<T*>(out));
+    GX_LAUNCH_CHECK();
+    return 0;
+  });
 }
 
 int gx_find_and_replace(int dtype, const void* in, const uint32_t* in_valid, int64_t in_begin_bit, int64_t n, const void* old_vals,
@@ -580,21 +564,14 @@ int gx_find_and_replace(int dtype, const void* in, const uint32_t* in_valid, int
   if (!out_valid && (in_valid || (m > 0 && new_valid))) return GX_EINVAL;
   if (out_null_count_dev) GX_HIP_TRY(hipMemsetAsync(out_null_count_dev, 0, sizeof(int64_t), s));
   unsigned long long* nulls = out_valid ? reinterpret_cast<unsigned long long*>(out_null_count_dev) : nullptr;
-#define GX_FR_GO(T)                                                                                                                   \
-  hipLaunchKernelGGL((k_find_replace<T>), dim3(tile_grid(n)), dim3(BT), 0, s, static_cast<const T*>(in), in_valid, in_begin_bit, n,   \
-                     static_cast<const T*>(old_vals), static_cast<const T*>(new_vals), new_valid, new_begin_bit, m, static_cast<T*>(out), \
-                     out_valid, nulls)
-  if (dtype == GX_FLOAT32) GX_FR_GO(float);
-  else if (dtype == GX_FLOAT64) GX_FR_GO(double);
-  else switch (gx_dtype_size(dtype)) {
-    case 1: GX_FR_GO(uint8_t); break;
-    case 2: GX_FR_GO(uint16_t); break;
-    case 4: GX_FR_GO(uint32_t); break;
-    default: GX_FR_GO(uint64_t); break;
-  }
-#undef GX_FR_GO
-  GX_LAUNCH_CHECK();
-  return 0;
+  return gx::with_dtype(dtype, [&](auto t) {  // integers match by their bits whatever their sign, floats by value
+    using T = gx::word_or_float_t<decltype(t)>;
+    hipLaunchKernelGGL((k_find_replace<T>), dim3(tile_grid(n)), dim3(BT), 0, s, static_cast<const T*>(in), in_valid, in_begin_bit, n,
+                       static_cast<const T*>(old_vals), static_cast<const T*>(new_vals), new_valid, new_begin_bit, m, static_cast<T*>(out),
+                       out_valid, nulls);
+    GX_LAUNCH_CHECK();
+    return 0;
+  });
 }
 
 int gx_normalize_nans_and_zeros(int dtype, const void* in, int64_t n, void* out, gx_stream_t s)

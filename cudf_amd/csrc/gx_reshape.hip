@@ -464,11 +464,7 @@ int gx_interleave(int elem_size, int ncols, const void* const* cols_host, const 
   const char** src       = cv.take<const char*>((size_t)ncols);
   const uint32_t** valid = cv.take<const uint32_t*>((size_t)ncols);
   long long* bbit        = cv.take<long long>((size_t)ncols);
-  if (!tmp) {
-    *tmp_bytes = cv.total();
-    return 0;
-  }
-  if (*tmp_bytes < cv.total()) return GX_ETMP;
+  if (int rc; !cv.ready(tmp_bytes, &rc)) return rc;
   if (nrows < 0 || nrows > gx::RS_MAX || nrows > gx::RS_MAX / ncols || !cols_host) return GX_EINVAL;
   for (int j = 0; j < ncols; ++j) {
     if (nrows > 0 && !cols_host[j]) return GX_EINVAL;
@@ -530,10 +526,7 @@ int gx_repeat_each(int elem_size, const void* in, const uint32_t* in_valid, int6
 int gx_repeat_map(const int32_t* offsets_dev, int64_t nrows, int64_t total, int32_t* out_map, void* tmp, size_t* tmp_bytes, gx_stream_t s)
 {
   if (!tmp_bytes) return GX_EINVAL;
-  if (!tmp) {
-    *tmp_bytes = 0;
-    return 0;
-  }
+  if (int rc; !gx::scratch_ready(tmp, 0, tmp_bytes, &rc)) return rc;  // no scratch: the query answers 0
   if (nrows < 0 || nrows > gx::RS_MAX || total < 0 || total > gx::RS_MAX || (total > 0 && nrows == 0)) return GX_EINVAL;
   if (total == 0) return 0;
   if (!offsets_dev || !out_map) return GX_EINVAL;
@@ -565,18 +558,9 @@ int gx_sequence(int dtype, void* out, int64_t n, const void* init_dev, const voi
   if (n < 0 || n > gx::RS_MAX) return GX_EINVAL;
   if (n == 0) return 0;
   if (!out || !init_dev) return GX_EINVAL;
-  switch (dtype) {
-    case GX_INT8:
-    case GX_UINT8: return gx::sequence_launch<uint8_t>(out, n, init_dev, step_dev, s);
-    case GX_INT16:
-    case GX_UINT16: return gx::sequence_launch<uint16_t>(out, n, init_dev, step_dev, s);
-    case GX_INT32:
-    case GX_UINT32: return gx::sequence_launch<uint32_t>(out, n, init_dev, step_dev, s);
-    case GX_INT64:
-    case GX_UINT64: return gx::sequence_launch<uint64_t>(out, n, init_dev, step_dev, s);
-    case GX_FLOAT32: return gx::sequence_launch<float>(out, n, init_dev, step_dev, s);
-    default: return gx::sequence_launch<double>(out, n, init_dev, step_dev, s);
-  }
+  return gx::with_dtype(dtype, [&](auto t) {  // integers wrap: one kernel per width, the unsigned one
+    return gx::sequence_launch<gx::word_or_float_t<decltype(t)>>(out, n, init_dev, step_dev, s);
+  });
 }
 
 }  // extern "C"

@@ -113,17 +113,15 @@ struct Cols {
   }
 };
 
-// ---- host: the one dtype switch, and the argument rules of every call that takes key columns
+// ---- host: a dtype's row of the table (gx_dtype.hpp) as the runtime values Cols carries, and the argument rules of every call
+// that takes key columns
 inline int key_kind_width(int dtype, int* kind, int* width)
 {
-  switch (dtype) {
-    case GX_INT8: case GX_INT16: case GX_INT32: case GX_INT64: *kind = K_SIGNED; break;
-    case GX_UINT8: case GX_UINT16: case GX_UINT32: case GX_UINT64: case GX_BOOL8: *kind = K_UNSIGNED; break;
-    case GX_FLOAT32: case GX_FLOAT64: *kind = K_FLOAT; break;
-    default: return GX_EDTYPE;
-  }
-  *width = gx_dtype_size(dtype);
-  return 0;
+  return with_dtype(dtype, [&](auto t) {
+    *kind  = decltype(t)::kind;
+    *width = (int)sizeof(typename decltype(t)::word_type);
+    return 0;
+  });
 }
 
 // Fills `c` from the host arrays of a call: 1 <= nkeys <= N and `dtypes` are demanded, an unknown dtype is GX_EDTYPE, `bits` (NULL =

@@ -4073,11 +4073,7 @@ int sort_impl(const void* keys_in, void* keys_out, const int32_t* vals_in, int32
   S.level0            = fc.on ? c.take<KeyT>(S.level0_rows) : nullptr;
   KeyT* ka_scratch    = keys_out ? nullptr : c.take<KeyT>((size_t)n);
   uint32_t* vb        = HAS_VAL ? c.take<uint32_t>(nb_buf) : nullptr;
-  if (tmp == nullptr) {
-    *tmp_bytes = c.total();
-    return 0;
-  }
-  if (*tmp_bytes < c.total()) return GX_ETMP;
+  if (int rc; !c.ready(tmp_bytes, &rc)) return rc;
   if (n > 0 && (keys_in == nullptr || (HAS_VAL && vals_out == nullptr))) return GX_EINVAL;
   if (n > 0 && keys_in == keys_out) return GX_EINVAL;
 
@@ -4392,11 +4388,7 @@ template <typename KeyT, int KIND>
 int sortx_sample(const void* keys, int64_t n, int64_t recv_rows_max, void* tmp, size_t* tmp_bytes, hipStream_t stream)
 {
   auto L = sortx_layout<KeyT>(tmp, n, recv_rows_max);
-  if (!tmp) {
-    *tmp_bytes = L.total;
-    return 0;
-  }
-  if (*tmp_bytes < L.total) return GX_ETMP;
+  if (int rc; !gx::scratch_ready(tmp, L.total, tmp_bytes, &rc)) return rc;
   const CursorCfg cs = sortx_cfg(n);
   GX_HIP_TRY(hipMemsetAsync(L.plan, 0, sizeof(SortPlan), stream));
   GX_HIP_TRY(hipMemsetAsync(L.hist2, 0, CELL_TABLE_BYTES, stream));
@@ -4499,20 +4491,10 @@ template <bool HAS_VAL>
 int dispatch(int dtype, const void* keys_in, void* keys_out, const int32_t* vals_in, int32_t* vals_out,
              int64_t n, int descending, bool radix_nan_rule, void* tmp, size_t* tmp_bytes, hipStream_t s)
 {
-  switch (dtype) {
-    case GX_INT8: return sort_impl<uint8_t, K_SIGNED, HAS_VAL>(keys_in, keys_out, vals_in, vals_out, n, descending, radix_nan_rule, tmp, tmp_bytes, s);
-    case GX_BOOL8:
-    case GX_UINT8: return sort_impl<uint8_t, K_UNSIGNED, HAS_VAL>(keys_in, keys_out, vals_in, vals_out, n, descending, radix_nan_rule, tmp, tmp_bytes, s);
-    case GX_INT16: return sort_impl<uint16_t, K_SIGNED, HAS_VAL>(keys_in, keys_out, vals_in, vals_out, n, descending, radix_nan_rule, tmp, tmp_bytes, s);
-    case GX_UINT16: return sort_impl<uint16_t, K_UNSIGNED, HAS_VAL>(keys_in, keys_out, vals_in, vals_out, n, descending, radix_nan_rule, tmp, tmp_bytes, s);
-    case GX_INT32: return sort_impl<uint32_t, K_SIGNED, HAS_VAL>(keys_in, keys_out, vals_in, vals_out, n, descending, radix_nan_rule, tmp, tmp_bytes, s);
-    case GX_UINT32: return sort_impl<uint32_t, K_UNSIGNED, HAS_VAL>(keys_in, keys_out, vals_in, vals_out, n, descending, radix_nan_rule, tmp, tmp_bytes, s);
-    case GX_FLOAT32: return sort_impl<uint32_t, K_FLOAT, HAS_VAL>(keys_in, keys_out, vals_in, vals_out, n, descending, radix_nan_rule, tmp, tmp_bytes, s);
-    case GX_INT64: return sort_impl<uint64_t, K_SIGNED, HAS_VAL>(keys_in, keys_out, vals_in, vals_out, n, descending, radix_nan_rule, tmp, tmp_bytes, s);
-    case GX_UINT64: return sort_impl<uint64_t, K_UNSIGNED, HAS_VAL>(keys_in, keys_out, vals_in, vals_out, n, descending, radix_nan_rule, tmp, tmp_bytes, s);
-    case GX_FLOAT64: return sort_impl<uint64_t, K_FLOAT, HAS_VAL>(keys_in, keys_out, vals_in, vals_out, n, descending, radix_nan_rule, tmp, tmp_bytes, s);
-    default: return GX_EDTYPE;
-  }
+  return with_dtype(dtype, [&](auto t) {
+    using D = decltype(t);
+    return sort_impl<typename D::word_type, D::kind, HAS_VAL>(keys_in, keys_out, vals_in, vals_out, n, descending, radix_nan_rule, tmp, tmp_bytes, s);
+  });
 }
 
 
@@ -4556,11 +4538,7 @@ int sorted_order_nullable(int dtype, const void* keys, const uint32_t* valid, in
   uint32_t* partials  = c.take<uint32_t>(scan::partials_count(n));
   ElemT* dense_keys   = c.take<ElemT>((size_t)nvalid);
   int32_t* dense_idx  = c.take<int32_t>((size_t)nvalid);
-  if (tmp == nullptr) {
-    *tmp_bytes = c.total();
-    return 0;
-  }
-  if (*tmp_bytes < c.total()) return GX_ETMP;
+  if (int rc; !c.ready(tmp_bytes, &rc)) return rc;
   if (n == 0) return 0;
   const bool nulls_first = (nulls_before != 0) != (descending != 0);
   rc = scan::device_scan<uint32_t, uint32_t>(BitLoader{valid}, n, 0u, SumOp(), false, pos, partials, stream);
@@ -4615,11 +4593,7 @@ int sorted_order_words32(const void* keys, int64_t n, int descending, int32_t* o
   char* sort_tmp  = c.take<char>(sort_bytes);  // first: the plan header callers inspect (gx_sort_status / gx_sort_info) sits at tmp
   uint64_t* w_in  = c.take<uint64_t>((size_t)n);
   uint64_t* w_out = c.take<uint64_t>((size_t)n);
-  if (tmp == nullptr) {
-    *tmp_bytes = c.total();
-    return 0;
-  }
-  if (*tmp_bytes < c.total()) return GX_ETMP;
+  if (int rc; !c.ready(tmp_bytes, &rc)) return rc;
   if (keys == nullptr || out == nullptr) return GX_EINVAL;
   int64_t blocks = div_up(n, 256 * 8);
   if (blocks > 8192) blocks = 8192;
@@ -4635,30 +4609,33 @@ int sorted_order_words32(const void* keys, int64_t n, int descending, int32_t* o
   return 0;
 }
 
+// f(tag) for the integer keys of 4 and 8 bytes, all that the sharded sort takes
+template <typename F>
+int sortx_dispatch(int dtype, F&& f)
+{
+  return with_dtype(dtype, [&](auto t) -> int {
+    using D = decltype(t);
+    if constexpr (D::kind == K_FLOAT || sizeof(typename D::word_type) < 4) return GX_EDTYPE;
+    else return f(t);
+  });
+}
+
 }  // namespace sort
 }  // namespace gx
 
 extern "C" {
 
 // ---- the sharded sort's halves (see gx.h)
-#define GX_SORTX_DISPATCH(CALL64S, CALL64U, CALL32S, CALL32U)  \
-  switch (dtype) {                                              \
-    case GX_INT64: return CALL64S;                              \
-    case GX_UINT64: return CALL64U;                             \
-    case GX_INT32: return CALL32S;                              \
-    case GX_UINT32: return CALL32U;                             \
-    default: return GX_EDTYPE;                                  \
-  }
 int gx_sortx_sample(int dtype, const void* keys, int64_t n, int64_t recv_rows_max, void* tmp, size_t* tmp_bytes, gx_stream_t s)
 {
   using namespace gx::sort;
   if (n < 0 || recv_rows_max < 0 || !tmp_bytes || n > 0x7FFFFFFFll || recv_rows_max > 0x7FFFFFFFll) return GX_EINVAL;
   if (tmp && n > 0 && !keys) return GX_EINVAL;
   hipStream_t st = (hipStream_t)s;
-  GX_SORTX_DISPATCH((sortx_sample<uint64_t, gx::K_SIGNED>(keys, n, recv_rows_max, tmp, tmp_bytes, st)),
-                    (sortx_sample<uint64_t, gx::K_UNSIGNED>(keys, n, recv_rows_max, tmp, tmp_bytes, st)),
-                    (sortx_sample<uint32_t, gx::K_SIGNED>(keys, n, recv_rows_max, tmp, tmp_bytes, st)),
-                    (sortx_sample<uint32_t, gx::K_UNSIGNED>(keys, n, recv_rows_max, tmp, tmp_bytes, st)))
+  return sortx_dispatch(dtype, [&](auto t) {
+    using D = decltype(t);
+    return sortx_sample<typename D::word_type, D::kind>(keys, n, recv_rows_max, tmp, tmp_bytes, st);
+  });
 }
 int gx_sortx_masks(const void* tmp, uint64_t* masks2_host, gx_stream_t s)
 {
@@ -4675,10 +4652,10 @@ int gx_sortx_level0(int dtype, const void* keys, int64_t n, int64_t recv_rows_ma
   hipStream_t st = (hipStream_t)s;
   const int hint = sortx_cfg(recv_rows_max).bits2_max;
   const auto* m  = reinterpret_cast<const unsigned long long*>(masks2_host);
-  GX_SORTX_DISPATCH((sortx_level0<uint64_t, gx::K_SIGNED>(keys, n, recv_rows_max, m, hint, tmp, st)),
-                    (sortx_level0<uint64_t, gx::K_UNSIGNED>(keys, n, recv_rows_max, m, hint, tmp, st)),
-                    (sortx_level0<uint32_t, gx::K_SIGNED>(keys, n, recv_rows_max, m, hint, tmp, st)),
-                    (sortx_level0<uint32_t, gx::K_UNSIGNED>(keys, n, recv_rows_max, m, hint, tmp, st)))
+  return sortx_dispatch(dtype, [&](auto t) {
+    using D = decltype(t);
+    return sortx_level0<typename D::word_type, D::kind>(keys, n, recv_rows_max, m, hint, tmp, st);
+  });
 }
 int gx_sortx_tables(const void* tmp, uint32_t* cur0_host, uint32_t* slot0_host, uint32_t* slot_total_host, int32_t* state_host, gx_stream_t s)
 {
@@ -4711,10 +4688,10 @@ int gx_sortx_finish(int dtype, int64_t n_send, int64_t recv_rows_max, int64_t n,
   if (n < 0 || n_send < 0 || !tmp || !masks2_host || (nreg > 0 && (!reg_start_host || !reg_count_host || !reg_bucket_host)) || (n > 0 && !out)) return GX_EINVAL;
   hipStream_t st = (hipStream_t)s;
   const auto* m  = reinterpret_cast<const unsigned long long*>(masks2_host);
-  GX_SORTX_DISPATCH((sortx_finish<uint64_t, gx::K_SIGNED>(n_send, recv_rows_max, n, m, reg_start_host, reg_count_host, reg_bucket_host, nreg, out, tmp, st)),
-                    (sortx_finish<uint64_t, gx::K_UNSIGNED>(n_send, recv_rows_max, n, m, reg_start_host, reg_count_host, reg_bucket_host, nreg, out, tmp, st)),
-                    (sortx_finish<uint32_t, gx::K_SIGNED>(n_send, recv_rows_max, n, m, reg_start_host, reg_count_host, reg_bucket_host, nreg, out, tmp, st)),
-                    (sortx_finish<uint32_t, gx::K_UNSIGNED>(n_send, recv_rows_max, n, m, reg_start_host, reg_count_host, reg_bucket_host, nreg, out, tmp, st)))
+  return sortx_dispatch(dtype, [&](auto t) {
+    using D = decltype(t);
+    return sortx_finish<typename D::word_type, D::kind>(n_send, recv_rows_max, n, m, reg_start_host, reg_count_host, reg_bucket_host, nreg, out, tmp, st);
+  });
 }
 int gx_sortx_status(const void* tmp, int32_t* ok_host, gx_stream_t s)
 {
@@ -4728,7 +4705,6 @@ int gx_sortx_status(const void* tmp, int32_t* ok_host, gx_stream_t s)
   *ok_host = (state == 3 && ok == 1 && status == 0) ? 1 : 0;
   return 0;
 }
-#undef GX_SORTX_DISPATCH
 
 int gx_sort_keys(int dtype, const void* in, void* out, int64_t n, int descending, void* tmp,
                  size_t* tmp_bytes, gx_stream_t stream)

@@ -7,20 +7,9 @@ const char* gx_version(void) { return "cudf_amd 0.1.0 (gfx950)"; }
 
 int gx_dtype_size(int dtype)
 {
-  switch (dtype) {
-    case GX_INT8:
-    case GX_UINT8:
-    case GX_BOOL8: return 1;
-    case GX_INT16:
-    case GX_UINT16: return 2;
-    case GX_INT32:
-    case GX_UINT32:
-    case GX_FLOAT32: return 4;
-    case GX_INT64:
-    case GX_UINT64:
-    case GX_FLOAT64: return 8;
-    default: return 0;
-  }
+  int size = 0;  // stays 0 for an unknown dtype
+  gx::with_dtype(dtype, [&](auto t) { return size = (int)sizeof(typename decltype(t)::value_type); });
+  return size;
 }
 
 }  // extern "C"
@@ -131,20 +120,9 @@ int gx_mix64_inplace(uint64_t* data, int64_t n, gx_stream_t s)
 int gx_fill_random(int dtype, void* out, int64_t n, uint64_t seed, int64_t lo, int64_t hi, gx_stream_t s)
 {
   if (n < 0 || (n > 0 && !out)) return GX_EINVAL;
-  switch (dtype) {
-    case GX_INT8:
-    case GX_UINT8:
-    case GX_BOOL8: return gx::fill_launch<uint8_t>(out, n, seed, lo, hi, 0, s);
-    case GX_INT16:
-    case GX_UINT16: return gx::fill_launch<uint16_t>(out, n, seed, lo, hi, 0, s);
-    case GX_INT32:
-    case GX_UINT32: return gx::fill_launch<uint32_t>(out, n, seed, lo, hi, 0, s);
-    case GX_INT64:
-    case GX_UINT64: return gx::fill_launch<uint64_t>(out, n, seed, lo, hi, 0, s);
-    case GX_FLOAT32: return gx::fill_launch<float>(out, n, seed, lo, hi, 1, s);
-    case GX_FLOAT64: return gx::fill_launch<double>(out, n, seed, lo, hi, 1, s);
-    default: return GX_EDTYPE;
-  }
+  return gx::with_dtype(dtype, [&](auto t) {  // integers of either sign: the unsigned kernel of their width
+    return gx::fill_launch<gx::word_or_float_t<decltype(t)>>(out, n, seed, lo, hi, decltype(t)::kind == gx::K_FLOAT ? 1 : 0, s);
+  });
 }
 
 /* see gx.h */
@@ -195,20 +173,10 @@ int gx_sequence_i32(int32_t* out, int64_t n, int32_t start, gx_stream_t s)
 int gx_checksum(int dtype, const void* in, int64_t n, int descending, uint64_t* res_dev, gx_stream_t s)
 {
   if (n < 0 || !res_dev || (n > 0 && !in)) return GX_EINVAL;
-  switch (dtype) {
-    case GX_INT8: return gx::checksum_launch<uint8_t, 1>(in, n, descending, res_dev, s);
-    case GX_UINT8:
-    case GX_BOOL8: return gx::checksum_launch<uint8_t, 0>(in, n, descending, res_dev, s);
-    case GX_INT16: return gx::checksum_launch<uint16_t, 1>(in, n, descending, res_dev, s);
-    case GX_UINT16: return gx::checksum_launch<uint16_t, 0>(in, n, descending, res_dev, s);
-    case GX_INT32: return gx::checksum_launch<uint32_t, 1>(in, n, descending, res_dev, s);
-    case GX_UINT32: return gx::checksum_launch<uint32_t, 0>(in, n, descending, res_dev, s);
-    case GX_FLOAT32: return gx::checksum_launch<uint32_t, 2>(in, n, descending, res_dev, s);
-    case GX_INT64: return gx::checksum_launch<uint64_t, 1>(in, n, descending, res_dev, s);
-    case GX_UINT64: return gx::checksum_launch<uint64_t, 0>(in, n, descending, res_dev, s);
-    case GX_FLOAT64: return gx::checksum_launch<uint64_t, 2>(in, n, descending, res_dev, s);
-    default: return GX_EDTYPE;
-  }
+  return gx::with_dtype(dtype, [&](auto t) {
+    using D = decltype(t);
+    return gx::checksum_launch<typename D::word_type, D::kind>(in, n, descending, res_dev, s);
+  });
 }
 
 }  // extern "C"

@@ -14,6 +14,7 @@
 #include <cudf/table/table_view.hpp>
 #include <cudf/types.hpp>
 
+#include "../../cudf_amd/csrc/gx_dtype.hpp"     // plain C++: the dtype table behind every host-side dispatch (no HIP include)
 #include "../../cudf_amd/csrc/gx_lds_book.hpp"  // plain C++: the bookkeeping behind gx::launch_lds (no HIP include)
 
 #include <atomic>
@@ -22,6 +23,7 @@
 #include <stdexcept>
 #include <string>
 #include <thread>
+#include <type_traits>
 #include <vector>
 
 using namespace cudf;
@@ -69,6 +71,41 @@ int main()
     CHECK(is_floating_point(data_type{type_id::FLOAT64}) && !is_floating_point(data_type{type_id::INT32}));
     CHECK(type_to_id<int32_t>() == type_id::INT32 && type_to_id<double>() == type_id::FLOAT64);
     CHECK(JoinNoMatch == std::numeric_limits<size_type>::min());
+  });
+  run("dtype table: every gx_dtype reaches the callable with its own row, anything else GX_EDTYPE and no call (csrc/gx_dtype.hpp)", [] {
+    struct Row {
+      int dtype;
+      size_t value_size;
+      bool is_signed, is_float;
+      size_t word_size;
+      int kind;  // 0 unsigned, 1 signed, 2 float
+      bool is_bool;
+    };
+    const Row rows[] = {
+      {GX_INT8, 1, true, false, 1, 1, false},    {GX_INT16, 2, true, false, 2, 1, false},   {GX_INT32, 4, true, false, 4, 1, false},
+      {GX_INT64, 8, true, false, 8, 1, false},   {GX_UINT8, 1, false, false, 1, 0, false},  {GX_UINT16, 2, false, false, 2, 0, false},
+      {GX_UINT32, 4, false, false, 4, 0, false}, {GX_UINT64, 8, false, false, 8, 0, false}, {GX_BOOL8, 1, false, false, 1, 0, true},
+      {GX_FLOAT32, 4, true, true, 4, 2, false},  {GX_FLOAT64, 8, true, true, 8, 2, false},
+    };
+    CHECK(sizeof(rows) / sizeof(rows[0]) == 11);
+    for (const Row& r : rows) {
+      int calls    = 0;
+      const int rc = gx::with_dtype(r.dtype, [&](auto t) {
+        using D = decltype(t);
+        using V = typename D::value_type;
+        using W = typename D::word_type;
+        ++calls;
+        CHECK(sizeof(V) == r.value_size && std::is_signed<V>::value == r.is_signed && std::is_floating_point<V>::value == r.is_float);
+        CHECK(sizeof(W) == r.word_size && std::is_unsigned<W>::value && std::is_integral<W>::value);
+        CHECK((int)D::kind == r.kind && D::is_bool == r.is_bool);
+        return 100 + r.dtype;
+      });
+      CHECK(calls == 1 && rc == 100 + r.dtype);  // the callable's own return code comes back
+    }
+    for (int bad : {0, -1, GX_BOOL8 + 1}) {
+      int calls = 0;
+      CHECK(gx::with_dtype(bad, [&](auto) { return ++calls; }) == GX_EDTYPE && calls == 0);
+    }
   });
   run("launch layer: the dynamic-LDS limit is recorded per (kernel, device) (csrc/gx_lds_book.hpp)", [] {
     static gx::LdsBook book;  // (static: the table is too large for the stack)

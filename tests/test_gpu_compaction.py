@@ -8,6 +8,8 @@ import subprocess
 import numpy as np
 import pytest
 
+from tests import route_values as route
+
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -292,6 +294,23 @@ def test_compare_scalar_and_its_use_as_a_mask(gx, dtype):
     if dt.kind in "iu":
         with pytest.raises(OverflowError):
             ops.compare_scalar(col, "eq", -1 if dt.kind == "u" else 2**70)
+
+
+@pytest.mark.parametrize("dtype", route.DTYPES)
+def test_compare_scalar_dtype_routes(gx, dtype):
+    """gx_compare_scalar picks the value type from the dtype: one wave and a tail row of the values that tell a wrong instantiation
+    from the right one (tests/route_values.py) -- a signed column compared as unsigned puts its negative values above the scalar,
+    a float compared as bits orders -0.0 and NaN."""
+    _, Column, ops = gx
+    v = route.route_values(dtype, seed=8)
+    dt = v.dtype
+    scalars = {"b": [True, False], "f": [0.0, -50.5]}.get(dt.kind) or [3, np.iinfo(dt).max // 2 + 1 if dt.kind == "u" else -3]
+    col = Column.from_numpy(v)
+    for scalar in scalars:
+        for op, fn in _CMP_NP.items():
+            with np.errstate(invalid="ignore"):
+                exp = fn(v, dt.type(scalar))
+            assert np.array_equal(ops.compare_scalar(col, op, scalar).to_numpy(), exp), (dtype, op, scalar)
 
 
 def test_argument_errors(gx):

@@ -32,6 +32,7 @@ pytestmark = pytest.mark.gpu
 
 from oracle import cudf_oracle as orc
 from tests import moments_cases as mc
+from tests import route_values as route
 from tests.test_gpu_cpp_parity import Dev, Out, NPT, shim  # noqa: F401  (the shim fixture and the device-column helpers)
 from tests.test_gpu_join_groupby import _groupby_raw
 
@@ -334,3 +335,24 @@ def test_square_centered_bit_for_bit(gx, n):
     nan = np.isnan(want)
     np.testing.assert_array_equal(np.isnan(got[:n]), nan)
     np.testing.assert_array_equal(got[:n][~nan].view(np.int64), want[~nan].view(np.int64))
+
+
+@pytest.mark.parametrize("dtype", route.DTYPES)
+def test_square_dtype_routes(gx, dtype):
+    """gx_square picks <value type, INT64 or the float's own type> from the dtype: one wave and a tail row of the values that tell a
+    wrong instantiation from the right one (tests/route_values.py).  Integers are shifted so that no square passes 2^63: int64
+    arithmetic, as in the kernel.  (Not told apart: INT64 from UINT64 -- the squares agree mod 2^64.)"""
+    from cudf_amd import _lib as L
+    Column, ops = gx
+    v = route.route_values(dtype, seed=4)
+    dt = v.dtype
+    if dt.kind in "iu" and dt.itemsize >= 4:
+        v = v >> (32 if dt.itemsize == 8 else 1)       # arithmetic for the signed types: negative values stay negative
+        if dt == np.uint32:
+            v[64] = 2**31 + 5                            # as INT32 it would be -(2^31 - 5): another square
+    col = Column.from_numpy(v)
+    out = Column.empty(dt if dt.kind == "f" else np.int64, len(v))
+    L.check(L.lib.gx_square(col.gx, col.data_ptr, len(v), out.data_ptr, ops.stream_ptr()), "gx_square")
+    with np.errstate(invalid="ignore", over="ignore"):
+        want = v * v if dt.kind == "f" else v.astype(np.int64) * v.astype(np.int64)
+    np.testing.assert_array_equal(out.to_numpy(), want)

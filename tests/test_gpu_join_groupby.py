@@ -5,6 +5,7 @@ import pytest
 pytestmark = pytest.mark.gpu
 
 from oracle import cudf_oracle as orc
+from tests import route_values as route
 from tests.golden import reference_vectors as gv
 
 
@@ -607,3 +608,105 @@ def test_groupby_dense_path_declines_or_falls_back(gx, case):
     np.testing.assert_array_equal(ca[o], res["count_all"][0])
     ev = res["sum"][1] if vv is not None else np.ones(len(ek), bool)
     np.testing.assert_array_equal(s[o][ev], res["sum"][0][ev])
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# dtype routes: one wave and a tail row of the values that tell a wrong kernel instantiation from the right one
+# (tests/route_values.py), every value dtype and the four key dtypes
+# ---------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("vdtype", route.DTYPES)
+def test_groupby_dtype_routes(gx, vdtype):
+    """The hash groupby picks its key word from the key dtype and <value type, is-float> from the value dtype, gx_groupby_arg_select
+    and gx_segmented_scan the value type (with its signedness).  SUM of floats has test_groupby_sum_count_matches_oracle."""
+    Column, ops = gx
+    kdtype = ["int32", "uint32", "int64", "uint64"][route.DTYPES.index(vdtype) % 4]
+    ki = np.iinfo(kdtype)
+    keys = np.array([ki.min, ki.max, 3, ki.max // 2 + 1, 7], kdtype)[np.arange(route.ROWS) % 5]
+    v = route.route_values(vdtype, seed=5, nan=False)
+    vv = np.ones(len(v), bool)
+    vv[[2, 30]] = False
+    K, V = Column.from_numpy(keys), Column.from_numpy(v, vv)
+    kind = np.dtype(vdtype).kind
+    ek, res = orc.groupby_agg(keys, v, ["sum", "min", "max", "count_valid", "count_all"], None, vv)
+    k, s, cv, ca = ops.groupby_sum_count(K, V)
+    o = np.argsort(k.to_numpy(), kind="stable")
+    np.testing.assert_array_equal(k.to_numpy()[o], ek)
+    np.testing.assert_array_equal(cv.to_numpy()[o], res["count_valid"][0])
+    np.testing.assert_array_equal(ca.to_numpy()[o], res["count_all"][0])
+    if kind != "f":
+        assert s.dtype == np.int64
+        np.testing.assert_array_equal(s.to_numpy()[o], res["sum"][0])
+    k, amin, amax, cv = ops.groupby_argmin_argmax(K, V)
+    k2, mn, mx, _ = ops.groupby_min_max(K, V)
+    o, o2 = np.argsort(k.to_numpy(), kind="stable"), np.argsort(k2.to_numpy(), kind="stable")
+    assert mn.dtype == v.dtype and mx.dtype == v.dtype
+    for got, arg, want in ((mn, amin, res["min"][0]), (mx, amax, res["max"][0])):
+        np.testing.assert_array_equal(got.to_numpy()[o2], want)
+        first = [int(np.flatnonzero((keys == ek[g]) & vv & (v == want[g]))[0]) for g in range(len(ek))]
+        np.testing.assert_array_equal(arg.to_numpy()[o], first)
+    order = ops.sorted_order(K)
+    sk, sv = ops.gather(K, order), ops.gather(V, order)
+    for op in {"b": ("sum",), "f": ("min", "max")}.get(kind, ("sum", "min", "max")):  # (the oracle scans no bool MIN / MAX)
+        out = ops.groupby_scan(sk, sv, op)
+        esk, eo, ev = orc.groupby_scan(keys, v, op, None, vv)
+        np.testing.assert_array_equal(sk.to_numpy(), esk)
+        assert out.dtype == eo.dtype
+        np.testing.assert_array_equal(out.to_numpy()[ev], eo[ev], err_msg=f"{vdtype} scan {op}")
+
+
+@pytest.mark.parametrize("kdtype", route.DTYPES)
+def test_run_heads_dtype_routes(gx, kdtype):
+    """gx_segmented_scan's and gx_group_heads' key dispatch picks <word, kind>: a float key compares normalised (-0.0 with +0.0, every
+    NaN with every NaN: one run each), an integer key by its bits.  The runs of the sorted column, as running counts and as labels."""
+    Column, ops = gx
+    v = route.route_values(kdtype, seed=6)
+    v = np.concatenate([v, v[::3]])             # ties, the specials among them
+    col = Column.from_numpy(v)
+    sk = ops.gather(col, ops.sorted_order(col))
+    s = sk.to_numpy()
+    same = s[1:] == s[:-1]
+    if s.dtype.kind == "f":
+        same |= np.isnan(s[1:]) & np.isnan(s[:-1])
+        assert ((s[1:] == 0) & (s[:-1] == 0) & (np.signbit(s[1:]) != np.signbit(s[:-1]))).any()   # -0.0 next to +0.0: one run
+    heads = np.concatenate([[True], ~same])
+    labels = np.cumsum(heads) - 1
+    starts = np.flatnonzero(heads)
+    ones = Column.from_numpy(np.ones(len(s), np.int32))
+    np.testing.assert_array_equal(ops.groupby_scan(sk, ones, "sum").to_numpy(), np.arange(len(s)) - starts[labels] + 1)
+    got_labels, got_offsets = ops.group_runs([sk])
+    np.testing.assert_array_equal(got_labels.cpu().numpy()[:len(s)], labels)
+    np.testing.assert_array_equal(got_offsets.cpu().numpy()[:len(starts)], starts)
+
+
+@pytest.mark.parametrize("vdtype", route.DTYPES)
+def test_segmented_reduce_dtype_routes(gx, vdtype):
+    """gx_segmented_reduce (the sort-path groupby's aggregation) picks <value type, signed> from the value dtype.  Five runs over
+    one wave and a tail row; integer SUM in int64, MIN / MAX in the value type; a run without a valid value counts 0.  (SUM of
+    floats has tests/test_gpu_float_sums.py.)"""
+    import torch
+    from cudf_amd import _lib as L
+    Column, ops = gx
+    v = route.route_values(vdtype, seed=9, nan=False)
+    n = len(v)
+    vv = np.ones(n, bool)
+    vv[[2, 30]] = False
+    vv[52:] = False                                            # the last run: nulls only
+    labels = (np.arange(n) // 13).astype(np.int32)
+    heads = np.concatenate([[1], (labels[1:] != labels[:-1])]).astype(np.uint8)
+    V = Column.from_numpy(v, vv)
+    d_heads, d_labels = torch.from_numpy(heads).cuda(), torch.from_numpy(labels).cuda()
+    kind = np.dtype(vdtype).kind
+    g = int(labels[-1]) + 1
+    for op, code in (("sum", L.OP_SUM), ("min", L.OP_MIN), ("max", L.OP_MAX)):
+        if op == "sum" and kind == "f":
+            continue
+        out = Column.empty(np.int64 if op == "sum" else v.dtype, g)
+        cnt = torch.full((g,), -7, dtype=torch.int32, device="cuda")
+        ops._run(L.lib.gx_segmented_reduce, V.gx, V.data_ptr, V.mask_ptr, ops.ptr(d_heads), ops.ptr(d_labels), n, code, out.data_ptr,
+                 ops.ptr(cnt))
+        want_cnt = np.array([int(vv[labels == r].sum()) for r in range(g)])
+        np.testing.assert_array_equal(cnt.cpu().numpy(), want_cnt)
+        for r in np.flatnonzero(want_cnt):
+            x = v[(labels == r) & vv]
+            want = x.astype(np.int64).sum() if op == "sum" else (x.min() if op == "min" else x.max())
+            assert out.to_numpy()[r] == want, (vdtype, op, r)

@@ -7,6 +7,7 @@ import pytest
 pytestmark = pytest.mark.gpu
 
 from oracle import cudf_oracle as orc
+from tests import route_values as route
 from tests.golden import reference_vectors as gv
 
 
@@ -202,3 +203,50 @@ def test_bitmask_utilities(gx):
     pos = torch.zeros(1, dtype=torch.int64, device="cuda")
     L.check(L.lib.gx_bitmask_first_unset(ptr(out), n, ptr(pos), stream_ptr()))
     assert int(pos.item()) == int(np.argmin(exp))
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# dtype routes: one wave and a tail row of the values that tell a wrong kernel instantiation from the right one
+# (tests/route_values.py).  uint16 and bool are in no list above.
+# ---------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("dtype", route.DTYPES)
+def test_dtype_routes_reduce_scan(gx, dtype):
+    """gx_reduce and gx_scan pick <value type, signed> from the dtype: MIN / MAX of a signed type sent down the unsigned route (or
+    the other way round) order the extremes wrongly, a wrong width reads other bytes.  Integer SUM too; float SUM has
+    tests/test_gpu_float_sums.py."""
+    Column, ops = gx
+    v = route.route_values(dtype, seed=1, nan=False)
+    valid = np.ones(len(v), bool)
+    valid[[2, 30]] = False
+    kind = np.dtype(dtype).kind
+    for op in ("min", "max") + (("sum",) if kind in "iu" else ()):
+        for m in (None, valid):
+            sel = np.ones(len(v), bool) if m is None else m
+            if kind == "b":  # (the oracle takes no bool) nulls are the identity
+                acc = np.minimum if op == "min" else np.maximum
+                ev = acc.accumulate(np.where(sel, v, op == "min"))
+                exp = ev[-1]
+            else:
+                exp, _ = orc.reduce(v, op, m, (np.uint64 if kind == "u" else np.int64) if op == "sum" else None)
+                ev, _ = orc.scan(v, op, True, m)
+            got, ok = ops.reduce(Column.from_numpy(v, m), op)
+            assert ok and got == exp, (dtype, op, got, exp)
+            out = ops.scan(Column.from_numpy(v, m), op, True).to_numpy()
+            assert out.dtype == v.dtype
+            np.testing.assert_array_equal(out[sel], ev[sel], err_msg=f"{dtype} {op}")
+
+
+@pytest.mark.parametrize("dtype", route.DTYPES)
+def test_dtype_routes_hash(gx, dtype):
+    """gx_murmur3_32 picks <word, mode> and gx_identity_hash_32 <value type, is_bool>: a BOOL8 byte of 2 or 255 hashes as `true`
+    (as UINT8 it would hash as 2 or 255), floats hash normalised (-0.0 as +0.0, every NaN as one), a negative integer's identity
+    hash is its sign-extended low word."""
+    Column, ops = gx
+    v = route.route_values(dtype, seed=2, raw_bool=True)
+    valid = np.ones(len(v), bool)
+    valid[[3, 30]] = False
+    if dtype == "bool":
+        assert set(v.view(np.uint8).tolist()) == {0, 1, 2, 255}
+    for m in (None, valid):
+        np.testing.assert_array_equal(ops.murmurhash3_x86_32([Column.from_numpy(v, m)], 619).to_numpy(), orc.murmur3_32(v, 619, m))
+        np.testing.assert_array_equal(ops.identity_hash([Column.from_numpy(v, m)]).to_numpy(), orc.identity_hash32(v, m))

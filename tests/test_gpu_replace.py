@@ -388,6 +388,20 @@ def test_clamp(lib, gx, ROWS, dtype):
         run_clamp(lib, code, x, lo, hi).check(dt, np.clip(x, lo, hi), None, "near 2^63")
 
 
+def test_clamp_bool8_bytes_other_than_0_and_1_are_true(lib, gx):
+    """gx_clamp reads is_bool from the dtype table: a BOOL8 byte of 2 or 255 is `true`, so [false, true] bounds nothing and every
+    row keeps its byte, and [false, false] turns every non-zero byte into 0 (as UINT8 the byte 2 would pass hi = 1).  One wave and a
+    tail row."""
+    L = gx[0]._lib
+    raw = np.random.default_rng(41).choice(np.array([0, 1, 2, 255], np.uint8), 65)
+    raw[:4] = [2, 0, 255, 1]
+    x = raw.view(np.bool_)
+    run_clamp(lib, L.BOOL8, x, np.False_, np.True_).check(np.dtype(bool), x, None, "inside the bounds: the byte is kept")
+    run_clamp(lib, L.BOOL8, x, np.False_, np.False_).check(np.dtype(bool), np.zeros(65, np.bool_), None, "above hi = false")
+    run_clamp(lib, L.BOOL8, x, np.True_, np.True_).check(np.dtype(bool), np.where(raw == 0, 1, raw).astype(np.uint8).view(np.bool_), None,
+                                                         "below lo = true")
+
+
 # ------------------------------------------------------------------------------------------------ find_and_replace
 def find_model(x, valid, old, new, new_valid):
     """out[i] = new[j] for the smallest j with x[i] == old[j] (the dtype's ==: NaN matches nothing, -0.0 == +0.0), valid rows only"""

@@ -5,6 +5,7 @@ import pytest
 pytestmark = pytest.mark.gpu
 
 from oracle import cudf_oracle as orc
+from tests import route_values as route
 from tests.golden import reference_vectors as gv
 
 
@@ -307,3 +308,49 @@ def test_hybrid_sort_presorted_and_few_values(gx):
         assert got.tobytes() == base.tobytes() and info[1] == 1, info
         order = ops.sorted_order(Column.from_numpy(v)).to_numpy()
         np.testing.assert_array_equal(order, np.argsort(v, kind="stable"))
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# dtype routes: one wave and a tail row of the values that tell a wrong kernel instantiation from the right one
+# (tests/route_values.py); bool is in no list above
+# ---------------------------------------------------------------------------------------------------------------------
+def _splitmix64(x):
+    m = (1 << 64) - 1
+    x = (x + 0x9E3779B97F4A7C15) & m
+    x = ((x ^ (x >> 30)) * 0xBF58476D1CE4E5B9) & m
+    x = ((x ^ (x >> 27)) * 0x94D049BB133111EB) & m
+    return x ^ (x >> 31)
+
+
+@pytest.mark.parametrize("dtype", route.DTYPES)
+def test_sort_checksum_fill_dtype_routes(gx, dtype):
+    """gx_sort_keys, gx_sorted_order and gx_checksum pick <word, kind> from the dtype, gx_fill_random the word (the value type for
+    floats).  The checksum counts the descents of the column in the sort's own order: none in the sorted column, and in its reverse
+    one per step between two equivalence classes (-0.0 with +0.0 and all NaNs are one class each)."""
+    Column, ops = gx
+    v = route.route_values(dtype, seed=7)
+    col = Column.from_numpy(v)
+    exp = orc.sort_keys(v, True)
+    got = ops.sort(col)
+    assert got.to_numpy().tobytes() == exp.tobytes()
+    np.testing.assert_array_equal(v[ops.sorted_order(col).to_numpy()].view(np.uint8), exp.view(np.uint8))
+    same = exp[1:] == exp[:-1]
+    if exp.dtype.kind == "f":
+        same |= np.isnan(exp[1:]) & np.isnan(exp[:-1])
+    assert ops.checksum(got)[2] == 0
+    assert ops.checksum(got, descending=True)[2] == int((~same).sum())
+    assert ops.checksum(Column.from_numpy(exp[::-1].copy()))[2] == int((~same).sum())
+    # the fill: splitmix64(seed + i), integers lo + r % (hi - lo) (or all of r's low bits), floats the top 53 bits in [0, 1)
+    dt = v.dtype
+    r = [_splitmix64(99 + i) for i in range(route.ROWS)]
+    bits = (1 << (8 * dt.itemsize)) - 1
+    uint = np.dtype(f"uint{8 * dt.itemsize}")
+    if dt.kind == "f":
+        want = np.array([(x >> 11) / 2.0**53 for x in r], np.float64).astype(dt)
+        np.testing.assert_array_equal(ops.random_column(dt, route.ROWS, 99).to_numpy(), want)
+    else:
+        lo, hi = (0, 2) if dt.kind == "b" else (-100, 1000) if dt.kind == "i" and dt.itemsize > 1 else (3, 120)
+        want = np.array([(lo + x % (hi - lo)) & bits for x in r], uint).view(dt)
+        np.testing.assert_array_equal(ops.random_column(dt, route.ROWS, 99, lo, hi).to_numpy(), want)
+        if dt.kind != "b":
+            np.testing.assert_array_equal(ops.random_column(dt, route.ROWS, 99).to_numpy(), np.array([x & bits for x in r], uint).view(dt))
