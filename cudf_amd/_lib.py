@@ -43,6 +43,39 @@ UNOPS = ("SIN", "COS", "TAN", "ARCSIN", "ARCCOS", "ARCTAN", "SINH", "COSH", "TAN
          "SQRT", "CBRT", "CEIL", "FLOOR", "ABS", "RINT", "BIT_COUNT", "BIT_INVERT", "NOT", "NEGATE")
 UNOP = {name: code for code, name in enumerate(UNOPS)}
 UNOP.update(IS_NAN=100, IS_NOT_NAN=101)
+# gx_ast_op (== cudf::ast::ast_operator): the binary operators, then the unary ones from IDENTITY on
+AST_OPS = ("ADD", "SUB", "MUL", "DIV", "TRUE_DIV", "FLOOR_DIV", "MOD", "PYMOD", "POW", "EQUAL", "NULL_EQUAL", "NOT_EQUAL", "LESS",
+           "GREATER", "LESS_EQUAL", "GREATER_EQUAL", "BITWISE_AND", "BITWISE_OR", "BITWISE_XOR", "LOGICAL_AND", "NULL_LOGICAL_AND",
+           "LOGICAL_OR", "NULL_LOGICAL_OR", "IDENTITY", "IS_NULL", "SIN", "COS", "TAN", "ARCSIN", "ARCCOS", "ARCTAN", "SINH", "COSH",
+           "TANH", "ARCSINH", "ARCCOSH", "ARCTANH", "EXP", "LOG", "SQRT", "CBRT", "CEIL", "FLOOR", "ABS", "RINT", "BIT_INVERT", "NOT",
+           "CAST_TO_INT64", "CAST_TO_UINT64", "CAST_TO_FLOAT64")
+AST_OP = {name: code for code, name in enumerate(AST_OPS)}
+AST_FIRST_UNARY = AST_OP["IDENTITY"]
+EXPR_COLUMN, EXPR_LITERAL, EXPR_UNARY, EXPR_BINARY = range(4)                                  # gx_expr_node_kind
+EXPR_LOAD, EXPR_APPLY, EXPR_APPLY_REV, EXPR_APPLY_UNARY, EXPR_SPILL = range(5)                  # gx_expr_instr_kind
+EXPR_SRC_COLUMN, EXPR_SRC_LITERAL, EXPR_SRC_SLOT = range(3)                                    # gx_expr_src_kind
+
+
+class ExprNode(ctypes.Structure):
+    _fields_ = [("kind", ctypes.c_int32), ("op", ctypes.c_int32), ("lhs", ctypes.c_int32), ("rhs", ctypes.c_int32)]
+
+
+class ExprColumn(ctypes.Structure):
+    _fields_ = [("data", ctypes.c_void_p), ("valid", ctypes.c_void_p), ("begin_bit", ctypes.c_int64), ("dtype", ctypes.c_int32),
+                ("reserved", ctypes.c_int32)]
+
+
+class ExprLiteral(ctypes.Structure):
+    _fields_ = [("value", ctypes.c_void_p), ("valid", ctypes.c_void_p), ("dtype", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+
+
+class ExprInstr(ctypes.Structure):
+    _fields_ = [(f, ctypes.c_uint8) for f in ("kind", "op", "src_kind", "src_index", "in_dtype", "out_dtype", "family", "family_op")]
+
+
+_pi = ctypes.POINTER(ctypes.c_int)
+_pi32 = ctypes.POINTER(ctypes.c_int32)
+
 # gx_interp (== cudf::interpolation), gx_quantile_mode, gx_quantile_path
 INTERP = {"linear": 0, "lower": 1, "higher": 2, "midpoint": 3, "nearest": 4}
 QUANTILE_MODE = {"auto": 0, "select": 1, "sort": 2}
@@ -212,6 +245,14 @@ _PROTOS = {
     "gx_unary_op_supported": (_i, [_i, _i, _i]),
     "gx_elementwise_tile_rows": (_i, []),
     "gx_elementwise_grid_cap": (_i, []),
+    # expressions (gx_expression.hip): one launch per expression tree; types, plan and limits are host code
+    "gx_compute_column": (_i, [ctypes.POINTER(ExprNode), _i, ctypes.POINTER(ExprColumn), _i, ctypes.POINTER(ExprLiteral), _i, _i64, _i, _p,
+                               _p, _p, _p]),
+    "gx_expr_result_dtype": (_i, [ctypes.POINTER(ExprNode), _i, _pi32, _i, _pi32, _i]),
+    "gx_expr_plan": (_i, [ctypes.POINTER(ExprNode), _i, _pi32, _i, _pi32, _i, ctypes.POINTER(ExprInstr), _i, _pi, _pi]),
+    "gx_expr_limits": (None, [_pi, _pi, _pi, _pi]),
+    "gx_expression_tile_rows": (_i, []),
+    "gx_expression_grid_cap": (_i, []),
     # null and value replacement (gx_replace.hip): streaming passes; only the policy fill has scratch (its carry table)
     "gx_replace_tile_rows": (_i, []),
     "gx_find_and_replace_chunk": (_i, []),

@@ -77,6 +77,21 @@ class DataFrame:
             raise ValueError(f"Item wrong length {key.size} instead of {len(self)}.")
         return self._from_columns(ops.apply_boolean_mask(list(self._cols.values()), key))
 
+    def eval(self, text: str) -> Column:
+        """pandas' DataFrame.eval for one expression over the columns: names, numeric literals, + - * / // % **, comparisons,
+        & | ~, and / or / not, parentheses (cudf_amd.ast.parse_eval has the typing rules).  The whole expression is one launch
+        (ops.compute_column); the Column operators stay eager."""
+        from .ast import parse_eval
+        expr, _ = parse_eval(text, {name: c.dtype for name, c in self._cols.items()})
+        return ops.compute_column(list(self._cols.values()), expr)
+
+    def query(self, text: str) -> "DataFrame":
+        """pandas' DataFrame.query: the rows where the bool expression `text` is true, in row order (a null drops its row)"""
+        mask = self.eval(text)
+        if mask.dtype != np.bool_:
+            raise ValueError(f"query: {text!r} is a {mask.dtype} expression, not a bool one")
+        return self._from_columns(ops.apply_boolean_mask(list(self._cols.values()), mask))
+
     def _from_columns(self, cols: Sequence[Column]) -> "DataFrame":
         out = DataFrame()
         for name, c in zip(self._cols, cols):

@@ -1754,6 +1754,73 @@ def is_not_nan(col: Column) -> Column:
 
 
 # ------------------------------------------------------------------------------------------------
+# expressions  (cudf::compute_column: transform.hpp, ast/expressions.hpp; gx_expression.hip)
+# ------------------------------------------------------------------------------------------------
+
+_GX2NP = {L.INT8: np.int8, L.INT16: np.int16, L.INT32: np.int32, L.INT64: np.int64, L.UINT8: np.uint8, L.UINT16: np.uint16,
+          L.UINT32: np.uint32, L.UINT64: np.uint64, L.FLOAT32: np.float32, L.FLOAT64: np.float64, L.BOOL8: np.bool_}
+
+
+def _expression_args(columns: Sequence[Column], expr):
+    """the node array of an expression over `columns`, the table columns it reads and its literals, checked against the table"""
+    from . import ast as A
+    columns = list(columns)
+    nodes, used, literals = A.flatten(expr)
+    for i in used:
+        if i >= len(columns):
+            raise IndexError(f"column reference {i} is out of range for a table of {len(columns)} columns")
+    node_arr = (L.ExprNode * len(nodes))(*[L.ExprNode(*nd) for nd in nodes])
+    return node_arr, [columns[i] for i in used], literals
+
+
+def _expression_dtype(node_arr, cols: Sequence[Column], literals) -> np.dtype:
+    cd = (ctypes.c_int32 * max(len(cols), 1))(*[c.gx for c in cols])
+    ld = (ctypes.c_int32 * max(len(literals), 1))(*[gx_dtype(l.dtype) for l in literals])
+    rc = _lib.gx_expr_result_dtype(node_arr, len(node_arr), cd, len(cols), ld, len(literals))
+    if rc == -2:
+        raise TypeError("the expression has a type error: operands of different dtypes, or an operator that does not take the dtype")
+    if rc <= 0:
+        raise ValueError("the expression is malformed or beyond the limits of gx_expr_limits")
+    return np.dtype(_GX2NP[rc])
+
+
+def expression_result_dtype(columns: Sequence[Column], expr) -> np.dtype:
+    """the dtype ops.compute_column gives for `expr` over `columns` (gx_expr_result_dtype): TypeError for a type error"""
+    node_arr, cols, literals = _expression_args(columns, expr)
+    return _expression_dtype(node_arr, cols, literals)
+
+
+def compute_column(columns: Sequence[Column], expr) -> Column:
+    """cudf::compute_column: the expression tree `expr` (cudf_amd.ast) over the columns of a table, in one launch and without
+    intermediate columns.  A row is null where an operand of a node is (IS_NULL, NULL_EQUAL and NULL_LOGICAL_* have their own
+    rules); a mask is allocated when a column the expression reads has nulls or a literal is invalid, and kept when a row is null."""
+    node_arr, cols, literals = _expression_args(columns, expr)
+    out_dt = _expression_dtype(node_arr, cols, literals)
+    if len({c.size for c in columns}) > 1:
+        raise ValueError("Column sizes don't match")
+    if not len(columns):
+        raise ValueError("compute_column needs a table with at least one column")
+    n = columns[0].size
+    may_be_null = any(c.has_nulls() for c in cols) or any(l.value is None for l in literals)
+    out = Column.empty(out_dt, n, nullable=may_be_null and n > 0)
+    if n == 0:
+        return out
+    keep = [_device_scalar(l.value, l.dtype) for l in literals]   # device scalars stay alive until the launch is queued
+    col_arr = (L.ExprColumn * max(len(cols), 1))(*[L.ExprColumn(c.data.data_ptr(), c.mask.data_ptr() if c.has_nulls() else None, 0, c.gx, 0)
+                                                   for c in cols])
+    lit_arr = (L.ExprLiteral * max(len(literals), 1))(*[L.ExprLiteral(val.data_ptr(), vb.data_ptr(), gx_dtype(l.dtype), 0)
+                                                       for l, (val, vb) in zip(literals, keep)])
+    nulls = _dev_i64() if may_be_null else None
+    L.check(_lib.gx_compute_column(node_arr, len(node_arr), col_arr, len(cols), lit_arr, len(literals), n, out.gx, out.data_ptr, out.mask_ptr,
+                                   ptr(nulls), stream_ptr()), "gx_compute_column")
+    if may_be_null:
+        out.null_count = int(nulls.item())
+        if out.null_count == 0:
+            out.mask = None
+    return out
+
+
+# ------------------------------------------------------------------------------------------------
 # null and value replacement  (cudf::replace_nulls / replace_nans / clamp / find_and_replace_all: replace.hpp; gx_replace.hip)
 # ------------------------------------------------------------------------------------------------
 

@@ -473,6 +473,101 @@ int gx_elementwise_tile_rows(void);                                             
 int gx_elementwise_grid_cap(void);                                               /* most workgroups of one launch */
 
 /* ------------------------------------------------------------------------------------------
+ * Expressions (cudf_amd/csrc/gx_expression.hip): cudf::compute_column.  One launch evaluates a whole expression tree over the
+ * columns of a table, row by row, with the per-value operators, compute classes and validity rules of the element-wise block
+ * above (one copy: csrc/gx_elementwise_ops.hpp): no intermediate column is written.  Conventions as above: raw device pointers,
+ * stream-ordered, no host synchronisation, n in [0, 2^31), n == 0 returns 0 and reads no pointer.
+ * The expression is a flat post-order array of gx_expr_node: COLUMN (lhs = index into cols), LITERAL (lhs = index into lits), UNARY
+ *   (op, lhs = child node), BINARY (op, lhs / rhs = child nodes).  A child's index is below its parent's, the last node is the
+ *   root, a node may be the child of several parents (it is then evaluated once per parent).  A literal is one element in device
+ *   memory with a device validity byte (NULL = valid), as the scalar sides of gx_binary_op.
+ * Types.  C(T) is the compute class of T as a dtype: INT32 for BOOL8 and everything narrower than 32 bits, else T.  The two
+ *   operands of a binary node must have the same dtype (no promotion: the caller inserts CAST_TO_*).  gx_ast_op carries the values
+ *   of cudf::ast::ast_operator:
+ *     ADD SUB MUL DIV MOD PYMOD -> C(T), gx_binary_op's operators in class C(T);  TRUE_DIV -> FLOAT64, double(a) / double(b);
+ *     FLOOR_DIV -> FLOAT64, floor(double(a) / double(b)) (not gx_binary_op's integer FLOOR_DIV);  POW -> FLOAT32 on FLOAT32, else
+ *     FLOAT64;  BITWISE_AND / OR / XOR -> C(T), integers only;  EQUAL ... GREATER_EQUAL, LOGICAL_AND / OR -> BOOL8;
+ *     NULL_EQUAL -> BOOL8, always valid;  NULL_LOGICAL_AND / OR -> BOOL8, Kleene validity;
+ *     IDENTITY -> T;  IS_NULL -> BOOL8, always valid;  NOT -> BOOL8 (x == 0);  ABS, BIT_INVERT -> C(T), computed in the class (ABS of
+ *     an INT8 -128 is 128), on the dtypes gx_unary_op takes them on;  SQRT CEIL FLOOR RINT -> T, floats;  CAST_TO_INT64 / UINT64 /
+ *     FLOAT64 -> the target, gx_cast's conversion.  The transcendental operators and CBRT are not built: GX_EDTYPE.
+ *   Every other node is null where an operand is; the data of a null row and the undefined cases of gx_binary_op are unspecified and
+ *   do not fault.  a * b + c is two roundings.  out_dtype must equal gx_expr_result_dtype: there is no cast on the final store.
+ * gx_compute_column: out_valid (optional) gets every one of the (n + 31) / 32 words, bits behind the last row 0, and nothing behind
+ *   them; *out_null_count_dev (optional) the null rows (0 without out_valid).  The bitmaps of the columns are read from their own
+ *   begin bits whether or not out_valid is given (IS_NULL and the NULL_* operators see them).  A workgroup owns
+ *   gx_expression_tile_rows() consecutive rows per trip (a multiple of 32: one writer per word, no atomics), at most
+ *   gx_expression_grid_cap() workgroups are launched, and a thread moves 16 bytes per access on the widest column the expression
+ *   reads or the output.  One launch per call; spill slots are LDS; a program without the division family, TRUE_DIV / FLOOR_DIV
+ *   and POW runs a variant of the kernel built without them (fewer registers, more waves).
+ * gx_expr_plan: the linear program of the accumulator machine the kernel runs, for a model on the host.  Instructions
+ *   (gx_expr_instr): LOAD acc = src;  BINARY acc = acc op src;  BINARY_REV acc = src op acc;  UNARY acc = op(acc);  SPILL slot
+ *   src_index = acc.  src is a column, a literal or a spill slot; in_dtype is the dtype of the operands (of src for LOAD), out_dtype
+ *   that of the accumulator afterwards.  The heavier child of a node runs first, so only a node with two non-leaf children spills,
+ *   and *n_slots never exceeds the Strahler number of the tree.  GX_EOVERFLOW when capacity is too small (*n_instructions is set).
+ * gx_expr_limits: at most 32 nodes, 16 columns, 16 literals, 4 spill slots; a program has at most 64 instructions (what a tree of 32
+ *   nodes can need; shared nodes count once per parent).  Beyond any of them every entry point returns GX_EINVAL.
+ * Errors: GX_EINVAL n outside [0, 2^31), a child index not below its parent, a column / literal index out of range, an operator
+ *   outside gx_ast_op or of the other arity, NULL where a pointer is needed with n > 0, a negative begin bit, a limit exceeded;
+ *   GX_EDTYPE an unknown dtype, operands of different dtypes, an operator that does not take the dtype, out_dtype != the result's.
+ * ------------------------------------------------------------------------------------------ */
+enum gx_ast_op {
+  GX_AST_ADD = 0, GX_AST_SUB = 1, GX_AST_MUL = 2, GX_AST_DIV = 3, GX_AST_TRUE_DIV = 4, GX_AST_FLOOR_DIV = 5, GX_AST_MOD = 6,
+  GX_AST_PYMOD = 7, GX_AST_POW = 8, GX_AST_EQUAL = 9, GX_AST_NULL_EQUAL = 10, GX_AST_NOT_EQUAL = 11, GX_AST_LESS = 12,
+  GX_AST_GREATER = 13, GX_AST_LESS_EQUAL = 14, GX_AST_GREATER_EQUAL = 15, GX_AST_BITWISE_AND = 16, GX_AST_BITWISE_OR = 17,
+  GX_AST_BITWISE_XOR = 18, GX_AST_LOGICAL_AND = 19, GX_AST_NULL_LOGICAL_AND = 20, GX_AST_LOGICAL_OR = 21,
+  GX_AST_NULL_LOGICAL_OR = 22, /* unary from here on */
+  GX_AST_IDENTITY = 23, GX_AST_IS_NULL = 24, GX_AST_SIN = 25, GX_AST_COS = 26, GX_AST_TAN = 27, GX_AST_ARCSIN = 28,
+  GX_AST_ARCCOS = 29, GX_AST_ARCTAN = 30, GX_AST_SINH = 31, GX_AST_COSH = 32, GX_AST_TANH = 33, GX_AST_ARCSINH = 34,
+  GX_AST_ARCCOSH = 35, GX_AST_ARCTANH = 36, GX_AST_EXP = 37, GX_AST_LOG = 38, GX_AST_SQRT = 39, GX_AST_CBRT = 40, GX_AST_CEIL = 41,
+  GX_AST_FLOOR = 42, GX_AST_ABS = 43, GX_AST_RINT = 44, GX_AST_BIT_INVERT = 45, GX_AST_NOT = 46, GX_AST_CAST_TO_INT64 = 47,
+  GX_AST_CAST_TO_UINT64 = 48, GX_AST_CAST_TO_FLOAT64 = 49
+};
+enum gx_expr_node_kind { GX_EXPR_COLUMN = 0, GX_EXPR_LITERAL = 1, GX_EXPR_UNARY = 2, GX_EXPR_BINARY = 3 };
+enum gx_expr_instr_kind { GX_EXPR_LOAD = 0, GX_EXPR_APPLY = 1, GX_EXPR_APPLY_REV = 2, GX_EXPR_APPLY_UNARY = 3, GX_EXPR_SPILL = 4 };
+enum gx_expr_src_kind { GX_EXPR_SRC_COLUMN = 0, GX_EXPR_SRC_LITERAL = 1, GX_EXPR_SRC_SLOT = 2 };
+typedef struct gx_expr_node {
+  int32_t kind; /* gx_expr_node_kind */
+  int32_t op;   /* gx_ast_op of UNARY / BINARY */
+  int32_t lhs;  /* column index, literal index, or the (left) child's node index */
+  int32_t rhs;  /* BINARY: the right child's node index */
+} gx_expr_node;
+typedef struct gx_expr_column {
+  const void* data;
+  const uint32_t* valid; /* NULL: no nulls */
+  int64_t begin_bit;     /* row i is bit begin_bit + i of valid */
+  int32_t dtype;
+  int32_t reserved;
+} gx_expr_column;
+typedef struct gx_expr_literal {
+  const void* value;    /* one element, device memory */
+  const uint8_t* valid; /* device byte, NULL: valid */
+  int32_t dtype;
+  int32_t reserved;
+} gx_expr_literal;
+typedef struct gx_expr_instr {
+  uint8_t kind;      /* gx_expr_instr_kind */
+  uint8_t op;        /* gx_ast_op of APPLY / APPLY_REV / APPLY_UNARY */
+  uint8_t src_kind;  /* gx_expr_src_kind of LOAD / APPLY / APPLY_REV */
+  uint8_t src_index; /* column, literal or slot; the slot written by SPILL */
+  uint8_t in_dtype;  /* dtype of the operands (LOAD: of src; SPILL: of the accumulator) */
+  uint8_t out_dtype; /* dtype of the accumulator afterwards */
+  uint8_t family;    /* for the kernel: operator family and the operator of that family (gx_binop / gx_unop) */
+  uint8_t family_op;
+} gx_expr_instr;
+int gx_compute_column(const gx_expr_node* nodes, int n_nodes, const gx_expr_column* cols, int n_cols, const gx_expr_literal* lits,
+                      int n_lits, int64_t n, int out_dtype, void* out, uint32_t* out_valid, int64_t* out_null_count_dev,
+                      gx_stream_t stream);
+/* host only: the root's dtype (> 0) or a gx_error */
+int gx_expr_result_dtype(const gx_expr_node* nodes, int n_nodes, const int32_t* col_dtypes, int n_cols, const int32_t* lit_dtypes,
+                         int n_lits);
+int gx_expr_plan(const gx_expr_node* nodes, int n_nodes, const int32_t* col_dtypes, int n_cols, const int32_t* lit_dtypes, int n_lits,
+                 gx_expr_instr* out_instructions, int capacity, int* n_instructions, int* n_slots); /* host only */
+void gx_expr_limits(int* max_nodes, int* max_columns, int* max_literals, int* max_slots);           /* host only */
+int gx_expression_tile_rows(void); /* rows one workgroup owns per trip */
+int gx_expression_grid_cap(void);  /* most workgroups of one launch */
+
+/* ------------------------------------------------------------------------------------------
  * Null and value replacement (cudf_amd/csrc/gx_replace.hip).  Replace the kernels of the reference's cpp/src/replace (nulls.cu,
  * nans.cu, clamp.cu, replace.cu).  All eleven gx_dtype (the functions that compare nothing take the element width in bytes, 1 / 2 /
  * 4 / 8); row counts lie in [0, 2^31).  Bitmaps are Arrow bitmaps read from their own begin bit on (a sliced view needs no
