@@ -34,8 +34,9 @@ constexpr int NRANGE     = 8;    // input ranges == XCDs: each gets its own look
 
 // How the key stream of a partition level is loaded: level 1 and the rescue pass read the level-0 slots, a use-once stream, with
 // NON-TEMPORAL loads, 16 bytes wide where a whole tile starts on a 16-byte boundary (3.64 -> 3.31 ms per 1e9 keys); level 0 reads the
-// caller's column with plain 8-byte loads (non-temporal loads cost it 0.5 ms, 16-byte loads gained nothing).  The other variants of
-// the three streaming kernels, measured per kernel in builds of their own and not kept: profiles/sort_load_policy_ab.txt.
+// caller's column with plain 8-byte loads (non-temporal loads cost it 0.5 ms, 16-byte loads gained nothing, and the two TOGETHER -- what
+// level 1 has -- cost the headline 0.42 ms: profiles/sort_level0_entry_vs_parent.txt, section 2).  The other variants of the three
+// streaming kernels, measured per kernel in builds of their own and not kept: profiles/sort_load_policy_ab.txt.
 typedef unsigned long long u64x2 __attribute__((ext_vector_type(2)));  // a 16-byte access of two 64-bit keys
 template <bool NT, typename T>
 __device__ __forceinline__ T stream_load(const T* p)
@@ -333,6 +334,8 @@ struct SortPlan {
 // tests/test_gpu_sort_level0_one_launch.py reads the LUT form the plan picked straight out of the caller's scratch, at this byte
 // (gx_sort_split_info reports splitter mode, not the form): keep the constant there in step with this one
 static_assert(offsetof(SortPlan, sp) + offsetof(SplitPlan, lut_log) == 166812, "SplitPlan::lut_log moved: update SP_LUT_FORM_BYTE in the test");
+// tests/test_gpu_sort_level0_entry.py reads the sign fold the same way (gx_sort_info does not report it)
+static_assert(offsetof(SortPlan, hy) + offsetof(HybridPlan, fold) == 98656, "HybridPlan::fold moved: update HY_FOLD_BYTE in the test");
 
 // level-0 digit of a sortable key: ((k >> shift0) & dm) | ((k >> fsh) & fhi), where (dm, fsh, fhi) = (0xFF, 0, 0), or
 // (0x7F, width - 8, 0x80) under the sign fold (HybridPlan::fold)
@@ -345,6 +348,29 @@ struct Digit0 {
 __device__ __forceinline__ Digit0 digit0_of(const HybridPlan& hy, int key_bits)
 {
   return hy.fold ? Digit0{hy.shift0, key_bits - 8, 0x7Fu, 0x80u} : Digit0{hy.shift0, 0, 0xFFu, 0u};
+}
+// The plan words a level-0 form needs BEFORE its first key load, read once at the kernel's entry (k_level0, k_hf_scatter<.., 0, 8>).
+// There nothing has written memory yet, so the compiler reads them with scalar loads, all behind one wait; the empty asm holds the
+// values in scalar registers at that point, so the loads cannot sink into a form's branch.  Read inside the forms of the merged
+// kernel, `fold` and `shift0` became VECTOR loads that every workgroup awaited (s_waitcnt vmcnt + v_readfirstlane) before it had
+// one key load in flight -- a round trip through a memory system that is streaming 16 B/row
+// (profiles/sort_level0_entry_isa.txt).  Words used behind the ranking (slot0, cap0, the cursors, the splitter tables) stay where they are.
+// (The splitter forms read `fold` and `shift0` without using them; float64 pays 0.04 ms per 1e9 rows that may be theirs: DESIGN.md section 8, row 11.)
+struct Level0Words {
+  int32_t state, sp_on;      // FastPlan::state, SplitPlan::on: which form runs, if any
+  int32_t fold, shift0;      // the bit digit (digit0_of) and the sign-fold check
+  int32_t slots_ready;       // splitter mode: k_hf_plan stage 1 has sized the slots
+  uint32_t lut_log;          // splitter mode: the LUT form (sp_level0_tile<.., 0 / 1>)
+};
+__device__ __forceinline__ Level0Words level0_words(const SortPlan* plan)
+{
+  Level0Words w{plan->hf.state, plan->sp.on, plan->hy.fold, plan->hy.shift0, plan->hf.slots_ready, plan->sp.lut_log};
+  asm volatile("" : "+s"(w.state), "+s"(w.sp_on), "+s"(w.fold), "+s"(w.shift0), "+s"(w.slots_ready), "+s"(w.lut_log));
+  return w;
+}
+__device__ __forceinline__ Digit0 digit0_of(const Level0Words& w, int key_bits)
+{
+  return w.fold ? Digit0{w.shift0, key_bits - 8, 0x7Fu, 0x80u} : Digit0{w.shift0, 0, 0xFFu, 0u};
 }
 // (sign fold) bits [h, sign) of every key are copies of its sign: h from OR(key ^ sign extension); 0 = do not fold
 __device__ __forceinline__ int fold_height(unsigned long long fold_or, unsigned long long V, int key_bits)
@@ -3206,8 +3232,10 @@ constexpr int hf_kpt()
 // its tiles).  Every thread of the workgroup calls it with the same tile; returns are block-uniform.
 template <typename KeyT, int KIND, int LVL, int NBL>
 __device__ __forceinline__ void hf_scatter_tile(const KeyT* __restrict__ in, KeyT* __restrict__ out, KeyT desc_mask, SortPlan* plan,
-                                                uint32_t* __restrict__ cellcur, int64_t n, KeyT* __restrict__ fin, int64_t vblock, int64_t nblocks)
+                                                uint32_t* __restrict__ cellcur, int64_t n, KeyT* __restrict__ fin, int64_t vblock, int64_t nblocks,
+                                                const Level0Words& w0 = Level0Words{})
 {
+  // w0 (level 0): the plan words read at the kernel's entry (Level0Words); the other levels do not look at it
   // fin (level 1, splitter mode): the sort's final output -- the keys of an EQUALITY bucket are copied straight to their place
   constexpr int KPT = hf_kpt<KeyT>(), TILE = BT * KPT, NB = 1 << NBL, BPT = NB > BT ? NB / BT : 1;
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -3221,8 +3249,11 @@ __device__ __forceinline__ void hf_scatter_tile(const KeyT* __restrict__ in, Key
   __shared__ uint2 s_wt[(LVL >= 1 && sizeof(KeyT) == 8) ? SP_NPIECE : 1];                  // splitter mode: the bucket's warp (sp_warp)
   HybridPlan& hy = plan->hy;
   FastPlan& hf   = plan->hf;
-  if (hf.state != (LVL == 0 ? 1 : 3)) return;
-  if (LVL == 0 && plan->sp.on) return;  // splitter mode: k_sp_level0 cuts the column
+  if constexpr (LVL == 0) {
+    if (w0.state != 1 || w0.sp_on) return;  // (splitter mode: sp_level0_tile cuts the column)
+  } else {
+    if (hf.state != 3) return;
+  }
   if (LVL == 2 && !(hy.ok && hy.lsd_mode)) return;
   const bool split     = LVL >= 1 && sizeof(KeyT) == 8 && plan->sp.on;  // (block-uniform) cells = equal-width slices of the bucket's range
   const uint32_t* xoff = cellcur + 2 * BINS * NB2MAX;  // LVL 2: first key of a big cell in X ...
@@ -3288,7 +3319,7 @@ __device__ __forceinline__ void hf_scatter_tile(const KeyT* __restrict__ in, Key
     nvalid            = (int)(rem < (int64_t)TILE ? rem : (int64_t)TILE);
   }
   const uint32_t dmask = LVL == 0 ? 0xFFu : ((1u << hy.bits2) - 1u);
-  const Digit0 dig     = LVL == 0 ? digit0_of(hy, (int)(8 * sizeof(KeyT))) : Digit0{hy.shift2, 0, dmask, 0u};
+  const Digit0 dig     = LVL == 0 ? digit0_of(w0, (int)(8 * sizeof(KeyT))) : Digit0{hy.shift2, 0, dmask, 0u};
   // the bucket's cell slots (HybridPlan::ccap / cbase), requested HERE: the two loads fly under the key loads and the ranking.
   // Asked for where they are used, next to the cursor atomics, they held the atomics back by a round trip per tile
   const uint32_t cap_s  = LVL >= 1 ? cell_cap(hy, seg) : 0u;
@@ -3389,7 +3420,7 @@ __device__ __forceinline__ void hf_scatter_tile(const KeyT* __restrict__ in, Key
       s_red[tid / GX_WAVE]      = wo;
       s_red[NW + tid / GX_WAVE] = wn;
     }
-    if (KIND == K_SIGNED && hy.fold) {  // the sign fold is verified on the exact OR of (key ^ sign extension)
+    if (KIND == K_SIGNED && w0.fold) {  // the sign fold is verified on the exact OR of (key ^ sign extension)
       KeyT vf = 0;
 #pragma unroll
       for (int j = 0; j < KPT; ++j) vf |= (KeyT)(key[j] ^ (KeyT)(KeyT(0) - (KeyT)(key[j] >> (8 * sizeof(KeyT) - 1))));
@@ -3527,6 +3558,9 @@ __global__ void __launch_bounds__(BT, 4) k_hf_scatter(const KeyT* __restrict__ i
       hf_scatter_tile<KeyT, KIND, LVL, NBL>(in, out, desc_mask, plan, cellcur, n, fin, (int64_t)t, (int64_t)ntiles);
       __syncthreads();  // the next tile reuses the LDS
     }
+  } else if constexpr (LVL == 0) {
+    const Level0Words w0 = level0_words(plan);
+    hf_scatter_tile<KeyT, KIND, LVL, NBL>(in, out, desc_mask, plan, cellcur, n, fin, (int64_t)blockIdx.x, (int64_t)gridDim.x, w0);
   } else {
     hf_scatter_tile<KeyT, KIND, LVL, NBL>(in, out, desc_mask, plan, cellcur, n, fin, (int64_t)blockIdx.x, (int64_t)gridDim.x);
   }
@@ -3707,10 +3741,13 @@ __device__ __forceinline__ void sp_level0_tile(const uint64_t* __restrict__ in, 
 // ---- level 0 of the cursor path behind ONE launch.  Its three forms -- the bit digit (hf_scatter_tile<.., 0, 8>) and the two LUT
 // forms of splitter mode (sp_level0_tile<.., 0 / 1>) -- are alternatives: the plan on the device picks one.  As three kernels, each
 // with a workgroup per tile, the two that returned at once cost 60 us each at 1e9 rows (139 509 workgroups dispatched for nothing):
-// 0.12 ms of the level-0 span between HIP events.  Splitter mode keeps 0.05 of it (4.49 -> 4.45 ms, float64 5.17 -> 5.11); the
-// bit-digit form inside this kernel runs 0.15 - 0.2 ms longer than as a kernel of its own -- same grid, same LDS, with or without
-// a pinned wave budget -- so the headline column's level 0 is where it was (profiles/sort_one_launch_vs_parent.txt, section 4).
-// Here the branch is taken once per workgroup, on the same plan words the three kernels tested (block-uniform: scalar branches).
+// 0.12 ms of the level-0 span between HIP events.  Splitter mode keeps 0.05 of it (4.49 -> 4.45 ms, float64 5.17 -> 5.11).  The
+// bit-digit form inside this kernel at first ran 0.15 - 0.2 ms longer than as a kernel of its own (profiles/sort_one_launch_vs_parent.txt,
+// section 4).  The cause was in the entry: inside the merged kernel the compiler read HybridPlan::fold and shift0 with VECTOR loads
+// and every workgroup waited for them before its first key load; the kernel of its own read them with scalar loads under the key
+// loads.  Now the plan words are read once, here, with scalar loads behind one wait (Level0Words), and level 0 of the headline
+// column takes 3.49 instead of 3.61 ms (profiles/sort_level0_entry_isa.txt, sort_level0_entry_vs_parent.txt).
+// The branch is taken once per workgroup, on the same plan words the three kernels tested (block-uniform: scalar branches).
 // Each form as a __noinline__ function instead (its own schedule by construction) saves and restores its callee-saved registers
 // around a call that never returns to anything: 140 - 172 B of scratch per lane, level 0 3.70 -> 4.50 ms, splitter mode 4.49 -> 6.95.
 // The forms cut the column into different tiles (8192 against SP_TILE = 7168 keys): the grid is the larger tile count, and each
@@ -3721,16 +3758,16 @@ template <typename KeyT, int KIND>
 __global__ void __launch_bounds__(BT, 4)
 k_level0(const KeyT* __restrict__ in, KeyT* __restrict__ out, KeyT desc_mask, SortPlan* plan, uint32_t* __restrict__ cellcur, int64_t n, int64_t nt_bit, int64_t nt_sp)
 {
-  const FastPlan& hf = plan->hf;
-  if (hf.state != 1) return;
+  const Level0Words w0 = level0_words(plan);
+  if (w0.state != 1) return;
   const int64_t b = (int64_t)blockIdx.x;
-  if (!plan->sp.on) {
-    if (b < nt_bit) hf_scatter_tile<KeyT, KIND, 0, 8>(in, out, desc_mask, plan, cellcur, n, (KeyT*)nullptr, b, nt_bit);
+  if (!w0.sp_on) {
+    if (b < nt_bit) hf_scatter_tile<KeyT, KIND, 0, 8>(in, out, desc_mask, plan, cellcur, n, (KeyT*)nullptr, b, nt_bit, w0);
     return;
   }
   if constexpr (sizeof(KeyT) == 8) {
-    if (!hf.slots_ready || b >= nt_sp) return;
-    if (plan->sp.lut_log == 2u) sp_level0_tile<KIND, 1>(in, out, desc_mask, plan, n, b, nt_sp);
+    if (!w0.slots_ready || b >= nt_sp) return;
+    if (w0.lut_log == 2u) sp_level0_tile<KIND, 1>(in, out, desc_mask, plan, n, b, nt_sp);
     else sp_level0_tile<KIND, 0>(in, out, desc_mask, plan, n, b, nt_sp);
   }
 }
