@@ -35,8 +35,12 @@ constexpr int NRANGE     = 8;    // input ranges == XCDs: each gets its own look
 // How the key stream of a partition level is loaded: level 1 and the rescue pass read the level-0 slots, a use-once stream, with
 // NON-TEMPORAL loads, 16 bytes wide where a whole tile starts on a 16-byte boundary (3.64 -> 3.31 ms per 1e9 keys); level 0 reads the
 // caller's column with plain 8-byte loads (non-temporal loads cost it 0.5 ms, 16-byte loads gained nothing, and the two TOGETHER -- what
-// level 1 has -- cost the headline 0.42 ms: profiles/sort_level0_entry_vs_parent.txt, section 2).  The other variants of the three
-// streaming kernels, measured per kernel in builds of their own and not kept: profiles/sort_load_policy_ab.txt.
+// level 1 has -- cost the headline 0.42 ms: profiles/sort_level0_entry_vs_parent.txt, section 2); the cell kernel reads its slot with
+// plain 8-byte loads (16-byte loads, plain and non-temporal, were built and lost: profiles/sort_key_requests_vs_parent.txt).  The other
+// variants of the three streaming kernels, measured per kernel in builds of their own and not kept: profiles/sort_load_policy_ab.txt.
+// What each kernel asks for BEFORE its key loads: level 0, level 1 and the cell kernel read their block-uniform plan words once at the
+// entry (Level0Words, Level1Words, CellWords); level 1 then needs one round trip for its region and one for the region's start and
+// the bucket's slots, the cell kernel one for the cell's size, slot and position (profiles/sort_cell_entry_isa.txt).
 typedef unsigned long long u64x2 __attribute__((ext_vector_type(2)));  // a 16-byte access of two 64-bit keys
 template <bool NT, typename T>
 __device__ __forceinline__ T stream_load(const T* p)
@@ -371,6 +375,22 @@ __device__ __forceinline__ Level0Words level0_words(const SortPlan* plan)
 __device__ __forceinline__ Digit0 digit0_of(const Level0Words& w, int key_bits)
 {
   return w.fold ? Digit0{w.shift0, key_bits - 8, 0x7Fu, 0x80u} : Digit0{w.shift0, 0, 0xFFu, 0u};
+}
+// The same for level 1 and the rescue pass (k_hf_scatter<.., 1 / 2, ..>): the words hf_scatter_tile tests or shifts by before its key
+// loads.  No workgroup of those launches writes any of them (hy.overflow, hy.bad and the cursors are other words).
+struct Level1Words {
+  int32_t state, sp_on;         // FastPlan::state, SplitPlan::on
+  int32_t ok, lsd_mode;         // the rescue pass runs only behind a plan with big cells
+  int32_t shift2, bits2;        // the level-1 digit
+  int32_t cell_max;             // fixed cell slots (ccap == 0)
+  uint32_t ext, ntiles;         // FastPlan::ext: the sharded sort's region table; else the tiles of the column's own regions
+};
+__device__ __forceinline__ Level1Words level1_words(const SortPlan* plan)
+{
+  Level1Words w{plan->hf.state, plan->sp.on, plan->hy.ok, plan->hy.lsd_mode, plan->hy.shift2, plan->hy.bits2, plan->hy.cell_max, plan->hf.ext,
+                plan->hf.reg_tile0[BINS * NRANGE]};
+  asm volatile("" : "+s"(w.state), "+s"(w.sp_on), "+s"(w.ok), "+s"(w.lsd_mode), "+s"(w.shift2), "+s"(w.bits2), "+s"(w.cell_max), "+s"(w.ext), "+s"(w.ntiles));
+  return w;
 }
 // (sign fold) bits [h, sign) of every key are copies of its sign: h from OR(key ^ sign extension); 0 = do not fold
 __device__ __forceinline__ int fold_height(unsigned long long fold_or, unsigned long long V, int key_bits)
@@ -1580,14 +1600,34 @@ __device__ __forceinline__ void pairs_write_out(KeyT* s_keys, const KeyT* __rest
 // LDS: the keys with one key of padding per 16 (a thread's window is 17 keys from its neighbour's: conflict-free 8-byte
 // accesses) + one byte per bin + one bin-group base per thread + scan words = 78.1 KiB for 8192-key cells (two workgroups
 // per CU), 156.1 KiB for 16384-key cells (float keys, pairs above 1.02e9 rows: one workgroup per CU, as k_local_sort).
+// The plan words the cell kernel needs BEFORE a cell's first key load, read once at the kernel's entry (the mechanism of Level0Words:
+// scalar loads, all behind one wait, held in scalar registers by the empty asm) and handed to the cells as values.  Read where they
+// are used they were six scalar round trips at the entry, one behind each short-circuit test, and -- inside the cell loop, which
+// stores and adds atomically -- vector loads that every cell awaited ahead of its size and slot
+// (profiles/sort_cell_entry_isa.txt).  Only words that no workgroup of this launch writes: hy.todo_count stays an atomic in the plan.
+struct CellWords {
+  int32_t attempt, ok;       // HybridPlan: the hybrid path sorted down to cells
+  int32_t state;             // FastPlan::state: 3 = the cursor path's cells, else the look-back path's
+  int32_t cell_max, nlocal;  // the cell size this launch is for; LDS passes of the stable fallback (0: no placement)
+  int32_t shift2, bits2;     // the level-1 digit: what is left for the cell sort, cells per bucket
+  int32_t sp_on;             // SplitPlan::on: the SPLIT form of the cells
+};
+__device__ __forceinline__ CellWords cell_words(const SortPlan* plan)
+{
+  CellWords w{plan->hy.attempt, plan->hy.ok, plan->hf.state, plan->hy.cell_max, plan->hy.nlocal, plan->hy.shift2, plan->hy.bits2, plan->sp.on};
+  asm volatile("" : "+s"(w.attempt), "+s"(w.ok), "+s"(w.state), "+s"(w.cell_max), "+s"(w.nlocal), "+s"(w.shift2), "+s"(w.bits2), "+s"(w.sp_on));
+  return w;
+}
 template <typename KeyT, int KIND, bool HAS_VAL, int CL2>
-__device__ __forceinline__ bool place_applies(const HybridPlan& hy, int exp)
+__device__ __forceinline__ bool place_applies(int shift2, int nlocal, int exp)
 {
   // packed words: pairs always (k_hy_plan's pos_bits rule), float keys when the position fits next to the key bits
   constexpr bool PACKED = HAS_VAL || KIND == K_FLOAT;
-  const int word_bits   = hy.shift2 + (PACKED ? CL2 : 0);
-  return hy.nlocal > 0 && !(exp & (32 | 16 | 8 | 4)) && word_bits >= CL2 && word_bits <= 64;
+  const int word_bits   = shift2 + (PACKED ? CL2 : 0);
+  return nlocal > 0 && !(exp & (32 | 16 | 8 | 4)) && word_bits >= CL2 && word_bits <= 64;
 }
+template <typename KeyT, int KIND, bool HAS_VAL, int CL2>
+__device__ __forceinline__ bool place_applies(const CellWords& w, int exp) { return place_applies<KeyT, KIND, HAS_VAL, CL2>(w.shift2, w.nlocal, exp); }
 // word of the cell sort: 8 bytes for 64-bit keys and for every packed (key bits, position) word; 32-bit integer keys travel as they are
 template <typename KeyT, int KIND, bool HAS_VAL>
 struct PlaceWord {
@@ -1602,33 +1642,38 @@ constexpr size_t place_lds_bytes(int cl2, int word_bytes = 8)
 struct CellMeta {
   uint32_t m, cap, slot, start;
 };
-__device__ __forceinline__ CellMeta cell_meta(const HybridPlan& hy, const uint32_t* __restrict__ hist2, const uint32_t* __restrict__ base2, uint32_t cell)
+// ONE batch: the four words are requested back to back, unconditionally (cell_slot reads cbase[b] behind its test of ccap[b]: a round
+// trip of its own), and the empty asm makes them block-uniform values in scalar registers before any is used -- nothing is left that
+// a later store or atomic of the cell loop could make the compiler fetch again between here and the key loads
+__device__ __forceinline__ CellMeta cell_meta(const CellWords& w, const HybridPlan& hy, const uint32_t* __restrict__ hist2, const uint32_t* __restrict__ base2,
+                                              uint32_t cell)
 {
-  const uint32_t b = cell >> hy.bits2, d2 = cell & ((1u << hy.bits2) - 1u);
-  return CellMeta{hist2[b * NB2MAX + d2], cell_cap(hy, b), cell_slot(hy, b, d2), base2[b * NB2MAX + d2]};
+  const uint32_t b = cell >> w.bits2, d2 = cell & ((1u << w.bits2) - 1u);
+  const uint32_t lm = hist2[b * NB2MAX + d2], lstart = base2[b * NB2MAX + d2], lccap = hy.ccap[b], lcbase = hy.cbase[b];
+  // (inside the cell loop these are vector loads: the cell is the same in every lane, said so)
+  uint32_t m = (uint32_t)__builtin_amdgcn_readfirstlane((int)lm), start = (uint32_t)__builtin_amdgcn_readfirstlane((int)lstart);
+  uint32_t ccap = (uint32_t)__builtin_amdgcn_readfirstlane((int)lccap), cbase = (uint32_t)__builtin_amdgcn_readfirstlane((int)lcbase);
+  asm volatile("" : "+s"(m), "+s"(start), "+s"(ccap), "+s"(cbase));
+  return CellMeta{m, ccap ? ccap : (uint32_t)w.cell_max, ccap ? cbase + d2 * ccap : cell * (uint32_t)w.cell_max, start};
 }
 // one cell of k_local_place (every thread of the workgroup calls it with the same cell; returns are block-uniform)
-// (pre: the cell's CellMeta when the caller has it already -- splitter mode asks for both of its slots' at once)
+// w: the plan words of the kernel's entry (CellWords); cm: the cell's size, slot and output position (cell_meta: one batch -- splitter
+// mode asks for both of its slots' at once)
 template <typename KeyT, int KIND, bool HAS_VAL, int CL2, bool SPLIT = false>
 __device__ __forceinline__ void local_place_cell(const uint32_t cell, const KeyT* in, KeyT* __restrict__ out, const uint32_t* vin,
-                                                 uint32_t* __restrict__ vout, KeyT desc_mask, SortPlan* plan,
-                                                 const uint32_t* __restrict__ hist2, const uint32_t* __restrict__ base2,
-                                                 uint32_t* __restrict__ todo, int exp, const CellMeta* pre = nullptr)
+                                                 uint32_t* __restrict__ vout, KeyT desc_mask, SortPlan* plan, const CellWords& w,
+                                                 uint32_t* __restrict__ todo, int exp, const CellMeta& cm)
 {
   constexpr int LOCAL_MAX = 1 << CL2, LS_KPT = 16, LS_BT = LOCAL_MAX / LS_KPT, NPB = 1 << CL2;
   constexpr bool PACKED = HAS_VAL || KIND == K_FLOAT;
   typedef typename PlaceWord<KeyT, KIND, HAS_VAL>::type WordT;  // what goes through LDS and the networks
   static_assert(!PACKED || sizeof(KeyT) == 8, "packed words: 64-bit keys");
   HybridPlan& hy = plan->hy;
-  const int bits2 = hy.bits2;
-  const uint32_t b  = cell >> bits2;
-  const uint32_t d2 = cell & ((1u << bits2) - 1u);
-  // (the cell's size, output position and slot are requested together: behind the size check the slot lookup would be a second
-  //  round trip before the first key load)
-  const uint32_t m    = pre ? pre->m : hist2[b * NB2MAX + d2];
-  const uint32_t cap  = pre ? pre->cap : cell_cap(hy, b);
-  const uint32_t slot = pre ? pre->slot : cell_slot(hy, b, d2);
-  const int64_t start = pre ? pre->start : base2[b * NB2MAX + d2];
+  const uint32_t b    = cell >> w.bits2;
+  const uint32_t m    = cm.m;
+  const uint32_t cap  = cm.cap;
+  const uint32_t slot = cm.slot;
+  const int64_t start = cm.start;
   if (m == 0 || m > cap) return;  // (a big cell -- cursor path only -- is sorted through X, see HybridPlan::big)
   in += (int64_t)slot - start;  // the cell sits in its slot of the level-1 buffer
   if (HAS_VAL) vin += (int64_t)slot - start;
@@ -1640,7 +1685,7 @@ __device__ __forceinline__ void local_place_cell(const uint32_t cell, const KeyT
   const unsigned tid  = threadIdx.x;
   const unsigned lane = lane_id();
   const int wbase     = (int)(tid / GX_WAVE) * (LS_KPT * GX_WAVE) + (int)lane;
-  const int shift2    = hy.shift2;
+  const int shift2    = w.shift2;
   const int dshift    = shift2 + (PACKED ? CL2 : 0) - CL2;
   // SPLIT (splitter mode, plain 64-bit keys): the counting digit is the CL2 bits of the key's position inside its bucket's range
   // that follow the cell's own (equal-width sub-slices of the cell; monotone, which is all the placement needs)
@@ -1656,6 +1701,7 @@ __device__ __forceinline__ void local_place_cell(const uint32_t cell, const KeyT
   if constexpr (SPLIT) {
     if (tid < (unsigned)SP_NPIECE) s_wt[tid] = plan->sp.wt[b][tid];
   }
+  // (plain 8-byte loads: 16-byte loads, plain and non-temporal, were built and measured and lost to these: profiles/sort_key_requests_vs_parent.txt)
   WordT key[LS_KPT];
 #pragma unroll
   for (int j = 0; j < LS_KPT; ++j) {
@@ -1773,20 +1819,25 @@ __device__ __forceinline__ void local_place_cell(const uint32_t cell, const KeyT
 }
 
 // The workgroups walk the cells with a stride (gridDim.x = the number of cells: one cell each, the default; a smaller grid is
-// the persistent form, A/B knob gx_sort_set_place_grid).
+// the persistent form, A/B knob gx_sort_set_place_grid).  A cell's keys are three round trips from the launch: the arguments and the
+// plan words (CellWords, read once here -- the walk and the cells see values, never the plan), the cell's metadata (cell_meta: one
+// batch), the keys.
 template <typename KeyT, int KIND, bool HAS_VAL, int CL2>
 __global__ void __launch_bounds__((1 << CL2) / 16, 4) k_local_place(const KeyT* in, KeyT* __restrict__ out, const uint32_t* vin,
                                                                     uint32_t* __restrict__ vout, KeyT desc_mask, SortPlan* plan,
                                                                     const uint32_t* __restrict__ hist2, const uint32_t* __restrict__ base2,
                                                                     uint32_t* __restrict__ todo, int exp, int cursor_path)
 {
-  HybridPlan& hy = plan->hy;
-  if (!hy.attempt || !hy.ok || (plan->hf.state == 3) != (cursor_path != 0)) return;
-  if (hy.cell_max != (1 << CL2)) return;  // (both cell sizes are launched when the device may choose: see k_hy_plan's cell_alt)
-  if (!place_applies<KeyT, KIND, HAS_VAL, CL2>(hy, exp)) return;  // k_local_sort, launched behind, takes every cell
-  const uint32_t ncells = (uint32_t)BINS << hy.bits2;
+  const uint32_t stride = gridDim.x;
+  // the plan words, once (CellWords): the early returns below test values, in the order they tested the plan
+  const CellWords w = cell_words(plan);
+  HybridPlan& hy    = plan->hy;
+  if (!w.attempt || !w.ok || (w.state == 3) != (cursor_path != 0)) return;
+  if (w.cell_max != (1 << CL2)) return;  // (both cell sizes are launched when the device may choose: see k_hy_plan's cell_alt)
+  if (!place_applies<KeyT, KIND, HAS_VAL, CL2>(w, exp)) return;  // k_local_sort, launched behind, takes every cell
+  const uint32_t ncells = (uint32_t)BINS << w.bits2;
   constexpr bool CAN_SPLIT = sizeof(KeyT) == 8 && !HAS_VAL && KIND != K_FLOAT && CL2 == 13;
-  if (CAN_SPLIT && cursor_path && plan->sp.on) {  // (block-uniform; an instantiation of its own: the bit-digit path is untouched)
+  if (CAN_SPLIT && cursor_path && w.sp_on) {  // (block-uniform; an instantiation of its own: the bit-digit path is untouched)
     if constexpr (CAN_SPLIT) {
       // a bucket uses the FIRST nc of its 1 << bits2 cell slots (about half of them: the grid is sized for half the slots), so the two
       // slots of a workgroup must not be the same cell index of two buckets -- both used or both empty: until run 14 half the
@@ -1797,30 +1848,31 @@ __global__ void __launch_bounds__((1 << CL2) / 16, 4) k_local_place(const KeyT* 
       // digits, 1400 per wave -- the 0.9 ms this stage took longer in splitter mode).
       // (odd rounds visit cell ^ flip -- a permutation of the round's cells only when the grid is a whole number of buckets: the default
       //  grid is; a grid from the A/B knob gx_sort_set_place_grid that is not walks linearly -- ADVICE r5: some cells twice, others never)
-      const uint32_t flip = (gridDim.x % (1u << hy.bits2)) == 0u ? (1u << hy.bits2) - 1u : 0u;
-      const uint32_t c0 = blockIdx.x, c1 = blockIdx.x + gridDim.x;  // (c0 < ncells: the grid is never larger than the slots)
+      const uint32_t flip = (stride % (1u << w.bits2)) == 0u ? (1u << w.bits2) - 1u : 0u;
+      const uint32_t c0 = blockIdx.x, c1 = blockIdx.x + stride;  // (c0 < ncells: the grid is never larger than the slots)
       const bool two    = c1 < ncells;
       const uint32_t s1 = two ? (c1 ^ flip) : c0;
-      const CellMeta m0 = cell_meta(hy, hist2, base2, c0);
-      const CellMeta m1 = cell_meta(hy, hist2, base2, s1);
+      const CellMeta m0 = cell_meta(w, hy, hist2, base2, c0);
+      const CellMeta m1 = cell_meta(w, hy, hist2, base2, s1);
       if (m0.m != 0u) {  // (block-uniform)
-        local_place_cell<KeyT, KIND, HAS_VAL, CL2, true>(c0, in, out, vin, vout, desc_mask, plan, hist2, base2, todo, exp, &m0);
+        local_place_cell<KeyT, KIND, HAS_VAL, CL2, true>(c0, in, out, vin, vout, desc_mask, plan, w, todo, exp, m0);
         __syncthreads();
       }
       if (two && m1.m != 0u) {
-        local_place_cell<KeyT, KIND, HAS_VAL, CL2, true>(s1, in, out, vin, vout, desc_mask, plan, hist2, base2, todo, exp, &m1);
+        local_place_cell<KeyT, KIND, HAS_VAL, CL2, true>(s1, in, out, vin, vout, desc_mask, plan, w, todo, exp, m1);
         __syncthreads();
       }
       uint32_t round = 2;  // (a smaller grid -- the A/B knob gx_sort_set_place_grid -- walks on)
-      for (uint32_t cell = blockIdx.x + 2u * gridDim.x; cell < ncells && cell >= 2u * gridDim.x; cell += gridDim.x, ++round) {
-        local_place_cell<KeyT, KIND, HAS_VAL, CL2, true>((round & 1u) ? (cell ^ flip) : cell, in, out, vin, vout, desc_mask, plan, hist2, base2, todo, exp);
+      for (uint32_t cell = blockIdx.x + 2u * stride; cell < ncells && cell >= 2u * stride; cell += stride, ++round) {
+        const uint32_t c = (round & 1u) ? (cell ^ flip) : cell;
+        local_place_cell<KeyT, KIND, HAS_VAL, CL2, true>(c, in, out, vin, vout, desc_mask, plan, w, todo, exp, cell_meta(w, hy, hist2, base2, c));
         __syncthreads();
       }
     }
     return;
   }
-  for (uint32_t cell = blockIdx.x; cell < ncells; cell += gridDim.x) {
-    local_place_cell<KeyT, KIND, HAS_VAL, CL2>(cell, in, out, vin, vout, desc_mask, plan, hist2, base2, todo, exp);
+  for (uint32_t cell = blockIdx.x; cell < ncells; cell += stride) {
+    local_place_cell<KeyT, KIND, HAS_VAL, CL2>(cell, in, out, vin, vout, desc_mask, plan, w, todo, exp, cell_meta(w, hy, hist2, base2, cell));
     __syncthreads();  // the next cell reuses the LDS
   }
 }
@@ -2109,7 +2161,7 @@ __global__ void __launch_bounds__((1 << CL2) / 16, 4) k_local_sort(const IoT* in
   HybridPlan& hy = plan->hy;
   if (!hy.attempt || !hy.ok || (plan->hf.state == 3) != (cursor_path != 0)) return;
   if (hy.cell_max != (1 << CL2)) return;
-  const bool listed    = todo != nullptr && place_applies<IoT, KIND, HAS_VAL, CL2>(hy, exp);  // (as k_local_place decided: on the column's type)
+  const bool listed    = todo != nullptr && place_applies<IoT, KIND, HAS_VAL, CL2>(hy.shift2, hy.nlocal, exp);  // (as k_local_place decided: on the column's type)
   const uint32_t count = listed ? hy.todo_count : ((uint32_t)BINS << hy.bits2);
   for (uint32_t e = blockIdx.x; e < count; e += gridDim.x) {
     local_sort_cell<KeyT, KIND, HAS_VAL, CL2, IoT>(listed ? todo[e] : e, in, out, vin, vout, desc_mask_in, plan, hist2, base2, exp);
@@ -3233,9 +3285,9 @@ constexpr int hf_kpt()
 template <typename KeyT, int KIND, int LVL, int NBL>
 __device__ __forceinline__ void hf_scatter_tile(const KeyT* __restrict__ in, KeyT* __restrict__ out, KeyT desc_mask, SortPlan* plan,
                                                 uint32_t* __restrict__ cellcur, int64_t n, KeyT* __restrict__ fin, int64_t vblock, int64_t nblocks,
-                                                const Level0Words& w0 = Level0Words{})
+                                                const Level0Words& w0 = Level0Words{}, const Level1Words& w1 = Level1Words{})
 {
-  // w0 (level 0): the plan words read at the kernel's entry (Level0Words); the other levels do not look at it
+  // w0 (level 0) / w1 (level 1, rescue pass): the plan words read at the kernel's entry (Level0Words, Level1Words); a level looks at its own only
   // fin (level 1, splitter mode): the sort's final output -- the keys of an EQUALITY bucket are copied straight to their place
   constexpr int KPT = hf_kpt<KeyT>(), TILE = BT * KPT, NB = 1 << NBL, BPT = NB > BT ? NB / BT : 1;
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -3252,10 +3304,10 @@ __device__ __forceinline__ void hf_scatter_tile(const KeyT* __restrict__ in, Key
   if constexpr (LVL == 0) {
     if (w0.state != 1 || w0.sp_on) return;  // (splitter mode: sp_level0_tile cuts the column)
   } else {
-    if (hf.state != 3) return;
+    if (w1.state != 3) return;
   }
-  if (LVL == 2 && !(hy.ok && hy.lsd_mode)) return;
-  const bool split     = LVL >= 1 && sizeof(KeyT) == 8 && plan->sp.on;  // (block-uniform) cells = equal-width slices of the bucket's range
+  if (LVL == 2 && !(w1.ok && w1.lsd_mode)) return;
+  const bool split     = LVL >= 1 && sizeof(KeyT) == 8 && w1.sp_on;  // (block-uniform) cells = equal-width slices of the bucket's range
   const uint32_t* xoff = cellcur + 2 * BINS * NB2MAX;  // LVL 2: first key of a big cell in X ...
   uint32_t* rescur     = cellcur + 3 * BINS * NB2MAX;  // ... and the rescue cursors (hist2 | base2 | xoff | rescur)
   const unsigned tid = threadIdx.x;
@@ -3263,22 +3315,29 @@ __device__ __forceinline__ void hf_scatter_tile(const KeyT* __restrict__ in, Key
   int64_t base;
   int nvalid;
   uint32_t seg;
+  uint32_t cap_s = 0u, base_s = 0u;  // levels 1 and 2: the bucket's cell slots (HybridPlan::ccap / cbase)
   if (LVL == 0) {
     const int64_t per = nblocks / NRANGE;  // whole tiles per range (the last range takes the rest)
     seg               = (per > 0 && v / per < NRANGE - 1) ? (uint32_t)(v / per) : (uint32_t)(NRANGE - 1);
     base              = v * TILE;
     nvalid            = (int)(n - base < (int64_t)TILE ? n - base : (int64_t)TILE);
-  } else if (!hf.ext) {
+  } else if (!w1.ext) {
     // the column's own regions (bucket, input range): a table inside the plan, every address below is known at launch
-    if (v >= (int64_t)hf.reg_tile0[BINS * NRANGE]) return;
+    if (v >= (int64_t)w1.ntiles) return;
+    // ONE round trip for the lookup: a thread's QPT consecutive entries and the one behind them are requested together and held
+    // (the empty asm) before any is compared.  Written as `lo <= v && v < hi` per entry it compiled to load lo, wait, branch, load hi,
+    // wait -- four to five serial round trips per tile (profiles/sort_cell_entry_isa.txt).  An empty region (lo == hi) never matches.
     constexpr int QPT = BINS * NRANGE / BT;  // region table entries per thread
+    static_assert(QPT == 4, "the region lookup holds QPT + 1 = 5 table entries");
+    uint32_t t0 = hf.reg_tile0[tid * QPT], t1 = hf.reg_tile0[tid * QPT + 1], t2 = hf.reg_tile0[tid * QPT + 2], t3 = hf.reg_tile0[tid * QPT + 3],
+             t4 = hf.reg_tile0[tid * QPT + 4];
+    asm volatile("" : "+v"(t0), "+v"(t1), "+v"(t2), "+v"(t3), "+v"(t4));
+    const uint32_t te[QPT + 1] = {t0, t1, t2, t3, t4};
 #pragma unroll
     for (int k = 0; k < QPT; ++k) {
-      const int q       = (int)tid * QPT + k;
-      const uint32_t lo = hf.reg_tile0[q], hi = hf.reg_tile0[q + 1];
-      if ((int64_t)lo <= v && v < (int64_t)hi) {
-        s_misc[0] = (uint32_t)q;
-        s_misc[1] = (uint32_t)(v - lo);
+      if ((int64_t)te[k] <= v && v < (int64_t)te[k + 1]) {
+        s_misc[0] = tid * QPT + (uint32_t)k;
+        s_misc[1] = (uint32_t)(v - te[k]);
       }
     }
     __syncthreads();
@@ -3288,10 +3347,19 @@ __device__ __forceinline__ void hf_scatter_tile(const KeyT* __restrict__ in, Key
       q  = (uint32_t)__builtin_amdgcn_readfirstlane((int)q);
       jt = (uint32_t)__builtin_amdgcn_readfirstlane((int)jt);
     }
-    seg               = q / NRANGE;  // the level-0 bucket
-    if (LVL == 2 && !hy.bigbucket[seg]) return;  // (block-uniform: nothing of this bucket is needed again)
-    base              = (int64_t)hf.reg_start[q] + (int64_t)jt * TILE;
-    const int64_t rem = (int64_t)hf.reg_count[q] - (int64_t)jt * TILE;
+    seg = q / NRANGE;  // the level-0 bucket
+    // ONE further batch: the region's start and size and the bucket's slot words (cell_slot reads cbase behind its test of ccap), all
+    // requested before the first is used.  The slot words fly under the key loads and the ranking as before -- asked for next to the
+    // cursor atomics they held the atomics back by a round trip per tile
+    uint32_t rstart = hf.reg_start[q], rcount = hf.reg_count[q], ccap = hy.ccap[seg], cbase = hy.cbase[seg];
+    uint32_t bigb   = LVL == 2 ? hy.bigbucket[seg] : 1u;
+    asm volatile("" : "+v"(rstart), "+v"(rcount), "+v"(ccap), "+v"(cbase), "+v"(bigb));
+    if constexpr (LVL == 2) bigb = (uint32_t)__builtin_amdgcn_readfirstlane((int)bigb);
+    if (LVL == 2 && !bigb) return;  // (block-uniform: nothing of this bucket is needed again)
+    cap_s             = ccap ? ccap : (uint32_t)w1.cell_max;
+    base_s            = ccap ? cbase : (seg << w1.bits2) * (uint32_t)w1.cell_max;
+    base              = (int64_t)rstart + (int64_t)jt * TILE;
+    const int64_t rem = (int64_t)rcount - (int64_t)jt * TILE;
     nvalid            = (int)(rem < (int64_t)TILE ? rem : (int64_t)TILE);
   } else {
     // the sharded sort's receive area (gx_sortx_finish): regions (bucket, source rank, input range) in an external table
@@ -3317,13 +3385,13 @@ __device__ __forceinline__ void hf_scatter_tile(const KeyT* __restrict__ in, Key
     base              = (int64_t)hf.x_start[q] + (int64_t)jt * TILE;
     const int64_t rem = (int64_t)hf.x_count[q] - (int64_t)jt * TILE;
     nvalid            = (int)(rem < (int64_t)TILE ? rem : (int64_t)TILE);
+    // the bucket's cell slots, requested HERE: the two loads fly under the key loads and the ranking.  Asked for where they are used,
+    // next to the cursor atomics, they held the atomics back by a round trip per tile
+    cap_s  = cell_cap(hy, seg);
+    base_s = cell_slot(hy, seg, 0u);
   }
-  const uint32_t dmask = LVL == 0 ? 0xFFu : ((1u << hy.bits2) - 1u);
-  const Digit0 dig     = LVL == 0 ? digit0_of(w0, (int)(8 * sizeof(KeyT))) : Digit0{hy.shift2, 0, dmask, 0u};
-  // the bucket's cell slots (HybridPlan::ccap / cbase), requested HERE: the two loads fly under the key loads and the ranking.
-  // Asked for where they are used, next to the cursor atomics, they held the atomics back by a round trip per tile
-  const uint32_t cap_s  = LVL >= 1 ? cell_cap(hy, seg) : 0u;
-  const uint32_t base_s = LVL >= 1 ? cell_slot(hy, seg, 0u) : 0u;
+  const uint32_t dmask = LVL == 0 ? 0xFFu : ((1u << w1.bits2) - 1u);
+  const Digit0 dig     = LVL == 0 ? digit0_of(w0, (int)(8 * sizeof(KeyT))) : Digit0{w1.shift2, 0, dmask, 0u};
   SpCell spc{0ull, 1ull, 0u, 63};
   if (split) {
     if (plan->sp.eq[seg]) {  // an equality bucket (block-uniform): every key is the same value -- no cells, no cell sort
@@ -3346,7 +3414,7 @@ __device__ __forceinline__ void hf_scatter_tile(const KeyT* __restrict__ in, Key
     if constexpr (sizeof(KeyT) == 8) return sp_cell(sp_warp(sp_frac(spc, (unsigned long long)k), s_wt), spnc);
     else return dig(k);
   };
-  if (split && sp_narrow(plan->sp, seg, hy.bits2)) {
+  if (split && sp_narrow(plan->sp, seg, w1.bits2)) {
     // a NARROW bucket (block-uniform): no more values in its range than it has cells, so every cell holds ONE value and the cell
     // sizes are all there is to know -- count (LDS histogram, one atomic per non-empty cell), nothing is moved; k_sp_fill writes
     // the bucket's output from the counts.  (Zipf-like columns: a third of the keys are values of 10^4 - 10^6 copies each.)
@@ -3553,16 +3621,18 @@ __global__ void __launch_bounds__(BT, 4) k_hf_scatter(const KeyT* __restrict__ i
                                                      uint32_t ntiles = 0)
 {
   if constexpr (LVL == 2) {
-    if (plan->hf.state != 3 || !(plan->hy.ok && plan->hy.lsd_mode)) return;
+    const Level1Words w1 = level1_words(plan);
+    if (w1.state != 3 || !(w1.ok && w1.lsd_mode)) return;
     for (uint32_t t = blockIdx.x; t < ntiles; t += gridDim.x) {
-      hf_scatter_tile<KeyT, KIND, LVL, NBL>(in, out, desc_mask, plan, cellcur, n, fin, (int64_t)t, (int64_t)ntiles);
+      hf_scatter_tile<KeyT, KIND, LVL, NBL>(in, out, desc_mask, plan, cellcur, n, fin, (int64_t)t, (int64_t)ntiles, Level0Words{}, w1);
       __syncthreads();  // the next tile reuses the LDS
     }
   } else if constexpr (LVL == 0) {
     const Level0Words w0 = level0_words(plan);
     hf_scatter_tile<KeyT, KIND, LVL, NBL>(in, out, desc_mask, plan, cellcur, n, fin, (int64_t)blockIdx.x, (int64_t)gridDim.x, w0);
   } else {
-    hf_scatter_tile<KeyT, KIND, LVL, NBL>(in, out, desc_mask, plan, cellcur, n, fin, (int64_t)blockIdx.x, (int64_t)gridDim.x);
+    const Level1Words w1 = level1_words(plan);
+    hf_scatter_tile<KeyT, KIND, LVL, NBL>(in, out, desc_mask, plan, cellcur, n, fin, (int64_t)blockIdx.x, (int64_t)gridDim.x, Level0Words{}, w1);
   }
 }
 
