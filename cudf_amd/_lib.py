@@ -62,7 +62,7 @@ class ExprNode(ctypes.Structure):
 
 class ExprColumn(ctypes.Structure):
     _fields_ = [("data", ctypes.c_void_p), ("valid", ctypes.c_void_p), ("begin_bit", ctypes.c_int64), ("dtype", ctypes.c_int32),
-                ("reserved", ctypes.c_int32)]
+                ("table", ctypes.c_int32)]
 
 
 class ExprLiteral(ctypes.Structure):
@@ -253,6 +253,15 @@ _PROTOS = {
     "gx_expr_limits": (None, [_pi, _pi, _pi, _pi]),
     "gx_expression_tile_rows": (_i, []),
     "gx_expression_grid_cap": (_i, []),
+    # conditional joins (gx_conditional_join.hip): the same program over row pairs; count (scratch) then write
+    "gx_conditional_join_count": (_i, [ctypes.POINTER(ExprNode), _i, ctypes.POINTER(ExprColumn), _i, ctypes.POINTER(ExprLiteral), _i, _i64,
+                                       _i64, _i, _p, _p, _sz, _p]),
+    "gx_conditional_join_write": (_i, [ctypes.POINTER(ExprNode), _i, ctypes.POINTER(ExprColumn), _i, ctypes.POINTER(ExprLiteral), _i, _i64,
+                                       _i64, _i, _i64, _i64, _p, _p, _p, _p]),
+    "gx_conditional_join_tile": (None, [_pi, _pi]),
+    "gx_conditional_join_grid_cap": (_i, []),
+    "gx_conditional_join_pairs_per_run": (_i, []),
+    "gx_conditional_join_set_shape": (_i, [_i, _i, _i]),
     # null and value replacement (gx_replace.hip): streaming passes; only the policy fill has scratch (its carry table)
     "gx_replace_tile_rows": (_i, []),
     "gx_find_and_replace_chunk": (_i, []),

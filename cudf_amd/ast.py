@@ -19,12 +19,16 @@ class Expression:
 
 
 class ColumnReference(Expression):
-    __slots__ = ("index",)
+    """column `index` of the table `table`: "left" (the one table of compute_column) or "right" (the other side of a conditional join)"""
+    __slots__ = ("index", "table")
 
-    def __init__(self, index: int):
+    def __init__(self, index: int, table: str = "left"):
         if int(index) != index or index < 0:
             raise ValueError(f"column index {index!r} must be a non-negative integer")
+        if table not in ("left", "right"):
+            raise ValueError(f"table {table!r} must be 'left' or 'right'")
         self.index = int(index)
+        self.table = table
 
 
 class Literal(Expression):
@@ -68,11 +72,20 @@ class Operation(Expression):
 
 def flatten(expr: Expression) -> Tuple[List[Tuple[int, int, int, int]], List[int], List[Literal]]:
     """(nodes, column indices, literals): nodes are (kind, op, lhs, rhs) in post order, the root last; a COLUMN node's lhs indexes
-    `column indices` (the distinct table columns the expression reads, in first-use order), a LITERAL node's lhs `literals`"""
+    `column indices` (the distinct table columns the expression reads, in first-use order), a LITERAL node's lhs `literals`.
+    ValueError for a reference to the right table: there is one table here (flatten_pair takes two)"""
+    nodes, columns, literals = flatten_pair(expr)
+    if any(table == "right" for table, _ in columns):
+        raise ValueError("the expression refers to the right table: only a conditional join has one")
+    return nodes, [index for _, index in columns], literals
+
+
+def flatten_pair(expr: Expression) -> Tuple[List[Tuple[int, int, int, int]], List[Tuple[str, int]], List[Literal]]:
+    """flatten for a predicate over two tables: the columns are (table, index) pairs, "left" / "right", in first-use order"""
     if not isinstance(expr, Expression):
         raise TypeError(f"{expr!r} is not an expression")
     nodes: List[Tuple[int, int, int, int]] = []
-    columns: List[int] = []
+    columns: List[Tuple[str, int]] = []
     literals: List[Literal] = []
     seen = {}
 
@@ -80,9 +93,10 @@ def flatten(expr: Expression) -> Tuple[List[Tuple[int, int, int, int]], List[int
         if id(e) in seen:
             return seen[id(e)]
         if isinstance(e, ColumnReference):
-            if e.index not in columns:
-                columns.append(e.index)
-            node = (L.EXPR_COLUMN, 0, columns.index(e.index), 0)
+            key = (e.table, e.index)
+            if key not in columns:
+                columns.append(key)
+            node = (L.EXPR_COLUMN, 0, columns.index(key), 0)
         elif isinstance(e, Literal):
             literals.append(e)
             node = (L.EXPR_LITERAL, 0, len(literals) - 1, 0)
@@ -147,9 +161,10 @@ class _Const:
         return Literal(v, np.bool_ if isinstance(v, bool) else (np.int64 if isinstance(v, int) else np.float64))
 
 
-def parse_eval(text: str, dtypes: dict):
+def parse_eval(text: str, dtypes: dict, right_dtypes: Optional[dict] = None):
     """The expression of DataFrame.eval: `text` over the columns `dtypes` (name -> dtype, in table order).  Returns (expression,
-    dtype).  Grammar: column names, numeric literals, + - * / // % **, the six comparisons, & | ~, and / or / not, parentheses.
+    dtype).  With right_dtypes (DataFrame.join_where) the expression is over two frames: `left.name` / `right.name` name a column
+    of one frame, a bare name must occur in exactly one of them (in both: ValueError).  Grammar: column names, numeric literals, + - * / // % **, the six comparisons, & | ~, and / or / not, parentheses.
     / is TRUE_DIV and // FLOOR_DIV (both FLOAT64), % PYMOD, ** POW; & | ~ are logical on bool operands and bitwise on integers.
     Operands of different dtypes are both cast (common_cast); a literal takes the dtype of the other side (TypeError when that
     dtype cannot hold it).  Anything else is a ValueError that names the construct."""
@@ -202,7 +217,17 @@ def parse_eval(text: str, dtypes: dict):
     def visit(node):
         if isinstance(node, pyast.Expression):
             return visit(node.body)
+        if right_dtypes is not None and isinstance(node, pyast.Attribute) and isinstance(node.value, pyast.Name) \
+                and node.value.id in ("left", "right"):
+            side = dtypes if node.value.id == "left" else right_dtypes
+            if node.attr not in side:
+                raise KeyError(f"{node.value.id}.{node.attr}")
+            return ColumnReference(list(side).index(node.attr), node.value.id), np.dtype(side[node.attr])
         if isinstance(node, pyast.Name):
+            if right_dtypes is not None and node.id in right_dtypes:
+                if node.id in dtypes:
+                    raise ValueError(f"eval: the name {node.id!r} is in both frames: write left.{node.id} or right.{node.id} in {text!r}")
+                return ColumnReference(list(right_dtypes).index(node.id), "right"), np.dtype(right_dtypes[node.id])
             if node.id not in dtypes:
                 raise KeyError(node.id)
             return ColumnReference(names.index(node.id)), np.dtype(dtypes[node.id])

@@ -251,6 +251,36 @@ class DataFrame:
                 out._cols[name + (suffixes[1] if name in self._cols else "")] = ops.gather(c, ri, nullify_out_of_bounds=null_r)
         return out
 
+    def join_where(self, other: "DataFrame", predicate, how: str = "inner", suffixes=("_x", "_y")) -> "DataFrame":
+        """Conditional (non-equi) join: the pairs of a row of this frame and a row of `other` for which `predicate` is true
+        (cudf::conditional_*_join; a null predicate is no match).  how in {"inner", "left", "outer", "leftsemi", "leftanti"}.
+        `predicate` is a cudf_amd.ast expression over both tables (ColumnReference(i, "left" / "right")) or a string in the grammar of
+        DataFrame.eval: left.name / right.name name a column of one frame, a bare name must occur in exactly one frame (in both:
+        ValueError).  Rows: ascending by (left row, right row); an unmatched left row keeps its place, unmatched right rows
+        (how="outer") come last.  Columns: this frame's, then `other`'s (suffixes where names collide; leftsemi / leftanti: this
+        frame's only); the side without a partner is null."""
+        kinds = {"inner": "inner", "left": "left", "outer": "full", "leftsemi": "leftsemi", "leftanti": "leftanti"}
+        if how not in kinds:
+            raise ValueError(f"join_where(how={how!r}): how must be one of {sorted(kinds)}")
+        if isinstance(predicate, str):
+            from .ast import parse_eval
+            predicate, dt = parse_eval(predicate, {name: c.dtype for name, c in self._cols.items()},
+                                       {name: c.dtype for name, c in other._cols.items()})
+            if dt != np.bool_:
+                raise ValueError(f"join_where: the predicate is a {dt} expression, not a bool one")
+        lcols, rcols = list(self._cols.values()), list(other._cols.values())
+        if how in ("leftsemi", "leftanti"):
+            fn = ops.conditional_left_semi_join if how == "leftsemi" else ops.conditional_left_anti_join
+            return self._take(fn(lcols, rcols, predicate))
+        fn = {"inner": ops.conditional_inner_join, "left": ops.conditional_left_join, "outer": ops.conditional_full_join}[how]
+        li, ri = fn(lcols, rcols, predicate)
+        out = DataFrame()
+        for name, c in self._cols.items():
+            out._cols[name + (suffixes[0] if name in other._cols else "")] = ops.gather(c, li, nullify_out_of_bounds=how == "outer")
+        for name, c in other._cols.items():
+            out._cols[name + (suffixes[1] if name in self._cols else "")] = ops.gather(c, ri, nullify_out_of_bounds=how != "inner")
+        return out
+
     def groupby(self, by: Union[str, Sequence[str]]) -> "GroupBy":
         return GroupBy(self, by)
 

@@ -1821,6 +1821,110 @@ def compute_column(columns: Sequence[Column], expr) -> Column:
 
 
 # ------------------------------------------------------------------------------------------------
+# conditional joins  (cudf::conditional_*_join: join/conditional_join.hpp; gx_conditional_join.hip)
+# ------------------------------------------------------------------------------------------------
+CONDITIONAL_JOIN_KINDS = {"inner": 0, "left": 1, "full": 2, "leftsemi": 3, "leftanti": 4}
+JOIN_NO_MATCH = -2**31
+
+
+class _ConditionalJoin:
+    """the arguments of one conditional join over the C ABI: count() runs the size pass, write() the output pass"""
+
+    def __init__(self, left_cols: Sequence[Column], right_cols: Sequence[Column], predicate, kind: str):
+        from . import ast as A
+        if kind not in CONDITIONAL_JOIN_KINDS:
+            raise ValueError(f"unknown conditional join kind {kind!r}: one of {sorted(CONDITIONAL_JOIN_KINDS)}")
+        self.kind = CONDITIONAL_JOIN_KINDS[kind]
+        sides = {"left": list(left_cols), "right": list(right_cols)}
+        for name, cols in sides.items():
+            if len({c.size for c in cols}) > 1:
+                raise ValueError(f"Column sizes of the {name} table don't match")
+        self.n_left = sides["left"][0].size if sides["left"] else 0
+        self.n_right = sides["right"][0].size if sides["right"] else 0
+        nodes, used, self.literals = A.flatten_pair(predicate)
+        for table, i in used:
+            if i >= len(sides[table]):
+                raise IndexError(f"column reference {i} is out of range for the {table} table of {len(sides[table])} columns")
+        self.cols = [sides[table][i] for table, i in used]
+        self.node_arr = (L.ExprNode * len(nodes))(*[L.ExprNode(*nd) for nd in nodes])
+        max_cols = ctypes.c_int(0)
+        _lib.gx_expr_limits(None, ctypes.byref(max_cols), None, None)
+        if len(self.cols) > max_cols.value:
+            raise ValueError("the expression is malformed or beyond the limits of gx_expr_limits")
+        if _expression_dtype(self.node_arr, self.cols, self.literals) != np.bool_:
+            raise TypeError("the predicate of a conditional join must be a BOOL8 expression")
+        self.keep = [_device_scalar(l.value, l.dtype) for l in self.literals]
+        self.col_arr = (L.ExprColumn * max(len(self.cols), 1))(*[
+            L.ExprColumn(c.data.data_ptr(), c.mask.data_ptr() if c.has_nulls() else None, 0, c.gx, int(table == "right"))
+            for c, (table, _) in zip(self.cols, used)])
+        self.lit_arr = (L.ExprLiteral * max(len(self.literals), 1))(*[L.ExprLiteral(val.data_ptr(), vb.data_ptr(), gx_dtype(l.dtype), 0)
+                                                                     for l, (val, vb) in zip(self.literals, self.keep)])
+        self.tmp = None
+
+    def _head(self):
+        return (self.node_arr, len(self.node_arr), self.col_arr, len(self.cols), self.lit_arr, len(self.literals), self.n_left, self.n_right,
+                self.kind)
+
+    def count(self) -> Tuple[int, int]:
+        """(rows of the result, rows of its left-join part): exact in 64 bits"""
+        nbytes = ctypes.c_size_t(0)
+        L.check(_lib.gx_conditional_join_count(*self._head(), None, None, ctypes.byref(nbytes), stream_ptr()), "gx_conditional_join_count")
+        self.tmp = torch.empty(max(nbytes.value, 1), dtype=torch.uint8, device="cuda")
+        sizes = torch.zeros(2, dtype=torch.int64, device="cuda")
+        L.check(_lib.gx_conditional_join_count(*self._head(), ptr(sizes), ptr(self.tmp), ctypes.byref(nbytes), stream_ptr()),
+                "gx_conditional_join_count")
+        total, left_total = (int(v) for v in sizes.tolist())
+        return total, left_total
+
+    def write(self, total: int, left_total: int, pairs: bool):
+        if total > 2**31 - 1:
+            raise OverflowError(f"the conditional join has {total} rows: more than 2^31 - 1")
+        out_l = Column.empty(np.int32, total)
+        out_r = Column.empty(np.int32, total) if pairs else None
+        L.check(_lib.gx_conditional_join_write(*self._head(), total, left_total, ptr(self.tmp), out_l.data_ptr,
+                                               out_r.data_ptr if pairs else None, stream_ptr()), "gx_conditional_join_write")
+        return (out_l, out_r) if pairs else out_l
+
+
+def _conditional_join(left_cols, right_cols, predicate, kind: str):
+    j = _ConditionalJoin(left_cols, right_cols, predicate, kind)
+    total, left_total = j.count()
+    return j.write(total, left_total, pairs=j.kind <= 2)
+
+
+def conditional_inner_join(left_cols: Sequence[Column], right_cols: Sequence[Column], predicate) -> Tuple[Column, Column]:
+    """cudf::conditional_inner_join: the (left row, right row) pairs where `predicate` (cudf_amd.ast over both tables:
+    ColumnReference(i, "left" / "right")) is valid and true, ascending by (left, right)."""
+    return _conditional_join(left_cols, right_cols, predicate, "inner")
+
+
+def conditional_left_join(left_cols: Sequence[Column], right_cols: Sequence[Column], predicate) -> Tuple[Column, Column]:
+    """cudf::conditional_left_join: the inner pairs, with (i, JOIN_NO_MATCH) in the place of a left row i without a match."""
+    return _conditional_join(left_cols, right_cols, predicate, "left")
+
+
+def conditional_full_join(left_cols: Sequence[Column], right_cols: Sequence[Column], predicate) -> Tuple[Column, Column]:
+    """cudf::conditional_full_join: the left join, then (JOIN_NO_MATCH, r) for the unmatched right rows, r ascending."""
+    return _conditional_join(left_cols, right_cols, predicate, "full")
+
+
+def conditional_left_semi_join(left_cols: Sequence[Column], right_cols: Sequence[Column], predicate) -> Column:
+    """cudf::conditional_left_semi_join: the left rows with at least one match, ascending."""
+    return _conditional_join(left_cols, right_cols, predicate, "leftsemi")
+
+
+def conditional_left_anti_join(left_cols: Sequence[Column], right_cols: Sequence[Column], predicate) -> Column:
+    """cudf::conditional_left_anti_join: the left rows without a match, ascending."""
+    return _conditional_join(left_cols, right_cols, predicate, "leftanti")
+
+
+def conditional_join_size(kind: str, left_cols: Sequence[Column], right_cols: Sequence[Column], predicate) -> int:
+    """cudf::conditional_*_join_size: the rows the join of `kind` ("inner", "left", "full", "leftsemi", "leftanti") returns; the
+    count pass alone, exact beyond 2^31 - 1."""
+    return _ConditionalJoin(left_cols, right_cols, predicate, kind).count()[0]
+
+
+# ------------------------------------------------------------------------------------------------
 # null and value replacement  (cudf::replace_nulls / replace_nans / clamp / find_and_replace_all: replace.hpp; gx_replace.hip)
 # ------------------------------------------------------------------------------------------------
 

@@ -27,7 +27,7 @@ enum class ast_operator : int32_t {
   FLOOR, ABS, RINT, BIT_INVERT, NOT, CAST_TO_INT64, CAST_TO_UINT64, CAST_TO_FLOAT64
 };
 
-// which table a column reference reads; only LEFT is evaluated (RIGHT belongs to the conditional joins)
+// which table a column reference reads: compute_column evaluates LEFT only; the conditional joins (join/conditional_join.hpp) LEFT and RIGHT
 enum class table_reference { LEFT, RIGHT, OUTPUT };
 
 enum class expression_kind { LITERAL, COLUMN_REFERENCE, OPERATION };

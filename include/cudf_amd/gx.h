@@ -508,7 +508,8 @@ int gx_elementwise_grid_cap(void);                                              
  * gx_expr_limits: at most 32 nodes, 16 columns, 16 literals, 4 spill slots; a program has at most 64 instructions (what a tree of 32
  *   nodes can need; shared nodes count once per parent).  Beyond any of them every entry point returns GX_EINVAL.
  * Errors: GX_EINVAL n outside [0, 2^31), a child index not below its parent, a column / literal index out of range, an operator
- *   outside gx_ast_op or of the other arity, NULL where a pointer is needed with n > 0, a negative begin bit, a limit exceeded;
+ *   outside gx_ast_op or of the other arity, a column whose `table` is not 0 (gx_compute_column has one table), NULL where a
+ *   pointer is needed with n > 0, a negative begin bit, a limit exceeded;
  *   GX_EDTYPE an unknown dtype, operands of different dtypes, an operator that does not take the dtype, out_dtype != the result's.
  * ------------------------------------------------------------------------------------------ */
 enum gx_ast_op {
@@ -537,7 +538,7 @@ typedef struct gx_expr_column {
   const uint32_t* valid; /* NULL: no nulls */
   int64_t begin_bit;     /* row i is bit begin_bit + i of valid */
   int32_t dtype;
-  int32_t reserved;
+  int32_t table; /* 0 = LEFT (the table of gx_compute_column), 1 = RIGHT: the conditional joins below */
 } gx_expr_column;
 typedef struct gx_expr_literal {
   const void* value;    /* one element, device memory */
@@ -566,6 +567,57 @@ int gx_expr_plan(const gx_expr_node* nodes, int n_nodes, const int32_t* col_dtyp
 void gx_expr_limits(int* max_nodes, int* max_columns, int* max_literals, int* max_slots);           /* host only */
 int gx_expression_tile_rows(void); /* rows one workgroup owns per trip */
 int gx_expression_grid_cap(void);  /* most workgroups of one launch */
+
+/* ------------------------------------------------------------------------------------------
+ * Conditional joins (cudf_amd/csrc/gx_conditional_join.hip): cudf::conditional_inner / left / full / left_semi / left_anti_join and
+ * their sizes (cpp/include/cudf/join/conditional_join.hpp, cpp/src/join/conditional_join_kernels.cuh).  The predicate is an
+ * expression of the block above over the columns of TWO tables: gx_expr_column::table says which (0 LEFT, 1 RIGHT), `cols` holds
+ * the columns of both sides in any order (16 together), row i of a LEFT column pairs with every row j of a RIGHT column.  The pair
+ * kernel runs the same program gx_compute_column runs (gx_expr_plan gives it, whichever side a column comes from).
+ * Contract.
+ *   The predicate's result dtype must be BOOL8, else GX_EDTYPE.  A pair matches iff the result is VALID and TRUE: a null result is
+ *   no match.  Column validity is read from each column's own begin bit; IS_NULL, NULL_EQUAL, NULL_LOGICAL_* and literals behave
+ *   as in gx_compute_column.
+ *   Order (fixed here; the reference leaves it open): INNER pairs ascending by (left, right); LEFT the same with (i, INT32_MIN) in
+ *   the place of a row i without a match; FULL = LEFT, then (INT32_MIN, r) for the unmatched right rows, r ascending; SEMI / ANTI
+ *   left rows ascending.
+ *   n_left, n_right in [0, 2^31).  An empty side is not read (its columns' pointers may be NULL): n_left == 0 gives nothing (FULL:
+ *   every right row), n_right == 0 gives nothing for INNER / SEMI and every left row for LEFT / FULL / ANTI.
+ *   Limits are the expression's (gx_expr_limits; 16 columns over both tables): beyond them GX_EINVAL.
+ * Two calls, stream-ordered, no host synchronisation inside; every argument is checked before anything is launched.
+ * gx_conditional_join_count: evaluates every pair once.  sizes_dev (device int64[2]): [0] the rows of the result (FULL: the tail
+ *   included), [1] the rows of its left-join part (== [0] except for FULL).  Both are tallied in 64 bits and exact beyond 2^31 - 1.
+ *   cub-style scratch query (tmp == NULL -> *tmp_bytes, host arithmetic on kind and the row counts, monotone in both); the scratch
+ *   then holds what the write pass needs -- INNER / LEFT / FULL: the exclusive scan of the counts per (left row, segment of the right
+ *   table), row-major, which IS the output position of that cell's first pair (LEFT / FULL: a row without a match in any segment gets
+ *   one place and a byte that says so), FULL: the bitmap of the unmatched right rows (the count pass clears a matched row's bit, one LDS atomic
+ *   per wave and matched row, one global atomic per workgroup, chunk and word) and its selection plan; SEMI / ANTI: one bit per left
+ *   row and its selection plan (gx_select_valid_count).  The size functions of the reference are this call alone.
+ * gx_conditional_join_write: total / left_total are the host's copies of sizes_dev[0] / [1], tmp the scratch of the count call with
+ *   the same arguments.  total > 2^31 - 1: GX_EOVERFLOW, before anything is launched.  INNER / LEFT / FULL evaluate the predicate
+ *   again (the reference's design) and store a left row's matches in ascending right row from its offset on; out_left / out_right
+ *   get `total` rows each.  SEMI / ANTI: out_left gets `total` rows (gx_compact_indices), out_right is not used.
+ * The kernel: a workgroup owns a tile of left rows (gx_conditional_join_tile: at most *left_rows; 128 or 64 where the tables are
+ *   short) and one segment of the right table (whole chunks of *right_rows rows; as many segments as fill the device when the left
+ *   tiles alone do not -- host arithmetic on the two row counts), a thread one left row; the columns the program reads are staged
+ *   as 64-bit payloads in LDS per tile and per chunk, and one run of the program evaluates gx_conditional_join_pairs_per_run()
+ *   pairs per thread.  At most gx_conditional_join_grid_cap() workgroups per segment are launched.
+ *   gx_conditional_join_set_shape (measurement knob; 0 = default): pairs per run in {2, 4, 8}, left rows in {64, 128, 256}
+ *   (0: by the device), right rows in {64, 128, 256}; else GX_EINVAL.
+ * Errors: GX_EINVAL as gx_compute_column, an unknown kind, `table` outside {0, 1}, total / left_total inconsistent; GX_EDTYPE as
+ *   gx_compute_column, a predicate that is not BOOL8; GX_EOVERFLOW see above; GX_ETMP scratch too small.
+ * ------------------------------------------------------------------------------------------ */
+enum gx_cj_kind { GX_CJ_INNER = 0, GX_CJ_LEFT = 1, GX_CJ_FULL = 2, GX_CJ_SEMI = 3, GX_CJ_ANTI = 4 };
+int gx_conditional_join_count(const gx_expr_node* nodes, int n_nodes, const gx_expr_column* cols, int n_cols, const gx_expr_literal* lits,
+                              int n_lits, int64_t n_left, int64_t n_right, int kind, int64_t* sizes_dev, void* tmp, size_t* tmp_bytes,
+                              gx_stream_t stream);
+int gx_conditional_join_write(const gx_expr_node* nodes, int n_nodes, const gx_expr_column* cols, int n_cols, const gx_expr_literal* lits,
+                              int n_lits, int64_t n_left, int64_t n_right, int kind, int64_t total, int64_t left_total, const void* tmp,
+                              int32_t* out_left, int32_t* out_right, gx_stream_t stream);
+void gx_conditional_join_tile(int* left_rows, int* right_rows); /* host only */
+int gx_conditional_join_grid_cap(void);                         /* most workgroups of one launch */
+int gx_conditional_join_pairs_per_run(void);                    /* R: pairs per thread and run of the program */
+int gx_conditional_join_set_shape(int pairs_per_run, int left_rows, int right_rows);
 
 /* ------------------------------------------------------------------------------------------
  * Null and value replacement (cudf_amd/csrc/gx_replace.hip).  Replace the kernels of the reference's cpp/src/replace (nulls.cu,
