@@ -2,7 +2,9 @@
 // allocates and forwards to the C ABI of the kernel layer (include/cudf_amd/gx.h).
 #pragma once
 #include <cudf/column/column.hpp>
+#include <cudf/column/column_factories.hpp>
 #include <cudf/column/column_view.hpp>
+#include <cudf/null_mask.hpp>
 #include <cudf/table/table.hpp>
 #include <cudf/table/table_view.hpp>
 #include <cudf/types.hpp>
@@ -14,6 +16,7 @@
 #include <cstdint>
 #include <memory>
 #include <string>
+#include <vector>
 
 namespace cudf {
 namespace detail {
@@ -30,12 +33,11 @@ inline void gx_check(int rc, char const* what)
 }
 
 // type_id values of the supported fixed-width types equal gx_dtype by construction (gx.h)
+inline bool is_gx_type(data_type t) { return static_cast<int>(t.id()) >= GX_INT8 && static_cast<int>(t.id()) <= GX_BOOL8; }
 inline int gx_type(data_type t)
 {
-  auto const id = static_cast<int>(t.id());
-  CUDF_EXPECTS(id >= GX_INT8 && id <= GX_BOOL8, "Only fixed-width numeric columns are supported on this path",
-               cudf::data_type_error);
-  return id;
+  CUDF_EXPECTS(is_gx_type(t), "Only fixed-width numeric columns are supported on this path", cudf::data_type_error);
+  return static_cast<int>(t.id());
 }
 
 // data pointer of row 0 of the view (offset applied)
@@ -83,6 +85,24 @@ inline int64_t read_i64(int64_t const* dev, rmm::cuda_stream_view stream)
 // A validity bitmap usable by the kernels for `c`: the kernels index bit i for row i, so a view
 // with a non-zero offset gets its bits re-based into a fresh bitmap (`holder` keeps it alive).
 bitmask_type const* rebased_mask(column_view const& c, rmm::device_buffer& holder, rmm::cuda_stream_view stream);
+
+// the validity of `input` as the mask of a new column of the same rows (empty without nulls)
+inline rmm::device_buffer mask_of(column_view const& input, rmm::cuda_stream_view stream, rmm::device_async_resource_ref mr)
+{
+  if (!input.has_nulls()) return rmm::device_buffer{0, stream, mr};
+  auto mask = create_null_mask(input.size(), mask_state::ALL_NULL, stream, mr);
+  gx_check(gx_bitmask_copy(static_cast<uint32_t*>(mask.data()), 0, input.null_mask(), input.offset(), input.size(), gxs(stream)), "gx_bitmask_copy");
+  return mask;
+}
+
+// cudf::empty_like(table_view) (cpp/src/copying/copy.cpp): the columns' types, zero rows
+inline std::unique_ptr<table> empty_like_table(table_view const& t)
+{
+  std::vector<std::unique_ptr<column>> cols;
+  cols.reserve(t.num_columns());
+  for (auto const& c : t) cols.emplace_back(make_empty_column(c.type()));
+  return std::make_unique<table>(std::move(cols));
+}
 
 // cudf::tile (each == false: gx_tile) and cudf::repeat with a scalar count (each == true: gx_repeat_each) differ in the entry point
 // alone: one launch per column, the null counts of all columns in one read (src/reshape.cpp)

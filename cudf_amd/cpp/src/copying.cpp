@@ -4,13 +4,12 @@
 // one mask kernel per input), include/cudf/copying.hpp + detail/scatter.cuh, detail/copy_if_else.cuh, src/copying/slice.cu,
 // split.cpp.  Here concatenate is one fused launch for any number of inputs (data, validity words and sliced views in the same
 // pass) whose null count is the sum of the views' null counts: nothing is read back.  scatter copies the target and writes in
-// place; its null counts come back in one read behind the last column.  slice and split only make views.
-#include "common.hpp"
+// place; its null counts come back in one read behind the last column.  slice and split only make views.  Operands and result
+// masks of scatter and copy_if_else follow the models of DESIGN.md 3.6 (result_column.hpp).
+#include "result_column.hpp"
 
-#include <cudf/column/column_factories.hpp>
 #include <cudf/concatenate.hpp>
 #include <cudf/copying.hpp>
-#include <cudf/null_mask.hpp>
 
 #include <algorithm>
 #include <limits>
@@ -72,111 +71,47 @@ void check_map(column_view const& map, char const* what)
   CUDF_EXPECTS(map.type().id() == type_id::INT32, std::string{what} + " must be an INT32 column", cudf::data_type_error);
 }
 
-// one side of a scatter or a copy_if_else: a column view or a scalar
-struct operand {
-  void const* data{nullptr};
-  uint32_t const* valid{nullptr};
-  int64_t begin_bit{0};
-  uint8_t const* scalar_valid{nullptr};
-  int is_scalar{0};
-  bool may_be_null{false};
-  data_type type{type_id::EMPTY};
-};
+using detail::source;
 
-operand operand_of(column_view const& c)
-{
-  operand o;
-  o.data        = detail::row0(c);
-  o.valid       = c.has_nulls() ? c.null_mask() : nullptr;
-  o.begin_bit   = c.offset();
-  o.may_be_null = c.has_nulls();
-  o.type        = c.type();
-  return o;
-}
-
-// a scalar's value and validity byte stay on the device; whether it is valid decides if the result needs a mask, which is the
-// one host read of this path
-operand operand_of(scalar const& s, rmm::cuda_stream_view stream, bool have_rows)
-{
-  operand o;
-  o.type = s.type();
-  detail::gx_type(o.type);
-  o.data = s.device_value_ptr();
-  CUDF_EXPECTS(o.data != nullptr, "Only fixed-width scalars are supported on this path", cudf::data_type_error);
-  o.scalar_valid = reinterpret_cast<uint8_t const*>(s.validity_data());
-  o.is_scalar    = 1;
-  o.may_be_null  = have_rows && !s.is_valid(stream);
-  return o;
-}
-
-// a copy of `target` with the n rows of map written from `src`; the null count is left for the caller (nulls_dev[k])
-struct scattered {
-  rmm::device_buffer data, mask;
-  bool with_mask;
-};
-
-scattered scatter_column(operand const& src, int32_t const* map, size_type n, column_view const& target, int64_t* count_dev,
-                         rmm::cuda_stream_view stream, rmm::device_async_resource_ref mr)
+// column k of a scatter: a copy of `target` with the n rows of map written from `src`; the kernel leaves the count of SET bits
+void scatter_column(detail::result_table& out, source const& src, int32_t const* map, size_type n, column_view const& target,
+                    rmm::cuda_stream_view stream, rmm::device_async_resource_ref mr)
 {
   auto const esz  = static_cast<int>(size_of(target.type()));
   auto const rows = target.size();
-  scattered out{rmm::device_buffer{detail::row0(target), static_cast<std::size_t>(rows) * esz, stream, mr}, rmm::device_buffer{0, stream, mr},
-                target.has_nulls() || src.may_be_null};
-  if (out.with_mask) {
-    out.mask = create_null_mask(rows, mask_state::ALL_VALID, stream, mr);
-    if (target.has_nulls())
-      run_concatenate(host_span<column_view const>{&target, 1}, esz, nullptr, static_cast<uint32_t*>(out.mask.data()), stream);
-  }
+  auto& col       = out.add(target.type(), rows, rmm::device_buffer{detail::row0(target), static_cast<std::size_t>(rows) * esz, stream, mr},
+                            target.has_nulls() || src.may_be_null, mask_state::ALL_VALID);
+  if (target.has_nulls()) run_concatenate(host_span<column_view const>{&target, 1}, esz, nullptr, col.valid(), stream);
   if (n > 0) {
-    detail::gx_check(gx_scatter(esz, src.data, src.valid, src.begin_bit, src.scalar_valid, src.is_scalar, map, n, out.data.data(),
-                                out.with_mask ? static_cast<uint32_t*>(out.mask.data()) : nullptr, rows, detail::gxs(stream)),
+    detail::gx_check(gx_scatter(esz, src.data, src.valid, src.begin_bit, src.scalar_valid, src.is_scalar, map, n, col.data(), col.valid(), rows,
+                                detail::gxs(stream)),
                      "gx_scatter");
   }
-  if (out.with_mask)
-    detail::gx_check(gx_bitmask_count(static_cast<uint32_t const*>(out.mask.data()), 0, rows, count_dev, detail::gxs(stream)), "scatter null count");
-  return out;
+  if (col.with_mask())
+    detail::gx_check(gx_bitmask_count(col.valid(), 0, rows, col.nulls_dev(), detail::gxs(stream)), "scatter null count");
 }
 
-std::unique_ptr<table> finish_scatter(std::vector<scattered>& parts, table_view const& target, rmm::device_uvector<int64_t>& counts_dev,
-                                      rmm::cuda_stream_view stream, rmm::device_async_resource_ref mr)
-{
-  auto const nc = target.num_columns();
-  std::vector<int64_t> set_bits(static_cast<std::size_t>(nc), 0);
-  bool any_mask = false;
-  for (auto const& p : parts) any_mask |= p.with_mask;
-  if (any_mask) {  // all counts in one read, as compact_table (stream_compaction.cpp) has it
-    CUDF_CUDA_TRY(hipMemcpyAsync(set_bits.data(), counts_dev.data(), set_bits.size() * sizeof(int64_t), hipMemcpyDeviceToHost, stream.value()));
-    stream.synchronize();
-  }
-  std::vector<std::unique_ptr<column>> cols;
-  cols.reserve(nc);
-  for (size_type k = 0; k < nc; ++k) {
-    auto& p          = parts[k];
-    auto const nulls = p.with_mask ? static_cast<size_type>(target.num_rows() - set_bits[k]) : 0;
-    cols.emplace_back(std::make_unique<column>(target.column(k).type(), target.num_rows(), std::move(p.data),
-                                               nulls > 0 ? std::move(p.mask) : rmm::device_buffer{0, stream, mr}, nulls));
-  }
-  return std::make_unique<table>(std::move(cols));
-}
-
-std::unique_ptr<column> select(operand const& lhs, operand const& rhs, column_view const& boolean_mask, rmm::cuda_stream_view stream,
+std::unique_ptr<column> select(source const& lhs, source const& rhs, column_view const& boolean_mask, rmm::cuda_stream_view stream,
                                rmm::device_async_resource_ref mr)
 {
   auto const n   = boolean_mask.size();
   auto const esz = static_cast<int>(size_of(lhs.type));
   if (n == 0) return make_empty_column(lhs.type);
-  rmm::device_buffer data{static_cast<std::size_t>(n) * esz, stream, mr};
-  bool const with_mask = lhs.may_be_null || rhs.may_be_null;
-  auto mask            = create_null_mask(n, with_mask ? mask_state::UNINITIALIZED : mask_state::UNALLOCATED, stream, mr);
-  rmm::device_buffer nulls_dev{sizeof(int64_t), stream};
+  detail::result_column out{lhs.type, n, lhs.may_be_null || rhs.may_be_null, mask_state::UNINITIALIZED, stream, mr};
   detail::gx_check(gx_copy_if_else(esz, lhs.data, lhs.valid, lhs.begin_bit, lhs.scalar_valid, lhs.is_scalar, rhs.data, rhs.valid,
                                    rhs.begin_bit, rhs.scalar_valid, rhs.is_scalar, static_cast<uint8_t const*>(detail::row0(boolean_mask)),
-                                   boolean_mask.has_nulls() ? boolean_mask.null_mask() : nullptr, boolean_mask.offset(), n, data.data(),
-                                   with_mask ? static_cast<uint32_t*>(mask.data()) : nullptr,
-                                   with_mask ? static_cast<int64_t*>(nulls_dev.data()) : nullptr, detail::gxs(stream)),
+                                   boolean_mask.has_nulls() ? boolean_mask.null_mask() : nullptr, boolean_mask.offset(), n, out.data(),
+                                   out.valid(), out.nulls_dev(), detail::gxs(stream)),
                    "gx_copy_if_else");
-  auto const nulls = with_mask ? static_cast<size_type>(detail::read_i64(static_cast<int64_t const*>(nulls_dev.data()), stream)) : 0;
-  return std::make_unique<column>(lhs.type, n, std::move(data), nulls > 0 ? std::move(mask) : rmm::device_buffer{0, stream, mr}, nulls);
+  return out.finish();
+}
+
+// a scalar side, built after check_select: its validity is the device read that decides whether the result needs a mask
+source checked_source_of(scalar const& s, bool have_rows, rmm::cuda_stream_view stream)
+{
+  auto o        = detail::source_of(s);
+  o.may_be_null = detail::scalar_may_be_null(s, have_rows, stream);
+  return o;
 }
 
 void check_select(data_type lhs, data_type rhs, column_view const& boolean_mask)
@@ -269,14 +204,11 @@ std::unique_ptr<table> scatter(table_view const& source, column_view const& scat
     CUDF_EXPECTS(source.column(k).type() == target.column(k).type(), "Column types do not match between source and target", cudf::data_type_error);
     detail::gx_type(target.column(k).type());
   }
-  auto const nc = target.num_columns();
-  rmm::device_uvector<int64_t> counts_dev(static_cast<std::size_t>(std::max<size_type>(nc, 1)), stream);
+  detail::result_table out{target.num_columns(), stream, mr};
   auto const* map = static_cast<int32_t const*>(detail::row0(scatter_map));
-  std::vector<scattered> parts;
-  parts.reserve(nc);
-  for (size_type k = 0; k < nc; ++k)
-    parts.emplace_back(scatter_column(operand_of(source.column(k)), map, scatter_map.size(), target.column(k), counts_dev.data() + k, stream, mr));
-  return finish_scatter(parts, target, counts_dev, stream, mr);
+  for (size_type k = 0; k < target.num_columns(); ++k)
+    scatter_column(out, detail::source_of(source.column(k)), map, scatter_map.size(), target.column(k), stream, mr);
+  return out.finish(target.num_rows(), true);
 }
 
 std::unique_ptr<table> scatter(std::vector<std::reference_wrapper<scalar const>> const& source, column_view const& indices,
@@ -288,15 +220,16 @@ std::unique_ptr<table> scatter(std::vector<std::reference_wrapper<scalar const>>
     CUDF_EXPECTS(source[k].get().type() == target.column(k).type(), "Type mismatch in scalar and target column", cudf::data_type_error);
     detail::gx_type(target.column(k).type());
   }
-  auto const nc = target.num_columns();
-  rmm::device_uvector<int64_t> counts_dev(static_cast<std::size_t>(std::max<size_type>(nc, 1)), stream);
+  // every scalar is checked before the first one's validity is read
+  std::vector<detail::source> srcs;
+  for (auto const& s : source) srcs.push_back(detail::source_of(s.get()));
+  detail::result_table out{target.num_columns(), stream, mr};
   auto const* map = static_cast<int32_t const*>(detail::row0(indices));
-  std::vector<scattered> parts;
-  parts.reserve(nc);
-  for (size_type k = 0; k < nc; ++k)
-    parts.emplace_back(scatter_column(operand_of(source[k].get(), stream, indices.size() > 0), map, indices.size(), target.column(k),
-                                      counts_dev.data() + k, stream, mr));
-  return finish_scatter(parts, target, counts_dev, stream, mr);
+  for (size_type k = 0; k < target.num_columns(); ++k) {
+    srcs[k].may_be_null = detail::scalar_may_be_null(source[k].get(), indices.size() > 0, stream);
+    scatter_column(out, srcs[k], map, indices.size(), target.column(k), stream, mr);
+  }
+  return out.finish(target.num_rows(), true);
 }
 
 // ------------------------------------------------------------------------------------ copy_if_else
@@ -306,7 +239,7 @@ std::unique_ptr<column> copy_if_else(column_view const& lhs, column_view const& 
   check_select(lhs.type(), rhs.type(), boolean_mask);
   CUDF_EXPECTS(lhs.size() == rhs.size(), "Both columns must be of the same size", std::invalid_argument);
   CUDF_EXPECTS(boolean_mask.size() == lhs.size(), "Boolean mask column must be the same size as lhs and rhs columns", std::invalid_argument);
-  return select(operand_of(lhs), operand_of(rhs), boolean_mask, stream, mr);
+  return select(detail::source_of(lhs), detail::source_of(rhs), boolean_mask, stream, mr);
 }
 
 std::unique_ptr<column> copy_if_else(scalar const& lhs, column_view const& rhs, column_view const& boolean_mask,
@@ -314,7 +247,7 @@ std::unique_ptr<column> copy_if_else(scalar const& lhs, column_view const& rhs, 
 {
   check_select(lhs.type(), rhs.type(), boolean_mask);
   CUDF_EXPECTS(boolean_mask.size() == rhs.size(), "Boolean mask column must be the same size as rhs column", std::invalid_argument);
-  return select(operand_of(lhs, stream, boolean_mask.size() > 0), operand_of(rhs), boolean_mask, stream, mr);
+  return select(checked_source_of(lhs, boolean_mask.size() > 0, stream), detail::source_of(rhs), boolean_mask, stream, mr);
 }
 
 std::unique_ptr<column> copy_if_else(column_view const& lhs, scalar const& rhs, column_view const& boolean_mask,
@@ -322,7 +255,7 @@ std::unique_ptr<column> copy_if_else(column_view const& lhs, scalar const& rhs, 
 {
   check_select(lhs.type(), rhs.type(), boolean_mask);
   CUDF_EXPECTS(boolean_mask.size() == lhs.size(), "Boolean mask column must be the same size as lhs column", std::invalid_argument);
-  return select(operand_of(lhs), operand_of(rhs, stream, boolean_mask.size() > 0), boolean_mask, stream, mr);
+  return select(detail::source_of(lhs), checked_source_of(rhs, boolean_mask.size() > 0, stream), boolean_mask, stream, mr);
 }
 
 std::unique_ptr<column> copy_if_else(scalar const& lhs, scalar const& rhs, column_view const& boolean_mask,
@@ -330,7 +263,7 @@ std::unique_ptr<column> copy_if_else(scalar const& lhs, scalar const& rhs, colum
 {
   check_select(lhs.type(), rhs.type(), boolean_mask);
   bool const rows = boolean_mask.size() > 0;
-  return select(operand_of(lhs, stream, rows), operand_of(rhs, stream, rows), boolean_mask, stream, mr);
+  return select(checked_source_of(lhs, rows, stream), checked_source_of(rhs, rows, stream), boolean_mask, stream, mr);
 }
 
 // ------------------------------------------------------------------------------------ slice / split

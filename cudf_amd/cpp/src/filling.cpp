@@ -3,12 +3,10 @@
 // sequence.cu.  fill writes the range and edits the bitmap (gx_bitmask_copy / gx_bitmask_set).  repeat with a count column casts
 // the counts to int64, scans them (so a total of 2^31 or more is seen before anything is sized from it), reads the total once,
 // computes one expansion map and gathers every column through it; with a scalar count it is one streaming launch per column.
-#include "common.hpp"
+#include "result_column.hpp"
 
-#include <cudf/column/column_factories.hpp>
 #include <cudf/copying.hpp>
 #include <cudf/filling.hpp>
-#include <cudf/null_mask.hpp>
 
 #include <limits>
 #include <stdexcept>
@@ -30,15 +28,7 @@ void check_fill(data_type type, size_type size, size_type begin, size_type end, 
   CUDF_EXPECTS(begin >= 0 && end <= size && begin <= end, "Range is out of bounds.", std::out_of_range);
   CUDF_EXPECTS(type == value.type(), "Data type mismatch.", cudf::data_type_error);
   detail::gx_type(type);
-  CUDF_EXPECTS(value.device_value_ptr() != nullptr, "Only fixed-width scalars are supported on this path", cudf::data_type_error);
-}
-
-std::unique_ptr<table> empty_like(table_view const& input)
-{
-  std::vector<std::unique_ptr<column>> cols;
-  cols.reserve(input.num_columns());
-  for (auto const& c : input) cols.emplace_back(make_empty_column(c.type()));
-  return std::make_unique<table>(std::move(cols));
+  detail::scalar_device_value(value);
 }
 
 }  // namespace
@@ -92,7 +82,7 @@ std::unique_ptr<table> repeat(table_view const& input, column_view const& count,
   CUDF_EXPECTS(input.num_rows() == count.size(), "in and count must have equal size", std::invalid_argument);
   for (auto const& c : input) detail::gx_type(c.type());
   auto const n = input.num_rows();
-  if (n == 0) return empty_like(input);
+  if (n == 0) return detail::empty_like_table(input);
   // counts as int64 with one 0 behind them: the exclusive scan of n + 1 entries ends in the total
   auto const n1 = static_cast<std::size_t>(n) + 1;
   rmm::device_uvector<int64_t> counts(n1, stream), offsets64(n1, stream);
@@ -105,7 +95,7 @@ std::unique_ptr<table> repeat(table_view const& input, column_view const& count,
     "gx_scan", stream);
   auto const total = detail::read_i64(offsets64.data() + n, stream);  // the one host read: it sizes the result
   CUDF_EXPECTS(total <= size_max, "The repeated rows exceed the column size limit", std::overflow_error);
-  if (total <= 0) return empty_like(input);
+  if (total <= 0) return detail::empty_like_table(input);
   rmm::device_uvector<int32_t> offsets(n1, stream), map(static_cast<std::size_t>(total), stream);
   detail::gx_check(gx_cast(GX_INT64, offsets64.data(), static_cast<int64_t>(n1), GX_INT32, offsets.data(), detail::gxs(stream)), "gx_cast");
   auto map_tmp = detail::run_with_scratch(

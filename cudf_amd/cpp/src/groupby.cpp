@@ -1,7 +1,7 @@
 // cudf::groupby::groupby::aggregate / scan over the C ABI.
 // reference: cpp/src/groupby/groupby.cu:40-71,220-259; hash path cpp/src/groupby/hash/*;
 // scan path cpp/src/groupby/sort/{scan.cpp:214-238, sort_helper.cu:73-162, group_scan_util.cuh:77-133}.
-#include "common.hpp"
+#include "result_column.hpp"
 #include "row_encoding.hpp"
 #include "sort_helper.hpp"
 
@@ -438,23 +438,12 @@ std::pair<std::unique_ptr<table>, std::vector<aggregation_result>> groupby::aggr
       return canonical ? permute(c->view(), mm_order->view(), stream, mr) : std::move(c);
     };
     auto const g = o.keys->size();
-    // validity of SUM / MEAN: groups without a valid value are null
-    auto validity = [&](size_type& nulls) {
-      rmm::device_buffer mask = create_null_mask(g, mask_state::ALL_VALID, stream, mr);
-      rmm::device_buffer cnt{sizeof(int64_t), stream};
-      detail::gx_check(gx_valid_from_counts(o.count_valid->view().head<int32_t>(), g, static_cast<uint32_t*>(mask.data()),
-                                            static_cast<int64_t*>(cnt.data()), detail::gxs(stream)),
-                       "groupby validity");
-      nulls = static_cast<size_type>(detail::read_i64(static_cast<int64_t const*>(cnt.data()), stream));
-      return mask;
-    };
+    using detail::mask_from_counts;  // groups without a valid value are null
     for (auto const& agg : req.aggregations) {
       switch (agg->kind) {
         case aggregation::SUM: {
           auto c = std::make_unique<column>(o.sum->view(), stream, mr);
-          size_type nulls = 0;
-          auto mask       = validity(nulls);
-          if (nulls > 0) c->set_null_mask(std::move(mask), nulls);
+          mask_from_counts(*c, o.count_valid->view().head<int32_t>(), stream, mr);
           results[i].results.emplace_back(fin(std::move(c)));
           break;
         }
@@ -466,22 +455,14 @@ std::pair<std::unique_ptr<table>, std::vector<aggregation_result>> groupby::aggr
                                             o.count_valid->view().head<int32_t>(), g, c->mutable_view().head<double>(),
                                             detail::gxs(stream)),
                            "groupby mean");
-          size_type nulls = 0;
-          auto mask       = validity(nulls);
-          if (nulls > 0) c->set_null_mask(std::move(mask), nulls);
+          mask_from_counts(*c, o.count_valid->view().head<int32_t>(), stream, mr);
           results[i].results.emplace_back(fin(std::move(c)));
           break;
         }
         case aggregation::SUM_OF_SQUARES: {
           auto c = permute(q.sum->view(), sq_order->view(), stream, mr);  // already in key order
-          rmm::device_buffer mask = create_null_mask(c->size(), mask_state::ALL_VALID, stream, mr);
-          rmm::device_buffer cnt{sizeof(int64_t), stream};
           auto cv = permute(q.count_valid->view(), sq_order->view(), stream, mr);
-          detail::gx_check(gx_valid_from_counts(cv->view().head<int32_t>(), c->size(), static_cast<uint32_t*>(mask.data()),
-                                                static_cast<int64_t*>(cnt.data()), detail::gxs(stream)),
-                           "groupby validity");
-          auto const nulls = static_cast<size_type>(detail::read_i64(static_cast<int64_t const*>(cnt.data()), stream));
-          if (nulls > 0) c->set_null_mask(std::move(mask), nulls);
+          mask_from_counts(*c, cv->view().head<int32_t>(), stream, mr);
           results[i].results.emplace_back(std::move(c));
           break;
         }
@@ -494,21 +475,15 @@ std::pair<std::unique_ptr<table>, std::vector<aggregation_result>> groupby::aggr
           std::unique_ptr<column> sum;
           if (!centred) sum = permute(o.sum->view(), order->view(), stream, mr);
           auto cv   = permute(o.count_valid->view(), order->view(), stream, mr);
-          auto c    = make_fixed_width_column(data_type{type_id::FLOAT64}, g, mask_state::UNALLOCATED, stream, mr);
-          rmm::device_buffer mask = create_null_mask(g, mask_state::ALL_VALID, stream, mr);
-          rmm::device_buffer cnt{sizeof(int64_t), stream};
+          detail::result_column c{data_type{type_id::FLOAT64}, g, true, mask_state::ALL_VALID, stream, mr};
           int ddof = 1;
           if (auto const* sv = dynamic_cast<detail::std_var_aggregation const*>(agg.get())) ddof = sv->_ddof;
           int const mode = agg->kind == aggregation::M2 ? 0 : (agg->kind == aggregation::VARIANCE ? 1 : 2);
           detail::gx_check(gx_var_from_sums(detail::gx_type(ssum->type()), ssum->view().head<void>(),
                                             centred ? nullptr : sum->view().head<void>(), cv->view().head<int32_t>(), g, ddof,
-                                            mode, c->mutable_view().head<double>(),
-                                            static_cast<uint32_t*>(mask.data()), static_cast<int64_t*>(cnt.data()),
-                                            detail::gxs(stream)),
+                                            mode, static_cast<double*>(c.data()), c.valid(), c.nulls_dev(), detail::gxs(stream)),
                            "groupby variance");
-          auto const nulls = static_cast<size_type>(detail::read_i64(static_cast<int64_t const*>(cnt.data()), stream));
-          if (nulls > 0) c->set_null_mask(std::move(mask), nulls);
-          results[i].results.emplace_back(std::move(c));  // already in key order
+          results[i].results.emplace_back(c.finish());  // already in key order
           break;
         }
         case aggregation::ARGMIN:
@@ -525,13 +500,7 @@ std::pair<std::unique_ptr<table>, std::vector<aggregation_result>> groupby::aggr
                                                    detail::gxs(stream)),
                              "groupby argmin/argmax");
           }
-          rmm::device_buffer mask = create_null_mask(gm, mask_state::ALL_VALID, stream, mr);
-          rmm::device_buffer cnt{sizeof(int64_t), stream};
-          detail::gx_check(gx_valid_from_counts(mm.count_valid->view().head<int32_t>(), gm, static_cast<uint32_t*>(mask.data()),
-                                                static_cast<int64_t*>(cnt.data()), detail::gxs(stream)),
-                           "groupby validity");
-          auto const nulls = static_cast<size_type>(detail::read_i64(static_cast<int64_t const*>(cnt.data()), stream));
-          if (nulls > 0) c->set_null_mask(std::move(mask), nulls);
+          mask_from_counts(*c, mm.count_valid->view().head<int32_t>(), stream, mr);
           results[i].results.emplace_back(fin_mm(std::move(c)));
           break;
         }
@@ -539,15 +508,7 @@ std::pair<std::unique_ptr<table>, std::vector<aggregation_result>> groupby::aggr
         case aggregation::MAX: {
           auto const& src = agg->kind == aggregation::MIN ? mm.mn : mm.mx;
           auto c          = std::make_unique<column>(src->view(), stream, mr);
-          // validity from THIS pass's counts (its group order)
-          rmm::device_buffer mask = create_null_mask(c->size(), mask_state::ALL_VALID, stream, mr);
-          rmm::device_buffer cnt{sizeof(int64_t), stream};
-          detail::gx_check(gx_valid_from_counts(mm.count_valid->view().head<int32_t>(), c->size(),
-                                                static_cast<uint32_t*>(mask.data()), static_cast<int64_t*>(cnt.data()),
-                                                detail::gxs(stream)),
-                           "groupby validity");
-          auto const nulls = static_cast<size_type>(detail::read_i64(static_cast<int64_t const*>(cnt.data()), stream));
-          if (nulls > 0) c->set_null_mask(std::move(mask), nulls);
+          mask_from_counts(*c, mm.count_valid->view().head<int32_t>(), stream, mr);  // THIS pass's counts (its group order)
           results[i].results.emplace_back(fin_mm(std::move(c)));
           break;
         }

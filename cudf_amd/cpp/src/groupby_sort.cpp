@@ -4,7 +4,7 @@
 // reference: cpp/src/groupby/sort/{sort_helper.cu:37-260, aggregate.cpp:94-142,276-301,879-903,
 // group_single_pass_reduction_util.cuh:133-200, group_count.cu:25-89, group_replace_nulls.cu},
 // cpp/src/groupby/groupby.cu:54-71,261-362.
-#include "common.hpp"
+#include "result_column.hpp"
 #include "sort_helper.hpp"
 
 #include <cudf/column/column_factories.hpp>
@@ -163,18 +163,10 @@ namespace {
 
 data_type sum_type_of(data_type v) { return is_floating_point(v) ? v : data_type{type_id::INT64}; }
 
-// validity of a per-group result from the number of valid values that went into it
+// detail::mask_from_counts, without its launch and read when there is no group
 void mask_from_counts(column& c, int32_t const* counts, rmm::cuda_stream_view stream, rmm::device_async_resource_ref mr)
 {
-  auto const g = c.size();
-  if (g == 0) return;
-  rmm::device_buffer mask = create_null_mask(g, mask_state::ALL_VALID, stream, mr);
-  rmm::device_buffer cnt{sizeof(int64_t), stream};
-  detail::gx_check(gx_valid_from_counts(counts, g, static_cast<uint32_t*>(mask.data()), static_cast<int64_t*>(cnt.data()),
-                                        detail::gxs(stream)),
-                   "groupby validity");
-  auto const nulls = static_cast<size_type>(detail::read_i64(static_cast<int64_t const*>(cnt.data()), stream));
-  if (nulls > 0) c.set_null_mask(std::move(mask), nulls);
+  if (c.size() > 0) detail::mask_from_counts(c, counts, stream, mr);
 }
 
 }  // namespace

@@ -18,14 +18,6 @@
 namespace cudf {
 namespace {
 
-std::unique_ptr<table> empty_like_table(table_view const& t)
-{
-  std::vector<std::unique_ptr<column>> cols;
-  cols.reserve(t.num_columns());
-  for (auto const& c : t) cols.emplace_back(make_empty_column(c.type()));
-  return std::make_unique<table>(std::move(cols));
-}
-
 // a (sorted) and b (sorted), both with rows: the stable merge, a's rows first among equivalent ones
 std::unique_ptr<table> merge_two(table_view const& a, table_view const& b, std::vector<size_type> const& key_cols,
                                  std::vector<order> const& column_order, std::vector<null_order> const& null_precedence,
@@ -111,7 +103,7 @@ std::unique_ptr<table> merge(std::vector<table_view> const& tables_to_merge, std
   std::vector<run> level;
   for (auto const& t : tables_to_merge)
     if (t.num_rows() > 0) level.push_back(run{t, nullptr});
-  if (level.empty()) return empty_like_table(first);
+  if (level.empty()) return detail::empty_like_table(first);
   if (level.size() == 1) return std::make_unique<table>(level.front().view, stream, mr);
   // a balanced tree over neighbours: a run is merged only with the run next to it, so equivalent rows never change sides
   while (level.size() > 1) {

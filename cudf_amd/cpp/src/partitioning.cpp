@@ -12,15 +12,6 @@
 namespace cudf {
 namespace {
 
-// cudf::empty_like(table_view) (cpp/src/copying/copy.cpp): the columns' types, zero rows
-std::unique_ptr<table> empty_like_table(table_view const& t)
-{
-  std::vector<std::unique_ptr<column>> cols;
-  cols.reserve(t.num_columns());
-  for (auto const& c : t) cols.emplace_back(make_empty_column(c.type()));
-  return std::make_unique<table>(std::move(cols));
-}
-
 // rows regrouped by value[i] % num_partitions through a stable map; ALWAYS num_partitions + 1 offsets, last = rows
 // (partitioning.cu:684-688: "Add the total row count as the last offset")
 std::pair<std::unique_ptr<table>, std::vector<size_type>> regroup(table_view const& input, uint32_t const* value, int num_partitions,
@@ -53,7 +44,7 @@ std::pair<std::unique_ptr<table>, std::vector<size_type>> hash_partition(table_v
   CUDF_EXPECTS(hash_function == hash_id::HASH_MURMUR3 || hash_function == hash_id::HASH_IDENTITY, "Unsupported hash function in hash_partition");
   // no partitions, no rows or nothing to hash: an empty table and num_partitions + 1 zeros (partitioning.cu:883-886)
   if (num_partitions <= 0 || input.num_rows() == 0 || keys.num_columns() == 0)
-    return {empty_like_table(input), std::vector<size_type>(static_cast<std::size_t>(std::max(num_partitions, 0)) + 1, 0)};
+    return {detail::empty_like_table(input), std::vector<size_type>(static_cast<std::size_t>(std::max(num_partitions, 0)) + 1, 0)};
   if (hash_function == hash_id::HASH_IDENTITY) {
     // IdentityHash<T> = static_cast<uint32_t>(element) for every numeric T (partitioning.cu:852-872, 885-889), rows folded like any
     // row hash: the first column's element hash, later columns through hash_combine, a null element = UINT32_MAX
@@ -88,7 +79,7 @@ std::pair<std::unique_ptr<table>, std::vector<size_type>> partition(table_view c
   CUDF_EXPECTS(t.num_rows() == partition_map.size(), "Size mismatch between table and partition map.");
   CUDF_EXPECTS(!partition_map.has_nulls(), "Unexpected null values in partition_map.");
   if (num_partitions <= 0 || t.num_rows() == 0)
-    return {empty_like_table(t), std::vector<size_type>(static_cast<std::size_t>(std::max(num_partitions, 0)) + 1, 0)};
+    return {detail::empty_like_table(t), std::vector<size_type>(static_cast<std::size_t>(std::max(num_partitions, 0)) + 1, 0)};
   // any integral map type but bool (partitioning.cu:780-842: is_index_type, else "Unexpected, non-integral partition map.")
   CUDF_EXPECTS(is_index_type(partition_map.type()), "Unexpected, non-integral partition map.");
   // map values lie in [0, num_partitions) (partitioning.hpp:52-55), so value % num_partitions is the value: the hash-partition
@@ -113,7 +104,7 @@ std::pair<std::unique_ptr<table>, std::vector<size_type>> round_robin_partition(
   CUDF_EXPECTS(start_partition < num_partitions, "Incorrect start_partition index. Must be less than number of partitions.");
   CUDF_EXPECTS(start_partition >= 0, "Incorrect start_partition index. Must be positive.");
   auto const n = input.num_rows();
-  if (n == 0) return {empty_like_table(input), std::vector<size_type>(static_cast<std::size_t>(num_partitions) + 1, 0)};
+  if (n == 0) return {detail::empty_like_table(input), std::vector<size_type>(static_cast<std::size_t>(num_partitions) + 1, 0)};
   if (input.num_columns() == 0) {  // no column to move: the offsets alone (round_robin_test.cpp:32-42)
     std::vector<size_type> offs(static_cast<std::size_t>(num_partitions) + 1, 0);
     for (size_type p = 0; p < num_partitions; ++p) {

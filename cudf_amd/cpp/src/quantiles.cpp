@@ -1,11 +1,9 @@
 // cudf::quantile / cudf::quantiles over the C ABI (gx_quantile_lookup, gx_quantile_index; cudf_amd/csrc/gx_quantile.hip).
 // reference: cpp/include/cudf/quantiles.hpp, cpp/src/quantiles/quantile.cu, quantiles.cu -- there one thrust::transform over the
 // quantiles; here the lookup kernel with one segment, and for quantiles() sorted_order + gather at host-computed indices.
-#include "common.hpp"
+#include "result_column.hpp"
 
-#include <cudf/column/column_factories.hpp>
 #include <cudf/copying.hpp>
-#include <cudf/null_mask.hpp>
 #include <cudf/quantiles.hpp>
 #include <cudf/sorting.hpp>
 
@@ -39,11 +37,9 @@ std::unique_ptr<column> quantile(column_view const& input, std::vector<double> c
   auto const nq       = static_cast<size_type>(q.size());
   if (nq == 0) return make_empty_column(out_type);
   if (input.is_empty()) return make_fixed_width_column(out_type, nq, mask_state::ALL_NULL, stream, mr);
-  auto out                = make_fixed_width_column(out_type, nq, mask_state::UNALLOCATED, stream, mr);
-  rmm::device_buffer mask = create_null_mask(nq, mask_state::ALL_VALID, stream, mr);
+  detail::result_column out{out_type, nq, true, mask_state::ALL_VALID, stream, mr};
   int32_t const offsets_host[2] = {0, input.size()};
   rmm::device_buffer offsets{offsets_host, sizeof(offsets_host), stream};
-  rmm::device_buffer nulls_dev{sizeof(int64_t), stream};
   auto const w        = size_of(out_type);
   size_type nulls     = 0;
   auto const* order   = ordered_indices.is_empty() ? nullptr
@@ -53,14 +49,12 @@ std::unique_ptr<column> quantile(column_view const& input, std::vector<double> c
     // a chunk's validity words start at a word boundary: MAX_Q is a multiple of 32
     detail::gx_check(gx_quantile_lookup(detail::gx_type(input.type()), detail::row0(input), input.has_nulls() ? input.null_mask() : nullptr,
                                         input.offset(), order, 1, static_cast<int32_t const*>(offsets.data()), nullptr, q.data() + first, cnt,
-                                        static_cast<int>(interp), exact ? 1 : 0, out->mutable_view().head<char>() + first * w,
-                                        static_cast<uint32_t*>(mask.data()) + first / 32, static_cast<int64_t*>(nulls_dev.data()),
-                                        detail::gxs(stream)),
+                                        static_cast<int>(interp), exact ? 1 : 0, static_cast<char*>(out.data()) + first * w, out.valid() + first / 32,
+                                        out.nulls_dev(), detail::gxs(stream)),
                      "quantile");
-    nulls += static_cast<size_type>(detail::read_i64(static_cast<int64_t const*>(nulls_dev.data()), stream));
+    nulls += static_cast<size_type>(detail::read_i64(out.nulls_dev(), stream));  // each chunk overwrites the count
   }
-  if (nulls > 0) out->set_null_mask(std::move(mask), nulls);
-  return out;
+  return out.finish(nulls);
 }
 
 std::unique_ptr<table> quantiles(table_view const& input, std::vector<double> const& q, interpolation interp, cudf::sorted is_input_sorted,

@@ -1,13 +1,10 @@
 // cudf::replace_nulls, replace_nans, find_and_replace_all, clamp and normalize_nans_and_zeros over the C ABI (gx_replace_nulls,
 // gx_replace_nulls_policy, gx_replace_nans, gx_find_and_replace, gx_clamp, gx_normalize_nans_and_zeros;
 // cudf_amd/csrc/gx_replace.hip).  reference: cpp/include/cudf/replace.hpp, cpp/src/replace/nulls.cu, nans.cu, replace.cu, clamp.cu.
-// One launch writes values, validity words and the null count; sliced views are read in place (offset data pointer, begin bit).
-// A mask is allocated only when the result can hold a null, and kept only when it does: the one host read of these paths, as
-// binary_operation has it (binaryop.cpp).  A call that cannot change a row returns a copy of its input.
-#include "common.hpp"
+// One launch writes values, validity words and the null count; replacements and the result mask follow the models of DESIGN.md 3.6
+// (result_column.hpp).  A call that cannot change a row returns a copy of its input.
+#include "result_column.hpp"
 
-#include <cudf/column/column_factories.hpp>
-#include <cudf/null_mask.hpp>
 #include <cudf/replace.hpp>
 
 #include <stdexcept>
@@ -15,68 +12,33 @@
 namespace cudf {
 namespace {
 
-bool is_float(data_type t) { return t.id() == type_id::FLOAT32 || t.id() == type_id::FLOAT64; }
+using detail::scalar_device_value;
 
+// a copy of the input's rows; as every result here it has a mask only when a row is null
 std::unique_ptr<column> copy_of(column_view const& input, rmm::cuda_stream_view stream, rmm::device_async_resource_ref mr)
 {
-  return std::make_unique<column>(input, stream, mr);
+  if (input.has_nulls()) return std::make_unique<column>(input, stream, mr);
+  return std::make_unique<column>(column_view{input.type(), input.size(), input.head<void>(), nullptr, 0, input.offset()}, stream, mr);
 }
 
-// the validity of `input` as the mask of a new column of the same rows (empty without nulls)
-rmm::device_buffer mask_of(column_view const& input, rmm::cuda_stream_view stream, rmm::device_async_resource_ref mr)
-{
-  if (!input.has_nulls()) return rmm::device_buffer{0, stream, mr};
-  auto mask = create_null_mask(input.size(), mask_state::ALL_NULL, stream, mr);
-  detail::gx_check(gx_bitmask_copy(static_cast<uint32_t*>(mask.data()), 0, input.null_mask(), input.offset(), input.size(), detail::gxs(stream)),
-                   "gx_bitmask_copy");
-  return mask;
-}
-
-void const* scalar_value(scalar const& s)
-{
-  auto const* p = s.device_value_ptr();
-  CUDF_EXPECTS(p != nullptr, "Only fixed-width scalars are supported on this path", cudf::data_type_error);
-  return p;
-}
-
-// the result of a launch that wrote data, `mask` (when with_mask) and the device null count
-std::unique_ptr<column> finish(data_type type, size_type n, rmm::device_buffer&& data, rmm::device_buffer&& mask, bool with_mask,
-                               rmm::device_buffer const& nulls_dev, rmm::cuda_stream_view stream, rmm::device_async_resource_ref mr)
-{
-  auto const nulls = with_mask ? static_cast<size_type>(detail::read_i64(static_cast<int64_t const*>(nulls_dev.data()), stream)) : 0;
-  return std::make_unique<column>(type, n, std::move(data), nulls > 0 ? std::move(mask) : rmm::device_buffer{0, stream, mr}, nulls);
-}
-
-// replacement: a column (repl_col) or the device value of a VALID scalar
-struct replacement_src {
-  void const* data{nullptr};
-  uint32_t const* valid{nullptr};
-  int64_t begin_bit{0};
-  int is_scalar{0};
-};
-replacement_src src_of(column_view const& c) { return {detail::row0(c), c.has_nulls() ? c.null_mask() : nullptr, c.offset(), 0}; }
-
-std::unique_ptr<column> run_replace(bool nans, column_view const& input, replacement_src const& r, rmm::cuda_stream_view stream,
+// `r`: the replacement column, or a scalar the caller has found VALID (its validity byte is not handed to the kernel)
+std::unique_ptr<column> run_replace(bool nans, column_view const& input, detail::source const& r, rmm::cuda_stream_view stream,
                                     rmm::device_async_resource_ref mr)
 {
   auto const n = input.size();
-  rmm::device_buffer data{static_cast<std::size_t>(n) * size_of(input.type()), stream, mr};
   // replace_nulls: a row is null where both sides are; replace_nans: where the input is, or a NaN row's replacement is
   bool const with_mask = nans ? (input.has_nulls() || r.valid != nullptr) : (input.has_nulls() && r.valid != nullptr);
-  auto mask            = create_null_mask(n, with_mask ? mask_state::UNINITIALIZED : mask_state::UNALLOCATED, stream, mr);
-  rmm::device_buffer nulls_dev{sizeof(int64_t), stream};
-  auto* out_valid  = with_mask ? static_cast<uint32_t*>(mask.data()) : nullptr;
-  auto* out_nulls  = with_mask ? static_cast<int64_t*>(nulls_dev.data()) : nullptr;
+  detail::result_column out{input.type(), n, with_mask, mask_state::UNINITIALIZED, stream, mr};
   auto const* ival = input.has_nulls() ? input.null_mask() : nullptr;
   if (nans)
     detail::gx_check(gx_replace_nans(detail::gx_type(input.type()), detail::row0(input), ival, input.offset(), r.data, r.valid, r.begin_bit,
-                                     nullptr, r.is_scalar, n, data.data(), out_valid, out_nulls, detail::gxs(stream)),
+                                     nullptr, r.is_scalar, n, out.data(), out.valid(), out.nulls_dev(), detail::gxs(stream)),
                      "gx_replace_nans");
   else
     detail::gx_check(gx_replace_nulls(static_cast<int>(size_of(input.type())), detail::row0(input), ival, input.offset(), r.data, r.valid,
-                                      r.begin_bit, nullptr, r.is_scalar, n, data.data(), out_valid, out_nulls, detail::gxs(stream)),
+                                      r.begin_bit, nullptr, r.is_scalar, n, out.data(), out.valid(), out.nulls_dev(), detail::gxs(stream)),
                      "gx_replace_nulls");
-  return finish(input.type(), n, std::move(data), std::move(mask), with_mask, nulls_dev, stream, mr);
+  return out.finish();
 }
 
 }  // namespace
@@ -89,7 +51,7 @@ std::unique_ptr<column> replace_nulls(column_view const& input, column_view cons
   CUDF_EXPECTS(input.size() == replacement.size(), "Column size mismatch", std::invalid_argument);
   if (input.size() == 0) return make_empty_column(input.type());
   if (!input.has_nulls()) return copy_of(input, stream, mr);
-  return run_replace(false, input, src_of(replacement), stream, mr);
+  return run_replace(false, input, detail::source_of(replacement), stream, mr);
 }
 
 std::unique_ptr<column> replace_nulls(column_view const& input, scalar const& replacement, rmm::cuda_stream_view stream,
@@ -98,8 +60,9 @@ std::unique_ptr<column> replace_nulls(column_view const& input, scalar const& re
   (void)detail::gx_type(input.type());
   CUDF_EXPECTS(input.type() == replacement.type(), "Data type mismatch", cudf::data_type_error);
   if (input.size() == 0) return make_empty_column(input.type());
+  auto const r = detail::source_of(replacement);
   if (!input.has_nulls() || !replacement.is_valid(stream)) return copy_of(input, stream, mr);
-  return run_replace(false, input, {scalar_value(replacement), nullptr, 0, 1}, stream, mr);
+  return run_replace(false, input, r, stream, mr);
 }
 
 std::unique_ptr<column> replace_nulls(column_view const& input, replace_policy const& policy, rmm::cuda_stream_view stream,
@@ -109,37 +72,36 @@ std::unique_ptr<column> replace_nulls(column_view const& input, replace_policy c
   auto const n = input.size();
   if (n == 0) return make_empty_column(input.type());
   if (!input.has_nulls()) return copy_of(input, stream, mr);
-  rmm::device_buffer data{static_cast<std::size_t>(n) * size_of(input.type()), stream, mr};
-  auto mask = create_null_mask(n, mask_state::UNINITIALIZED, stream, mr);
-  rmm::device_buffer nulls_dev{sizeof(int64_t), stream};
+  detail::result_column out{input.type(), n, true, mask_state::UNINITIALIZED, stream, mr};
   auto const tmp = detail::run_with_scratch(
     [&](void* tmp, std::size_t* bytes) {
       return gx_replace_nulls_policy(static_cast<int>(size_of(input.type())), detail::row0(input), input.null_mask(), input.offset(), n,
-                                     policy == replace_policy::FOLLOWING ? 1 : 0, data.data(), static_cast<uint32_t*>(mask.data()),
-                                     static_cast<int64_t*>(nulls_dev.data()), tmp, bytes, detail::gxs(stream));
+                                     policy == replace_policy::FOLLOWING ? 1 : 0, out.data(), out.valid(), out.nulls_dev(), tmp, bytes,
+                                     detail::gxs(stream));
     },
     "gx_replace_nulls_policy", stream);
-  return finish(input.type(), n, std::move(data), std::move(mask), true, nulls_dev, stream, mr);
+  return out.finish();
 }
 
 std::unique_ptr<column> replace_nans(column_view const& input, column_view const& replacement, rmm::cuda_stream_view stream,
                                      rmm::device_async_resource_ref mr)
 {
   CUDF_EXPECTS(input.type() == replacement.type(), "Data type mismatch", cudf::data_type_error);
-  CUDF_EXPECTS(is_float(input.type()), "nans replacement takes a floating-point column", std::invalid_argument);
+  CUDF_EXPECTS(is_floating_point(input.type()), "nans replacement takes a floating-point column", std::invalid_argument);
   CUDF_EXPECTS(input.size() == replacement.size(), "Column size mismatch", std::invalid_argument);
   if (input.size() == 0) return make_empty_column(input.type());
-  return run_replace(true, input, src_of(replacement), stream, mr);
+  return run_replace(true, input, detail::source_of(replacement), stream, mr);
 }
 
 std::unique_ptr<column> replace_nans(column_view const& input, scalar const& replacement, rmm::cuda_stream_view stream,
                                      rmm::device_async_resource_ref mr)
 {
   CUDF_EXPECTS(input.type() == replacement.type(), "Data type mismatch", cudf::data_type_error);
-  CUDF_EXPECTS(is_float(input.type()), "nans replacement takes a floating-point column", std::invalid_argument);
+  CUDF_EXPECTS(is_floating_point(input.type()), "nans replacement takes a floating-point column", std::invalid_argument);
   if (input.size() == 0) return make_empty_column(input.type());
+  auto const r = detail::source_of(replacement);
   if (!replacement.is_valid(stream)) return copy_of(input, stream, mr);
-  return run_replace(true, input, {scalar_value(replacement), nullptr, 0, 1}, stream, mr);
+  return run_replace(true, input, r, stream, mr);
 }
 
 std::unique_ptr<column> find_and_replace_all(column_view const& input, column_view const& values_to_replace,
@@ -155,17 +117,13 @@ std::unique_ptr<column> find_and_replace_all(column_view const& input, column_vi
   auto const n = input.size();
   if (n == 0) return make_empty_column(input.type());
   if (values_to_replace.size() == 0) return copy_of(input, stream, mr);
-  rmm::device_buffer data{static_cast<std::size_t>(n) * size_of(input.type()), stream, mr};
-  bool const with_mask = input.has_nulls() || replacement_values.has_nulls();
-  auto mask            = create_null_mask(n, with_mask ? mask_state::UNINITIALIZED : mask_state::UNALLOCATED, stream, mr);
-  rmm::device_buffer nulls_dev{sizeof(int64_t), stream};
+  detail::result_column out{input.type(), n, input.has_nulls() || replacement_values.has_nulls(), mask_state::UNINITIALIZED, stream, mr};
   detail::gx_check(gx_find_and_replace(dtype, detail::row0(input), input.has_nulls() ? input.null_mask() : nullptr, input.offset(), n,
                                        detail::row0(values_to_replace), detail::row0(replacement_values),
                                        replacement_values.has_nulls() ? replacement_values.null_mask() : nullptr, replacement_values.offset(),
-                                       values_to_replace.size(), data.data(), with_mask ? static_cast<uint32_t*>(mask.data()) : nullptr,
-                                       with_mask ? static_cast<int64_t*>(nulls_dev.data()) : nullptr, detail::gxs(stream)),
+                                       values_to_replace.size(), out.data(), out.valid(), out.nulls_dev(), detail::gxs(stream)),
                    "gx_find_and_replace");
-  return finish(input.type(), n, std::move(data), std::move(mask), with_mask, nulls_dev, stream, mr);
+  return out.finish();
 }
 
 std::unique_ptr<column> clamp(column_view const& input, scalar const& lo, scalar const& lo_replace, scalar const& hi,
@@ -183,11 +141,11 @@ std::unique_ptr<column> clamp(column_view const& input, scalar const& lo, scalar
   if (has_lo) CUDF_EXPECTS(lo_replace.is_valid(stream), "lo_replace can't be null if lo is not null", std::invalid_argument);
   if (has_hi) CUDF_EXPECTS(hi_replace.is_valid(stream), "hi_replace can't be null if hi is not null", std::invalid_argument);
   rmm::device_buffer data{static_cast<std::size_t>(n) * size_of(input.type()), stream, mr};
-  detail::gx_check(gx_clamp(dtype, detail::row0(input), n, has_lo ? scalar_value(lo) : nullptr, nullptr,
-                            has_lo ? scalar_value(lo_replace) : nullptr, has_hi ? scalar_value(hi) : nullptr, nullptr,
-                            has_hi ? scalar_value(hi_replace) : nullptr, data.data(), detail::gxs(stream)),
+  detail::gx_check(gx_clamp(dtype, detail::row0(input), n, has_lo ? scalar_device_value(lo) : nullptr, nullptr,
+                            has_lo ? scalar_device_value(lo_replace) : nullptr, has_hi ? scalar_device_value(hi) : nullptr, nullptr,
+                            has_hi ? scalar_device_value(hi_replace) : nullptr, data.data(), detail::gxs(stream)),
                    "gx_clamp");
-  return std::make_unique<column>(input.type(), n, std::move(data), mask_of(input, stream, mr), input.null_count());
+  return std::make_unique<column>(input.type(), n, std::move(data), detail::mask_of(input, stream, mr), input.null_count());
 }
 
 std::unique_ptr<column> clamp(column_view const& input, scalar const& lo, scalar const& hi, rmm::cuda_stream_view stream,
@@ -198,18 +156,18 @@ std::unique_ptr<column> clamp(column_view const& input, scalar const& lo, scalar
 
 std::unique_ptr<column> normalize_nans_and_zeros(column_view const& input, rmm::cuda_stream_view stream, rmm::device_async_resource_ref mr)
 {
-  CUDF_EXPECTS(is_float(input.type()), "Expects float or double input", std::invalid_argument);
+  CUDF_EXPECTS(is_floating_point(input.type()), "Expects float or double input", std::invalid_argument);
   auto const n = input.size();
   if (n == 0) return make_empty_column(input.type());
   rmm::device_buffer data{static_cast<std::size_t>(n) * size_of(input.type()), stream, mr};
   detail::gx_check(gx_normalize_nans_and_zeros(detail::gx_type(input.type()), detail::row0(input), n, data.data(), detail::gxs(stream)),
                    "gx_normalize_nans_and_zeros");
-  return std::make_unique<column>(input.type(), n, std::move(data), mask_of(input, stream, mr), input.null_count());
+  return std::make_unique<column>(input.type(), n, std::move(data), detail::mask_of(input, stream, mr), input.null_count());
 }
 
 void normalize_nans_and_zeros(mutable_column_view& in_out, rmm::cuda_stream_view stream)
 {
-  CUDF_EXPECTS(is_float(in_out.type()), "Expects float or double input", std::invalid_argument);
+  CUDF_EXPECTS(is_floating_point(in_out.type()), "Expects float or double input", std::invalid_argument);
   if (in_out.size() == 0) return;
   auto* p = in_out.head<char>() + static_cast<std::size_t>(in_out.offset()) * size_of(in_out.type());
   detail::gx_check(gx_normalize_nans_and_zeros(detail::gx_type(in_out.type()), p, in_out.size(), p, detail::gxs(stream)),

@@ -1,12 +1,10 @@
 // cudf::interleave_columns, cudf::tile and cudf::transpose over the C ABI (gx_interleave, gx_tile; cudf_amd/csrc/gx_reshape.hip).
 // reference: cpp/include/cudf/reshape.hpp, cpp/include/cudf/transpose.hpp, cpp/src/reshape/interleave_columns.cu, tile.cu,
 // cpp/src/transpose/transpose.cu.  One launch writes values, validity words and the null count; sliced views are read in place
-// (offset data pointer, begin bit).  A mask is allocated only when an input has nulls and kept only when the result does: the one
-// host read of these paths.  transpose is the interleave plus views: its per-view null counts come from one copy of the bitmap.
-#include "common.hpp"
+// (offset data pointer, begin bit); the result mask follows the contract of DESIGN.md 3.6 (result_column.hpp).
+// transpose is the interleave plus views: its per-view null counts come from one copy of the bitmap.
+#include "result_column.hpp"
 
-#include <cudf/column/column_factories.hpp>
-#include <cudf/null_mask.hpp>
 #include <cudf/reshape.hpp>
 #include <cudf/transpose.hpp>
 
@@ -49,17 +47,13 @@ std::unique_ptr<column> interleave(table_view const& input, data_type type, rmm:
     bits[j]       = c.offset();
     with_mask |= c.has_nulls();
   }
-  rmm::device_buffer data{static_cast<std::size_t>(total) * esz, stream, mr};
-  auto mask = create_null_mask(total, with_mask ? mask_state::UNINITIALIZED : mask_state::UNALLOCATED, stream, mr);
-  rmm::device_buffer nulls_dev{sizeof(int64_t), stream};
+  detail::result_column out{type, total, with_mask, mask_state::UNINITIALIZED, stream, mr};
   auto scratch = detail::run_with_scratch(
     [&](void* t, std::size_t* b) {
-      return gx_interleave(esz, k, cols.data(), valid.data(), bits.data(), n, data.data(), with_mask ? static_cast<uint32_t*>(mask.data()) : nullptr,
-                           with_mask ? static_cast<int64_t*>(nulls_dev.data()) : nullptr, t, b, detail::gxs(stream));
+      return gx_interleave(esz, k, cols.data(), valid.data(), bits.data(), n, out.data(), out.valid(), out.nulls_dev(), t, b, detail::gxs(stream));
     },
     "gx_interleave", stream);
-  auto const nulls = with_mask ? static_cast<size_type>(detail::read_i64(static_cast<int64_t const*>(nulls_dev.data()), stream)) : 0;
-  return std::make_unique<column>(type, total, std::move(data), nulls > 0 ? std::move(mask) : rmm::device_buffer{0, stream, mr}, nulls);
+  return out.finish();
 }
 
 }  // namespace
@@ -75,47 +69,18 @@ std::unique_ptr<table> tile_or_repeat_each(bool each, table_view const& input, s
   CUDF_EXPECTS(static_cast<int64_t>(n) * count <= size_max, "The result exceeds the column size limit", std::overflow_error);
   for (auto const& c : input) gx_type(c.type());
   auto const total = static_cast<size_type>(n * count);
-  std::vector<std::unique_ptr<column>> cols;
-  cols.reserve(nc);
-  if (total == 0) {
-    for (auto const& c : input) cols.emplace_back(make_empty_column(c.type()));
-    return std::make_unique<table>(std::move(cols));
-  }
-  struct part {
-    rmm::device_buffer data, mask;
-    bool with_mask;
-  };
-  std::vector<part> parts;
-  parts.reserve(nc);
-  rmm::device_uvector<int64_t> counts_dev(static_cast<std::size_t>(std::max<size_type>(nc, 1)), stream);
-  bool any_mask = false;
-  for (size_type k = 0; k < nc; ++k) {
-    auto const& c  = input.column(k);
+  if (total == 0) return empty_like_table(input);
+  result_table out{nc, stream, mr};
+  for (auto const& c : input) {
     auto const esz = static_cast<int>(size_of(c.type()));
-    part p{rmm::device_buffer{static_cast<std::size_t>(total) * esz, stream, mr},
-           create_null_mask(total, c.has_nulls() ? mask_state::UNINITIALIZED : mask_state::UNALLOCATED, stream, mr), c.has_nulls()};
-    auto* out_valid = p.with_mask ? static_cast<uint32_t*>(p.mask.data()) : nullptr;
-    auto* out_nulls = p.with_mask ? counts_dev.data() + k : nullptr;
-    auto const* iv  = p.with_mask ? c.null_mask() : nullptr;
+    auto& col      = out.add(c.type(), total, c.has_nulls(), mask_state::UNINITIALIZED);
+    auto const* iv = c.has_nulls() ? c.null_mask() : nullptr;
     if (each)
-      gx_check(gx_repeat_each(esz, row0(c), iv, c.offset(), n, count, p.data.data(), out_valid, out_nulls, gxs(stream)), "gx_repeat_each");
+      gx_check(gx_repeat_each(esz, row0(c), iv, c.offset(), n, count, col.data(), col.valid(), col.nulls_dev(), gxs(stream)), "gx_repeat_each");
     else
-      gx_check(gx_tile(esz, row0(c), iv, c.offset(), n, count, p.data.data(), out_valid, out_nulls, gxs(stream)), "gx_tile");
-    any_mask |= p.with_mask;
-    parts.emplace_back(std::move(p));
+      gx_check(gx_tile(esz, row0(c), iv, c.offset(), n, count, col.data(), col.valid(), col.nulls_dev(), gxs(stream)), "gx_tile");
   }
-  std::vector<int64_t> nulls(static_cast<std::size_t>(nc), 0);
-  if (any_mask) {  // all counts in one read (entries of columns without a mask are not written and not used)
-    CUDF_CUDA_TRY(hipMemcpyAsync(nulls.data(), counts_dev.data(), nulls.size() * sizeof(int64_t), hipMemcpyDeviceToHost, stream.value()));
-    stream.synchronize();
-  }
-  for (size_type k = 0; k < nc; ++k) {
-    auto& p      = parts[k];
-    auto const z = p.with_mask ? static_cast<size_type>(nulls[k]) : 0;
-    cols.emplace_back(std::make_unique<column>(input.column(k).type(), total, std::move(p.data),
-                                               z > 0 ? std::move(p.mask) : rmm::device_buffer{0, stream, mr}, z));
-  }
-  return std::make_unique<table>(std::move(cols));
+  return out.finish(total);
 }
 
 }  // namespace detail

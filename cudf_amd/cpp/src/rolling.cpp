@@ -3,10 +3,8 @@
 // fixed windows take a tile kernel with two segmented scans in LDS (constant work per row), the rest a row loop; the groups of
 // grouped_rolling_window are the runs of equal key rows: gx_group_heads per key column, then gx_group_offsets.
 // Stream-ordered up to the read of the null count, which decides whether the result keeps its mask.
-#include "common.hpp"
+#include "result_column.hpp"
 
-#include <cudf/column/column_factories.hpp>
-#include <cudf/null_mask.hpp>
 #include <cudf/rolling.hpp>
 
 #include <algorithm>
@@ -24,10 +22,9 @@ plan plan_of(column_view const& input, size_type min_periods, rolling_aggregatio
 {
   CUDF_EXPECTS(min_periods >= 0, "min_periods must be non-negative");
   auto const id = input.type().id();
-  CUDF_EXPECTS(static_cast<int>(id) >= GX_INT8 && static_cast<int>(id) <= GX_BOOL8, "rolling_window: the input must be a fixed-width numeric or BOOL8 column");
-  bool const is_float = id == type_id::FLOAT32 || id == type_id::FLOAT64;
+  CUDF_EXPECTS(detail::is_gx_type(input.type()), "rolling_window: the input must be a fixed-width numeric or BOOL8 column");
   switch (agg.kind) {
-    case aggregation::SUM: return {GX_OP_SUM, is_float ? input.type() : data_type{id == type_id::UINT64 ? type_id::UINT64 : type_id::INT64}};
+    case aggregation::SUM: return {GX_OP_SUM, is_floating_point(input.type()) ? input.type() : data_type{id == type_id::UINT64 ? type_id::UINT64 : type_id::INT64}};
     case aggregation::MIN: return {GX_OP_MIN, input.type()};
     case aggregation::MAX: return {GX_OP_MAX, input.type()};
     case aggregation::MEAN: return {GX_OP_MEAN, data_type{type_id::FLOAT64}};
@@ -43,15 +40,12 @@ std::unique_ptr<column> run(column_view const& input, plan const& pl, int64_t pr
 {
   auto const n = input.size();
   if (n == 0) return make_empty_column(pl.out_type);
-  rmm::device_buffer data{static_cast<std::size_t>(n) * size_of(pl.out_type), stream, mr};
-  auto mask = create_null_mask(n, mask_state::ALL_NULL, stream, mr);
-  rmm::device_buffer nulls_dev{sizeof(int64_t), stream};
+  detail::result_column out{pl.out_type, n, true, mask_state::ALL_NULL, stream, mr};  // any window can fall short of min_periods
   detail::gx_check(gx_rolling_window(detail::gx_type(input.type()), detail::row0(input), input.has_nulls() ? input.null_mask() : nullptr,
-                                     input.offset(), n, preceding, following, pcol, fcol, labels, offsets, min_periods, pl.op, data.data(),
-                                     static_cast<uint32_t*>(mask.data()), static_cast<int64_t*>(nulls_dev.data()), detail::gxs(stream)),
+                                     input.offset(), n, preceding, following, pcol, fcol, labels, offsets, min_periods, pl.op, out.data(),
+                                     out.valid(), out.nulls_dev(), detail::gxs(stream)),
                    "gx_rolling_window");
-  auto const nulls = static_cast<size_type>(detail::read_i64(static_cast<int64_t const*>(nulls_dev.data()), stream));
-  return std::make_unique<column>(pl.out_type, n, std::move(data), nulls > 0 ? std::move(mask) : rmm::device_buffer{0, stream, mr}, nulls);
+  return out.finish();
 }
 
 }  // namespace

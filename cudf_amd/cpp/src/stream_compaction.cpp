@@ -9,9 +9,8 @@
 // A selector writes the plan (selection bits + chunk starts) and the number of kept rows; that count is the one value read back
 // before the outputs are allocated, the null counts of all output columns come back in one more read behind the scatters.
 #include "ordered_rows.hpp"
+#include "result_column.hpp"
 
-#include <cudf/column/column_factories.hpp>
-#include <cudf/null_mask.hpp>
 #include <cudf/stream_compaction.hpp>
 
 #include <stdexcept>
@@ -19,51 +18,22 @@
 namespace cudf {
 namespace {
 
-std::unique_ptr<table> empty_like_table(table_view const& t)
-{
-  std::vector<std::unique_ptr<column>> cols;
-  cols.reserve(t.num_columns());
-  for (auto const& c : t) cols.emplace_back(make_empty_column(c.type()));
-  return std::make_unique<table>(std::move(cols));
-}
-
 // every column of `input` compacted from one plan
 std::unique_ptr<table> compact_table(table_view const& input, void const* plan, size_type count, rmm::cuda_stream_view stream,
                                      rmm::device_async_resource_ref mr)
 {
-  if (count == 0) return empty_like_table(input);
-  auto const n  = input.num_rows();
-  auto const nc = input.num_columns();
-  rmm::device_uvector<int64_t> nulls_dev(static_cast<std::size_t>(nc), stream);
-  std::vector<rmm::device_buffer> data, masks;
-  data.reserve(nc);
-  masks.reserve(nc);
-  bool any_mask = false;
-  for (size_type k = 0; k < nc; ++k) {
-    auto const& c  = input.column(k);
+  if (count == 0) return detail::empty_like_table(input);
+  auto const n = input.num_rows();
+  detail::result_table out{input.num_columns(), stream, mr};
+  for (auto const& c : input) {
     auto const esz = gx_dtype_size(detail::gx_type(c.type()));
-    data.emplace_back(static_cast<std::size_t>(count) * esz, stream, mr);
-    bool const with_mask = c.has_nulls();
-    masks.emplace_back(create_null_mask(count, with_mask ? mask_state::ALL_NULL : mask_state::UNALLOCATED, stream, mr));
-    any_mask |= with_mask;
-    detail::gx_check(gx_compact_column(esz, detail::row0(c), with_mask ? c.null_mask() : nullptr, c.offset(), n, plan, data.back().data(),
-                                       with_mask ? static_cast<uint32_t*>(masks.back().data()) : nullptr, nulls_dev.data() + k,
-                                       detail::gxs(stream)),
+    auto& col      = out.add(c.type(), count, c.has_nulls(), mask_state::ALL_NULL);
+    // the kernel writes its count with or without a mask
+    detail::gx_check(gx_compact_column(esz, detail::row0(c), c.has_nulls() ? c.null_mask() : nullptr, c.offset(), n, plan, col.data(), col.valid(),
+                                       col.count_slot(), detail::gxs(stream)),
                      "gx_compact_column");
   }
-  std::vector<int64_t> nulls(static_cast<std::size_t>(nc), 0);
-  if (any_mask) {
-    CUDF_CUDA_TRY(hipMemcpyAsync(nulls.data(), nulls_dev.data(), nulls.size() * sizeof(int64_t), hipMemcpyDeviceToHost, stream.value()));
-    stream.synchronize();
-  }
-  std::vector<std::unique_ptr<column>> cols;
-  cols.reserve(nc);
-  for (size_type k = 0; k < nc; ++k) {
-    auto const nk = static_cast<size_type>(nulls[k]);
-    cols.emplace_back(std::make_unique<column>(input.column(k).type(), count, std::move(data[k]),
-                                               nk > 0 ? std::move(masks[k]) : rmm::device_buffer{0, stream, mr}, nk));
-  }
-  return std::make_unique<table>(std::move(cols));
+  return out.finish(count);
 }
 
 // runs a selector (scratch-query convention, the count as a device word in front of it) and compacts the table from its plan
@@ -82,7 +52,7 @@ std::unique_ptr<table> select_and_compact(table_view const& input, Selector&& se
 std::unique_ptr<table> apply_boolean_mask(table_view const& input, column_view const& boolean_mask, rmm::cuda_stream_view stream,
                                           rmm::device_async_resource_ref mr)
 {
-  if (boolean_mask.is_empty()) return empty_like_table(input);  // (apply_boolean_mask: an empty mask gives empty_like(input))
+  if (boolean_mask.is_empty()) return detail::empty_like_table(input);  // (apply_boolean_mask: an empty mask gives empty_like(input))
   CUDF_EXPECTS(input.num_rows() == boolean_mask.size(), "Column size mismatch");
   CUDF_EXPECTS(boolean_mask.type().id() == type_id::BOOL8, "Mask must be Boolean type");
   if (input.num_columns() == 0) return std::make_unique<table>(input, stream, mr);

@@ -5,10 +5,8 @@
 // and the null count; sliced views are read in place (offset data pointer, begin bit), as binaryop.cpp does.  A mask is allocated
 // only when a column the expression reads is nullable or a literal is invalid, and kept only when a row is null: the one host read.
 #include "ast_lowering.hpp"
-#include "common.hpp"
+#include "result_column.hpp"
 
-#include <cudf/column/column_factories.hpp>
-#include <cudf/null_mask.hpp>
 #include <cudf/transform.hpp>
 
 #include <stdexcept>
@@ -50,9 +48,9 @@ int32_t flatten_expression(ast::expression const& e, table_view const& left, tab
     case ast::expression_kind::LITERAL: {
       auto const& lit = static_cast<ast::literal const&>(e);
       auto const& s   = lit.get_value();
-      CUDF_EXPECTS(s.device_value_ptr() != nullptr, "Only fixed-width scalars are supported on this path", cudf::data_type_error);
+      auto const* value = scalar_device_value(s);
       f.lit_dtypes.push_back(detail::gx_type(s.type()));
-      f.lits.push_back(gx_expr_literal{s.device_value_ptr(), reinterpret_cast<uint8_t const*>(s.validity_data()), f.lit_dtypes.back(), 0});
+      f.lits.push_back(gx_expr_literal{value, reinterpret_cast<uint8_t const*>(s.validity_data()), f.lit_dtypes.back(), 0});
       if (right == nullptr && left.num_rows() > 0) f.may_be_null = f.may_be_null || !s.is_valid(stream);  // a join asks for no mask
       node = gx_expr_node{GX_EXPR_LITERAL, 0, static_cast<int32_t>(f.lits.size()) - 1, 0};
       break;
@@ -97,17 +95,12 @@ std::unique_ptr<column> compute_column(table_view const& table, ast::expression 
   data_type const output_type{static_cast<type_id>(rc)};
   auto const n = table.num_rows();
   if (n == 0) return make_empty_column(output_type);
-  rmm::device_buffer data{static_cast<std::size_t>(n) * size_of(output_type), stream, mr};
-  bool const with_mask = f.may_be_null;
-  auto mask            = create_null_mask(n, with_mask ? mask_state::UNINITIALIZED : mask_state::UNALLOCATED, stream, mr);
-  rmm::device_buffer nulls_dev{sizeof(int64_t), stream};
+  detail::result_column out{output_type, n, f.may_be_null, mask_state::UNINITIALIZED, stream, mr};
   detail::gx_check(gx_compute_column(f.nodes.data(), static_cast<int>(f.nodes.size()), f.cols.data(), static_cast<int>(f.cols.size()),
-                                     f.lits.data(), static_cast<int>(f.lits.size()), n, rc, data.data(),
-                                     with_mask ? static_cast<uint32_t*>(mask.data()) : nullptr,
-                                     with_mask ? static_cast<int64_t*>(nulls_dev.data()) : nullptr, detail::gxs(stream)),
+                                     f.lits.data(), static_cast<int>(f.lits.size()), n, rc, out.data(), out.valid(), out.nulls_dev(),
+                                     detail::gxs(stream)),
                    "gx_compute_column");
-  auto const nulls = with_mask ? static_cast<size_type>(detail::read_i64(static_cast<int64_t const*>(nulls_dev.data()), stream)) : 0;
-  return std::make_unique<column>(output_type, n, std::move(data), nulls > 0 ? std::move(mask) : rmm::device_buffer{0, stream, mr}, nulls);
+  return out.finish();
 }
 
 }  // namespace cudf

@@ -11,16 +11,6 @@
 namespace cudf {
 namespace {
 
-// the validity of `input` as the mask of a new column of the same rows (empty without nulls)
-rmm::device_buffer mask_of(column_view const& input, rmm::cuda_stream_view stream, rmm::device_async_resource_ref mr)
-{
-  if (!input.has_nulls()) return rmm::device_buffer{0, stream, mr};
-  auto mask = create_null_mask(input.size(), mask_state::ALL_NULL, stream, mr);
-  detail::gx_check(gx_bitmask_copy(static_cast<uint32_t*>(mask.data()), 0, input.null_mask(), input.offset(), input.size(), detail::gxs(stream)),
-                   "gx_bitmask_copy");
-  return mask;
-}
-
 std::unique_ptr<column> run_unary(column_view const& input, int op, data_type out_type, rmm::cuda_stream_view stream,
                                   rmm::device_async_resource_ref mr)
 {
@@ -34,7 +24,7 @@ std::unique_ptr<column> run_unary(column_view const& input, int op, data_type ou
   if (n == 0) return make_empty_column(out_type);
   rmm::device_buffer data{static_cast<std::size_t>(n) * size_of(out_type), stream, mr};
   detail::gx_check(gx_unary_op(op, in, detail::row0(input), n, out, data.data(), detail::gxs(stream)), "gx_unary_op");
-  return std::make_unique<column>(out_type, n, std::move(data), mask_of(input, stream, mr), input.null_count());
+  return std::make_unique<column>(out_type, n, std::move(data), detail::mask_of(input, stream, mr), input.null_count());
 }
 
 std::unique_ptr<column> validity_as_bool(column_view const& input, bool invert, rmm::cuda_stream_view stream,
@@ -60,8 +50,7 @@ std::unique_ptr<column> unary_operation(column_view const& input, unary_operator
 
 bool is_supported_cast(data_type from, data_type to) noexcept
 {
-  auto const ok = [](data_type t) { return static_cast<int>(t.id()) >= GX_INT8 && static_cast<int>(t.id()) <= GX_BOOL8; };
-  return ok(from) && ok(to);
+  return detail::is_gx_type(from) && detail::is_gx_type(to);
 }
 
 std::unique_ptr<column> cast(column_view const& input, data_type out_type, rmm::cuda_stream_view stream, rmm::device_async_resource_ref mr)
@@ -73,7 +62,7 @@ std::unique_ptr<column> cast(column_view const& input, data_type out_type, rmm::
   detail::gx_check(gx_cast(static_cast<int>(input.type().id()), detail::row0(input), n, static_cast<int>(out_type.id()), data.data(),
                            detail::gxs(stream)),
                    "gx_cast");
-  return std::make_unique<column>(out_type, n, std::move(data), mask_of(input, stream, mr), input.null_count());
+  return std::make_unique<column>(out_type, n, std::move(data), detail::mask_of(input, stream, mr), input.null_count());
 }
 
 std::unique_ptr<column> is_null(column_view const& input, rmm::cuda_stream_view stream, rmm::device_async_resource_ref mr)

@@ -5,6 +5,8 @@
 #include <map>
 #include <tuple>
 #include <cudf/aggregation.hpp>
+#include <cudf/ast/expressions.hpp>
+#include <cudf/binaryop.hpp>
 #include <cudf/column/column_factories.hpp>
 #include <cudf/copying.hpp>
 #include <cudf/groupby.hpp>
@@ -14,8 +16,15 @@
 #include <cudf/join/filtered_join.hpp>
 #include <cudf/join/hash_join.hpp>
 #include <cudf/join/join.hpp>
+#include <cudf/quantiles.hpp>
 #include <cudf/reduction.hpp>
+#include <cudf/replace.hpp>
+#include <cudf/reshape.hpp>
+#include <cudf/rolling.hpp>
+#include <cudf/scalar/scalar.hpp>
 #include <cudf/sorting.hpp>
+#include <cudf/stream_compaction.hpp>
+#include <cudf/transform.hpp>
 #include <cudf_amd/gx.h>  // gx_sequence_i32: a device fill for the allocator test
 #include <chrono>
 #include <cudf_amd/device_faults.hpp>
@@ -1756,6 +1765,203 @@ int main()
     rb.reset();
     CHECK(hipStreamDestroy(s1) == hipSuccess);
     CHECK(hipStreamDestroy(s2) == hipSuccess);
+  });
+
+  // ---- the result-mask contract of the value entry points and their operand model, one entry point per family.
+  // The input: 33 rows seen through a slice at offset 1 of a 34-row column, so that the begin bit and a validity-word boundary are
+  // both in play.  Three inputs each: no mask, a mask with every row valid, one null in the last row -- bit 32 of a result whose
+  // rows map one to one.  Values, null_count() and nullable() (only with a null) against literals computed here.
+  constexpr size_type R = 33;
+  enum { NO_MASK, ALL_VALID_MASK, LAST_ROW_NULL };
+  struct sliced {
+    std::unique_ptr<column> owner;
+    column_view view;
+  };
+  auto slice33 = [](int which, auto v34) {  // v34: the 34 values of the owner; view row r holds v34[r + 1]
+    std::vector<int> valid;
+    if (which != NO_MASK) valid.assign(R + 1, 1);
+    if (which == LAST_ROW_NULL) valid[R] = 0;
+    auto owner = make_col(v34, valid);
+    auto view  = slice(owner->view(), {1, R + 1})[0];
+    return sliced{std::move(owner), view};
+  };
+  auto from = [](auto first) {  // view row r holds first + r
+    std::vector<decltype(first)> v(R + 1);
+    for (int i = 0; i <= R; ++i) v[i] = static_cast<decltype(first)>(first + (i - 1));
+    return v;
+  };
+  // nullable only with a null, the count the device's, the nulls where they belong
+  auto mask_is = [](column_view const& r, size_type rows, std::vector<int> const& null_rows) {
+    if (r.size() != rows || r.nullable() != !null_rows.empty() || r.null_count() != static_cast<size_type>(null_rows.size())) return false;
+    auto v = valid_host(r);
+    for (int i : null_rows) v[i] ^= 1;
+    return std::all_of(v.begin(), v.end(), [](int b) { return b == 1; });
+  };
+  // a scalar that is not fixed-width: no device value
+  struct opaque_scalar : scalar {
+    explicit opaque_scalar(type_id id) : scalar(data_type{id}, true) {}
+  };
+  auto const i32 = data_type{type_id::INT32};
+  int const cases[] = {NO_MASK, ALL_VALID_MASK, LAST_ROW_NULL};
+  auto nulls_of    = [](int w, int row) { return w == LAST_ROW_NULL ? std::vector<int>{row} : std::vector<int>{}; };
+
+  run("mask contract: binary_operation column o column and column o scalar", [&] {
+    numeric_scalar<int32_t> ten{10};
+    for (int w : cases) {
+      auto a = slice33(w, from(int32_t{1})), b = slice33(NO_MASK, from(int32_t{100}));
+      auto r = binary_operation(a.view, b.view, binary_operator::ADD, i32);
+      auto s = binary_operation(a.view, ten, binary_operator::ADD, i32);
+      CHECK(mask_is(r->view(), R, nulls_of(w, 32)) && mask_is(s->view(), R, nulls_of(w, 32)));
+      auto hr = to_host<int32_t>(r->view()), hs = to_host<int32_t>(s->view());
+      for (int i = 0; i < R - (w == LAST_ROW_NULL); ++i) CHECK(hr[i] == 101 + 2 * i && hs[i] == 11 + i);
+    }
+    auto a = slice33(NO_MASK, from(int32_t{1}));
+    opaque_scalar o{type_id::INT32};
+    CHECK(throws<data_type_error>([&] { (void)binary_operation(a.view, o, binary_operator::ADD, i32); }));
+    CHECK(throws<data_type_error>([&] { (void)binary_operation(o, a.view, binary_operator::ADD, i32); }));
+  });
+  run("mask contract: copy_if_else and scatter", [&] {
+    std::vector<uint8_t> even(R);
+    std::vector<int32_t> map(R), tv(R);
+    for (int i = 0; i < R; ++i) {
+      even[i] = i % 2 == 0;
+      map[i]  = i < 32 ? 31 - i : 32;
+      tv[i]   = 1000 + i;
+    }
+    auto eb = make_col(even);
+    column_view const m{data_type{type_id::BOOL8}, R, eb->view().head<void>(), nullptr, 0};
+    auto mp = make_col(map), target = make_col(tv);
+    for (int w : cases) {
+      auto a = slice33(w, from(int32_t{1})), b = slice33(NO_MASK, from(int32_t{100}));
+      auto r = copy_if_else(a.view, b.view, m);  // row 32 is even: the left side
+      CHECK(mask_is(r->view(), R, nulls_of(w, 32)));
+      auto h = to_host<int32_t>(r->view());
+      for (int i = 0; i < R - (w == LAST_ROW_NULL); ++i) CHECK(h[i] == (i % 2 == 0 ? 1 + i : 100 + i));
+      auto t = scatter(table_view{{a.view}}, mp->view(), table_view{{target->view()}});
+      CHECK(mask_is(t->get_column(0).view(), R, nulls_of(w, 32)));
+      h = to_host<int32_t>(t->get_column(0).view());
+      for (int j = 0; j < 32; ++j) CHECK(h[j] == 32 - j);  // row j was written from source row 31 - j
+      if (w != LAST_ROW_NULL) CHECK(h[32] == 33);
+    }
+    auto a = slice33(NO_MASK, from(int32_t{1}));
+    opaque_scalar o{type_id::INT32};
+    CHECK(throws<data_type_error>([&] { (void)copy_if_else(a.view, o, m); }));
+    CHECK(throws<data_type_error>([&] { (void)copy_if_else(o, a.view, m); }));
+    std::vector<std::reference_wrapper<scalar const>> src{o};
+    CHECK(throws<data_type_error>([&] { (void)scatter(src, mp->view(), table_view{{target->view()}}); }));
+  });
+  run("mask contract: replace_nulls (column, policy), replace_nans, find_and_replace_all", [&] {
+    auto with_nan = from(1.0);
+    with_nan[1 + 5] = std::nan("");  // view row 5
+    auto fb   = slice33(NO_MASK, from(100.0));
+    auto olds = make_col<int32_t>({3, 33}), news = make_col<int32_t>({-3, -33});
+    for (int w : cases) {
+      auto a = slice33(w, from(int32_t{1})), b = slice33(NO_MASK, from(int32_t{100}));
+      // the null row turns valid: no result is nullable
+      auto r = replace_nulls(a.view, b.view);
+      auto p = replace_nulls(a.view, replace_policy::PRECEDING);
+      CHECK(mask_is(r->view(), R, {}) && mask_is(p->view(), R, {}));
+      auto hr = to_host<int32_t>(r->view()), hp = to_host<int32_t>(p->view());
+      for (int i = 0; i < 32; ++i) CHECK(hr[i] == 1 + i && hp[i] == 1 + i);
+      CHECK(hr[32] == (w == LAST_ROW_NULL ? 132 : 33) && hp[32] == (w == LAST_ROW_NULL ? 32 : 33));
+      auto f = slice33(w, with_nan);
+      auto n = replace_nans(f.view, fb.view);
+      CHECK(mask_is(n->view(), R, nulls_of(w, 32)));
+      auto hn = to_host<double>(n->view());
+      for (int i = 0; i < R - (w == LAST_ROW_NULL); ++i) CHECK(hn[i] == (i == 5 ? 105.0 : 1.0 + i));
+      auto q = find_and_replace_all(a.view, olds->view(), news->view());
+      CHECK(mask_is(q->view(), R, nulls_of(w, 32)));
+      auto hq = to_host<int32_t>(q->view());
+      for (int i = 0; i < R - (w == LAST_ROW_NULL); ++i) CHECK(hq[i] == (i == 2 ? -3 : i == 32 ? -33 : 1 + i));
+    }
+    auto a = slice33(LAST_ROW_NULL, from(int32_t{1}));
+    auto f = slice33(NO_MASK, with_nan);
+    opaque_scalar o{type_id::INT32}, of{type_id::FLOAT64};
+    CHECK(throws<data_type_error>([&] { (void)replace_nulls(a.view, o); }));
+    CHECK(throws<data_type_error>([&] { (void)replace_nans(f.view, of); }));
+  });
+  run("mask contract: compute_column, interleave_columns, tile, apply_boolean_mask", [&] {
+    std::vector<uint8_t> keep(R, 1);
+    keep[0] = 0;
+    auto kb = make_col(keep);
+    column_view const m{data_type{type_id::BOOL8}, R, kb->view().head<void>(), nullptr, 0};
+    ast::column_reference c0{0}, c1{1};
+    ast::operation add{ast::ast_operator::ADD, c0, c1};
+    for (int w : cases) {
+      bool const z = w == LAST_ROW_NULL;
+      auto a = slice33(w, from(int32_t{1})), b = slice33(NO_MASK, from(int32_t{100}));
+      table_view const ab{{a.view, b.view}};
+      auto r = compute_column(ab, add);
+      CHECK(mask_is(r->view(), R, nulls_of(w, 32)));
+      auto h = to_host<int32_t>(r->view());
+      for (int i = 0; i < R - z; ++i) CHECK(h[i] == 101 + 2 * i);
+      auto il = interleave_columns(ab);  // a's row 32 is row 64
+      CHECK(mask_is(il->view(), 2 * R, nulls_of(w, 64)));
+      h = to_host<int32_t>(il->view());
+      for (int i = 0; i < R; ++i) CHECK((h[2 * i] == 1 + i || (z && i == 32)) && h[2 * i + 1] == 100 + i);
+      auto t = tile(table_view{{a.view}}, 2);  // the null row comes twice
+      CHECK(mask_is(t->get_column(0).view(), 2 * R, z ? std::vector<int>{32, 65} : std::vector<int>{}));
+      h = to_host<int32_t>(t->get_column(0).view());
+      for (int j = 0; j < 2 * R; ++j) CHECK(h[j] == 1 + j % R || (z && j % R == 32));
+      auto k = apply_boolean_mask(table_view{{a.view}}, m);  // row 0 dropped: the null is row 31
+      CHECK(mask_is(k->get_column(0).view(), R - 1, nulls_of(w, 31)));
+      h = to_host<int32_t>(k->get_column(0).view());
+      for (int j = 0; j < R - 1 - z; ++j) CHECK(h[j] == 2 + j);
+    }
+    auto a = slice33(NO_MASK, from(int32_t{1}));
+    numeric_scalar<int64_t> wide{1};
+    ast::literal lit{wide};
+    ast::operation mixed{ast::ast_operator::ADD, c0, lit};
+    CHECK(throws<data_type_error>([&] { (void)compute_column(table_view{{a.view}}, mixed); }));
+  });
+  run("mask contract: rolling_window and quantile", [&] {
+    for (int w : cases) {
+      bool const z = w == LAST_ROW_NULL;
+      auto a = slice33(w, from(int32_t{1}));
+      auto r = rolling_window(a.view, 1, 0, 1, *make_sum_aggregation<rolling_aggregation>());  // each window is its row
+      CHECK(r->type().id() == type_id::INT64 && mask_is(r->view(), R, nulls_of(w, 32)));
+      auto h = to_host<int64_t>(r->view());
+      for (int i = 0; i < R - z; ++i) CHECK(h[i] == 1 + i);
+      auto q = quantile(a.view, {0.0, 0.5, 1.0}, interpolation::LOWER);  // reads rows 0, 16 and 32
+      CHECK(mask_is(q->view(), 3, nulls_of(w, 2)));
+      auto hq = to_host<double>(q->view());
+      CHECK(hq[0] == 1.0 && hq[1] == 17.0 && (z || hq[2] == 33.0));
+    }
+  });
+  run("mask contract: hash groupby SUM and MIN, sort groupby SUM", [&] {
+    std::vector<int32_t> mod(R + 1), runs(R + 1);  // the last view row is a group of its own
+    for (int i = 0; i <= R; ++i) {
+      int const row = i - 1;
+      mod[i]        = row < 32 ? (row & 1) : 2;
+      runs[i]       = row < 16 ? 0 : row < 32 ? 1 : 2;
+    }
+    for (int w : cases) {
+      bool const z = w == LAST_ROW_NULL;
+      auto a = slice33(w, from(int32_t{1})), km = slice33(NO_MASK, mod), kr = slice33(NO_MASK, runs);
+      std::vector<groupby::aggregation_request> reqs(1);
+      reqs[0].values = a.view;
+      reqs[0].aggregations.push_back(make_sum_aggregation<groupby_aggregation>());
+      reqs[0].aggregations.push_back(make_min_aggregation<groupby_aggregation>());
+      groupby::groupby hashed{table_view{{km.view}}};
+      auto [k, res] = hashed.aggregate(reqs);
+      auto [kh, idx] = by_key(*k, res[0].results);
+      CHECK(kh.size() == 3);
+      auto const& sum = *res[0].results[0];
+      auto const& mn  = *res[0].results[1];
+      CHECK(mask_is(sum.view(), 3, nulls_of(w, idx[2])) && mask_is(mn.view(), 3, nulls_of(w, idx[2])));
+      auto hs = to_host<int64_t>(sum.view());
+      auto hm = to_host<int32_t>(mn.view());
+      CHECK(kh[idx[0]] == 0 && hs[idx[0]] == 256 && hm[idx[0]] == 1);  // rows 0, 2, .. 30: 1 + 3 + .. + 31
+      CHECK(kh[idx[1]] == 1 && hs[idx[1]] == 272 && hm[idx[1]] == 2);  // rows 1, 3, .. 31: 2 + 4 + .. + 32
+      CHECK(kh[idx[2]] == 2 && (z || (hs[idx[2]] == 33 && hm[idx[2]] == 33)));
+      reqs[0].aggregations.pop_back();
+      groupby::groupby sorted_keys{table_view{{kr.view}}, null_policy::EXCLUDE, sorted::YES};
+      auto [k2, res2] = sorted_keys.aggregate(reqs);
+      CHECK((to_host<int32_t>(k2->view().column(0)) == std::vector<int32_t>{0, 1, 2}));
+      CHECK(mask_is(res2[0].results[0]->view(), 3, nulls_of(w, 2)));
+      auto h2 = to_host<int64_t>(res2[0].results[0]->view());
+      CHECK(h2[0] == 136 && h2[1] == 392 && (z || h2[2] == 33));  // 1 + .. + 16, 17 + .. + 32
+    }
   });
 
   std::printf("%d run, %d failed\n", g_run, g_failed);
